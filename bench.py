@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the xlating-FIR hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps), times exactly K steps once, and prints the line.  `--dump-outputs DIR` then writes the
+outputs of the last timed call (a seeded sample of clients, dump_outputs) as DIR/*.npy.  `--full` adds everything else below: the
+timed region repeated REPEATS times (median), parity_spot, the per-kernel pass, the variants and native run, the in-run counter
+passes and the cpu_baseline.
 
 N > 1 without a torch.distributed environment re-launches itself under `python -m torch.distributed.run` (one rank per
 GPU, rendezvous on 127.0.0.1); inside such a launch (RANK / WORLD_SIZE set, e.g. by the driver) it just runs its rank.
@@ -18,14 +23,15 @@ of 8 consecutive blocks (xlating_batch_process_device_group) -- results identica
 
 A "step" = one pass of the hot path over one batch of synthetic input = BLOCKS_PER_STEP consecutive blocks (240 calls of
 8 blocks, 252 M samples of the stream) for every client of every GPU.  The timed region (exactly `--steps` steps between
-barrier + synchronize on both sides, max over ranks) is repeated REPEATS = 3 times; `value` / `ms_per_step` are the
-MEDIAN repeat, all three are printed ("repeats").  20 steps ~ 1.1 s per repeat at 1024 clients.
+barrier + synchronize on both sides, max over ranks) runs once; with `--full` it is repeated REPEATS = 3 times and `value` /
+`ms_per_step` are the MEDIAN repeat, all three are printed ("repeats").  20 steps ~ 1.1 s per repeat at 1024 clients.
     N > 1: rank 0's blocks are broadcast over RCCL/xGMI, 8 blocks per broadcast, on a side stream (the path's only
     exchange step), then each rank runs its own clients on them -- no further communication.
 Inputs are synthetic (xorshift bytes), already resident in HBM when the timed region starts.
 
-Prints ONE JSON line (rank 0): value = input IQ Msamples/s summed over all clients and GPUs.
-"roofline":     PHYSICAL: "traffic" = HBM bytes one call's launches move by the PMC counters (FETCH_SIZE / WRITE_SIZE in
+Prints ONE JSON line (rank 0): value = input IQ Msamples/s summed over all clients and GPUs.  The entries below marked [--full]
+are measured only with `--full`; a plain run's "traffic" is the committed digest profiles/pmc_latest.json, and it says so.
+"roofline":     PHYSICAL [counters: --full]: "traffic" = HBM bytes one call's launches move by the PMC counters (FETCH_SIZE / WRITE_SIZE in
                 separate rocprofv3 passes over `bench.py --replay-calls`, run as subprocesses right after the timed region
                 -- "traffic_source" says "measured in this run", or names the committed file it fell back to), "achieved" =
                 traffic / the mean duration of a call's launches (HIP events on the launch stream inside the timed region),
@@ -33,12 +39,12 @@ Prints ONE JSON line (rank 0): value = input IQ Msamples/s summed over all clien
                 the ceiling that binds each launch.  The per-client-read MODEL of SURVEY 8(d) (2 B in + 8/D B out per
                 (client, sample): every client "reads" the block the engine reads once) is kept as "model_frac" -- it is
                 not traffic and can exceed 1.
-"parity_spot":  after the timed region EVERY client of this GPU is fetched and compared with a population of oracle filters
+"parity_spot":  [--full] after the timed region EVERY client of this GPU is fetched and compared with a population of oracle filters
                 run on the host cores (oracle/population.c; stream state fast-forwarded over the run: phase recurrence
                 only, then one real super-block to load the history, the next one compared).
-"native":       the same workload with the reference's default arithmetic (cpu_optimization NATIVE_CF32,
+"native":       [--full] the same workload with the reference's default arithmetic (cpu_optimization NATIVE_CF32,
                 src/config.c:252-264): bit-exact scalar order, direct FIR kernel.
-"variants":     context for the headline, each a short run of its own on this box: other filter lengths / call granularities / client
+"variants":     [--full] context for the headline, each a short run of its own on this box: other filter lengths / call granularities / client
                 counts (2048 and 4096: where the launches, not the recurrence, bound the call -- the 2048 one with its own counters
                 and EVERY client checked); "polyphase, float32 matrix-core mix": the all-float32 arithmetic (option mix_kernel = 3),
                 every client checked; "inverse launch A/B in this process": the size rule's inverse kernel and its alternate alternating on this box;
@@ -47,7 +53,7 @@ Prints ONE JSON line (rank 0): value = input IQ Msamples/s summed over all clien
                 "host-delivered outputs": process_host + fetch per call (PCIe-inclusive; never `value`).
 "roofline.frac_algorithmic_shared": SURVEY 8(d)'s shared-read minimum (2/N B in + 8/D B out per (client, sample)) over the launches' own
                 time / 8 TB/s -- the USEFUL fraction, next to the counter fraction `frac`.
-"cpu_baseline": the reference itself (oracle/_ref, unmodified sources, -O3 -ffast-math AVX2) -- or the repo's CPU
+"cpu_baseline": [--full] the reference itself (oracle/_ref, unmodified sources, -O3 -ffast-math AVX2) -- or the repo's CPU
                 restatement when that build is absent -- timed on this box's host cores on a bounded sample.
 """
 import argparse
@@ -175,13 +181,16 @@ class PlumbingEngine:
     def timing(self, *a):
         pass
 
-    timing_stride = sync = close = timing
+    timing_stride = sync = close = fetch = timing
 
     def timing_read(self, reset=True):
         return 0, 0.0, 0.0
 
     def output_len(self, cid):
         return 0
+
+    def output(self, cid):
+        return np.zeros(0, np.complex64)
 
 
 class GroupFeeder:
@@ -376,11 +385,12 @@ def make_host(ctx, group):
 
 
 def run_workload(ctx, total_clients, ntaps_rate, steps, warmup, mode, group=GROUP, options=None, staggered=False,
-                 spot=False, poly3=True, blocks_per_step=BLOCKS_PER_STEP, repeats=1, replay_calls=0):
+                 spot=False, poly3=True, blocks_per_step=BLOCKS_PER_STEP, repeats=1, replay_calls=0, dump_dir=None):
     """Build this rank's engine with its shard of clients and time `repeats` x `steps` steps.  Returns dict of measurements.
     options: engine plan options (xlating_batch_set_option); staggered: the clients join over 21 consecutive blocks
     before the warm-up (every join lands on another output grid) instead of all before block 0.
-    replay_calls > 0: no timing at all -- warm up, run that many calls, return (the PMC passes profile this)."""
+    replay_calls > 0: no timing at all -- warm up, run that many calls, return (the PMC passes profile this).
+    dump_dir: rank 0 writes the outputs of the last timed call there (dump_outputs), before anything else runs on the engine."""
     xl, torch, dist, rank, world = ctx["xl"], ctx["torch"], ctx["dist"], ctx["rank"], ctx["world"]
     cuda = ctx["cuda"]
     code, taps = ctx["lpf"](1.0, FS, RATE // 2, RATE // ntaps_rate)
@@ -448,6 +458,8 @@ def run_workload(ctx, total_clients, ntaps_rate, steps, warmup, mode, group=GROU
                            "broadcast that elapsed while the previous feed's launches were still running on the compute stream"}
     nt, fir_ms, nco_ms = eng.timing_read(reset=True)
     eng.timing(False)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, eng, ids, mine)
     dt = sorted(secs)[len(secs) // 2]
     plan = eng.describe()
     polyphase = mode == "optimized" and "polyphase: none" not in plan
@@ -478,6 +490,31 @@ def run_workload(ctx, total_clients, ntaps_rate, steps, warmup, mode, group=GROU
             "plan": plan, "polyphase": polyphase, "kernels_ms": kernels_ms, "group": group, "steps": steps,
             "parity_spot": spot_res, "rank_seconds": rank_secs, "feed_timing": feed,
             "rccl_comm_count": getattr(host, "comm_count", None)}
+
+
+DUMP_CLIENTS = 64               # --dump-outputs: clients whose outputs are written (a fixed, seeded sample of rank 0's clients)
+DUMP_SEED = 0x5EED
+DUMP_MAX_BYTES = 48 << 20       # well inside the 64 MB the dump may hold
+
+
+def dump_outputs(out_dir, eng, ids, mine):
+    """`--dump-outputs DIR`: what the timed path handed its callers in its last step -- the outputs of its last call (GROUP blocks),
+    fetched from the engine the way a caller takes them (fetch + output), for a fixed, seeded sample of rank 0's clients:
+      outputs.npy  float32 [clients, outputs per client, 2] (re, im)
+      clients.npy  float64 [clients, 2] (global client index, centre frequency in Hz)
+    The inputs are seeded, so two builds run with the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    eng.fetch()
+    k = max((eng.output_len(ids[c]) for c in mine[:1]), default=0)
+    n = min(DUMP_CLIENTS, len(mine), DUMP_MAX_BYTES // max(8 * k, 1))
+    pick = sorted(np.random.default_rng(DUMP_SEED).choice(len(mine), size=n, replace=False).tolist())
+    outs = [eng.output(ids[mine[i]]) for i in pick]
+    if len({o.size for o in outs}) > 1:
+        raise RuntimeError(f"bench.py: the sampled clients' last calls hold different output counts: {sorted({o.size for o in outs})}")
+    kout = outs[0].size if outs else 0
+    y = np.stack(outs).view(np.float32) if outs else np.zeros(0, np.float32)
+    np.save(os.path.join(out_dir, "outputs.npy"), np.ascontiguousarray(y.reshape(len(outs), kout, 2)))
+    np.save(os.path.join(out_dir, "clients.npy"), np.array([[mine[i], client_center_freq(mine[i])] for i in pick], np.float64).reshape(-1, 2))
 
 
 def config5_center_freq(c, n):
@@ -1042,7 +1079,7 @@ EXPECTED_WEAK = {"clients_per_gpu": 1024, "Msamples_per_s_per_gpu": "5.3e6 - 5.5
 
 
 COMPACT_MAX_BYTES = 4096  # the driver keeps an 8 KB tail of stdout: the one line it parses must fit with room to spare
-FULL_JSON_DEFAULT = os.path.join(ROOT, "profiles", "bench_last_full.json")
+FULL_JSON_DEFAULT = os.path.join(ROOT, "bench_out", "bench_last_full.json")  # (git-ignored: a run leaves the tree clean)
 
 # compact `configs` keys <- prefix of the full record's variants[...] key
 CONFIG_KEYS = (("one_block_per_call", "one block per call"), ("config3_64_mixed_clients", "config 3"), ("config2_dropin_single_filter", "config 2"),
@@ -1148,7 +1185,12 @@ def main():
     ap.add_argument("--replay-calls", type=int, default=0, help=argparse.SUPPRESS)  # the counter passes profile this: no timing, N calls
     ap.add_argument("--replay-set", default="", help=argparse.SUPPRESS)  # ... of each of these workloads, back to back ("server:1024,config5:1024")
     ap.add_argument("--plumbing-test", action="store_true", help=argparse.SUPPRESS)  # tests/test_bench_launch.py only
-    ap.add_argument("--full-json", default=None, help="where the full record goes (default profiles/bench_last_full.json; the stdout line is the compact one)")
+    ap.add_argument("--full-json", default=None, help="where the full record goes (default bench_out/bench_last_full.json; the stdout line is the compact one)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: median of 3 timed repeats, parity_spot, per-kernel durations, variants, the "
+                         "native run, the in-run counter passes and the cpu_baseline (a plain run times --steps steps once and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed call (a seeded sample of clients) to DIR/*.npy")
     args = ap.parse_args()
 
     if "RANK" not in os.environ and args.gpus > 1:
@@ -1207,13 +1249,14 @@ def main():
         return
     bps = BLOCKS_PER_STEP if cuda else 64
     m = run_workload(ctx, total_clients, args.lpf_cutoff_rate, args.steps, args.warmup, args.mode,
-                     spot=not args.no_spot, blocks_per_step=bps, repeats=REPEATS)
+                     spot=args.full and not args.no_spot, poly3=args.full, blocks_per_step=bps, repeats=REPEATS if args.full else 1,
+                     dump_dir=args.dump_outputs)
     value, model_gbs, ach_tf, bpu, fpu = summarize(m)
 
     variants = {}
     native = None
     VB = 320  # blocks per step of the variants (their number is context, not the headline)
-    if not args.no_variants and (cuda or world > 1):
+    if args.full and not args.no_variants and (cuda or world > 1):
         vs = max(2, args.steps // 4)
         other_mode = "native" if args.mode == "optimized" else "optimized"
         if cuda:
@@ -1299,7 +1342,7 @@ def main():
     k5 = next((k for k in variants if k.startswith("config 5")), None)
     kb = next((k for k in variants if k.startswith("2048 clients")), None)
     pmc_all = None
-    if cuda and world == 1 and not args.no_pmc:
+    if cuda and world == 1 and args.full and not args.no_pmc:
         wls = [f"server:{total_clients}"] + ([f"server:2048"] if kb and args.clients == 1024 else []) + (["config5:1024"] if k5 else [])
         pmc_all, note = measure_traffic(args, wls)
         if pmc_all:
@@ -1421,10 +1464,14 @@ def main():
                                          "concurrent with the three launches; bounds the engine below ~1500 clients",
                                          "note": "bytes per CALL, ms per LAUNCH (one launch tabulates the phase tables of four calls); in the timed region a "
                                                  "call cannot be shorter than a quarter of a chain launch, so that launch is at most 4 x call_period_ms"}
-        roofline["kernel"] = ("xlp_forward_kernel + " + ("xlp_mix_mfma_kernel" if "mix=mfma" in m["plan"] else "xlp_mix_f32_kernel") + " + " + next((k for k in (m["kernels_ms"] or {}) if k.startswith("xlp_inverse")), "xlp_inverse_kernel") + ": the three launches of one call on the polyphase "
+        # (the launches' names: from the per-kernel pass (--full), else from the plan, as run_workload names them)
+        launches = list(m["kernels_ms"] or {}) or ["xlp_forward_kernel", "xlp_mix_mfma_kernel" if "mix=mfma" in m["plan"] else "xlp_mix_f32_kernel",
+                                                   "xlp_inverse8_kernel" if "inv=lanes8" in m["plan"] else
+                                                   ("xlp_inverse32_kernel" if "inv=cut32" in m["plan"] else "xlp_inverse_kernel")]
+        roofline["kernel"] = ("xlp_forward_kernel + " + ("xlp_mix_mfma_kernel" if "mix=mfma" in m["plan"] else "xlp_mix_f32_kernel") + " + " + next((k for k in launches if k.startswith("xlp_inverse")), "xlp_inverse_kernel") + ": the three launches of one call on the polyphase "
                               "overlap-save path (the next call's NCO phase recurrence runs beside them on a side stream)")
         roofline["per_kernel"] = pk
-        roofline["kernel_short"] = "+".join(k.replace("_kernel", "") for k in (m["kernels_ms"] or {})) + " (the 3 launches of one call)"
+        roofline["kernel_short"] = "+".join(k.replace("_kernel", "") for k in launches) + " (the 3 launches of one call)"
         # what bounds the STEP at this client count: the next call's float32 NCO phase recurrence (the reference's own p *= incr chain,
         # src/xlating.c:70-73: 3121 dependent steps per block and client) runs beside the launches on reserved CUs; one chain launch
         # tabulates CHAIN_CALLS calls.  frac_of_recurrence_floor = its share of the call period: ~1 = the step IS the recurrence
@@ -1518,7 +1565,7 @@ def main():
                              "note": "what DESIGN.md section 8 (history: DESIGN_HISTORY.md section 7) predicts for --gpus 1/2/4/8, to judge a measured curve against"},
         "device": xl.device_info() if cuda else "none (plumbing test)",
     }
-    if world == 1 and not args.no_cpu_baseline and cuda:
+    if world == 1 and args.full and not args.no_cpu_baseline and cuda:
         out["cpu_baseline"] = cpu_baseline(args.lpf_cutoff_rate, args.cpu_seconds)
     # the full record goes to a file; stdout gets ONE compact line (<= 4 KB) the driver can parse
     full_path = args.full_json or (FULL_JSON_DEFAULT if cuda else os.path.join("/tmp", f"xl_bench_full_{os.getpid()}.json"))

@@ -45,7 +45,7 @@ def _run(extra, env_extra=None, timeout=300, variants=False, compact=False):
 
 
 def test_self_launch_two_ranks_strong_scaling():
-    j = _run(["--gpus", "2", "--scaling", "strong"])
+    j = _run(["--gpus", "2", "--scaling", "strong", "--full"])
     assert j["n_gpus"] == 2 and j["steps"] == 2 and j["warmup"] == 1
     assert j["scaling"] == "strong" and j["config"]["clients_total"] == 1024  # BASELINE configs[3]: 1024 clients in total
     assert j["config"]["rccl_ranks"] == 2
@@ -53,7 +53,7 @@ def test_self_launch_two_ranks_strong_scaling():
     assert j["data"] == "cpu-plumbing-test" and j["value"] > 0
     blocks_per_step = int(j["config"]["step"].split()[0])
     assert abs(j["ms_per_step"] * j["steps"] / 1e3 - j["config"]["us_per_block"] * blocks_per_step * j["steps"] / 1e6) < 1e-3
-    # the timed region is repeated; the line reports the median repeat and shows all of them
+    # --full: the timed region is repeated; the line reports the median repeat and shows all of them
     assert j["repeats"]["n"] == 3 and j["repeats"]["median"] == j["ms_per_step"] and len(j["repeats"]["values"]) == 3
     assert j["roofline"]["frac"] <= 1.0 and "model_frac" in j["roofline"]["algorithmic"]
     assert set(j["expected_scaling"]["strong"]["Msamples_per_s"]) == {"1", "2", "4", "8"}
@@ -111,6 +111,22 @@ def test_compact_line_of_a_fully_populated_record_stays_under_4096_bytes():
     assert c["roofline"]["per_kernel"]["xlp_inverse32"] == {"ms": 0.1029, "frac_hbm": 0.5406}
 
 
+def test_plain_run_times_the_steps_once_and_dumps_the_last_call(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps, one timed region, no variants / native / cpu_baseline / parity_spot; the
+    result line keeps its contract keys.  --dump-outputs DIR writes the last timed call's outputs of a seeded client sample as .npy."""
+    import numpy as np
+
+    for gpus in ("1", "2"):  # (weak scaling: 64 clients per GPU, rank 0 holds clients 0, N, 2N, ...)
+        d = tmp_path / f"dump{gpus}"
+        c, _, j = _run(["--gpus", gpus, "--clients", "64", "--dump-outputs", str(d)], variants=True, compact=True)
+        assert j["steps"] == 2 and j["repeats"]["n"] == 1 and j["repeats"]["ms_per_step"] == [j["ms_per_step"]]
+        assert not j["variants"] and j["native"] is None and j["parity_spot"] is None and "cpu_baseline" not in j
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(c) and c["ms_per_step"] > 0
+        y, cl = np.load(d / "outputs.npy"), np.load(d / "clients.npy")
+        assert y.dtype == np.float32 and y.ndim == 3 and y.shape[2] == 2 and cl.dtype == np.float64
+        assert y.shape[0] == cl.shape[0] == 64 and set(cl[:, 0].astype(int)) <= set(range(0, 64 * int(gpus), int(gpus)))
+
+
 def test_world_size_mismatch_is_refused():
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--plumbing-test", "--gpus", "2"], capture_output=True,
@@ -121,7 +137,7 @@ def test_world_size_mismatch_is_refused():
 def test_two_ranks_line_carries_strong_and_weak_fully_populated():
     """N > 1: ONE line with both ways to use the GPUs -- the headline's scaling mode and the other one -- each with its value, step
     time and every rank's wall time of every timed repeat (the value uses the max over ranks)."""
-    j = _run(["--gpus", "2", "--clients", "64"], variants=True)
+    j = _run(["--gpus", "2", "--clients", "64", "--full"], variants=True)
     mg = j["multi_gpu"]
     assert set(mg) >= {"strong", "weak"} and mg["weak"]["value"] == j["value"] and mg["weak"]["clients_total"] == 128
     assert mg["strong"]["value"] > 0 and mg["strong"]["ms_per_step"] > 0

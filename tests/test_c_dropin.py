@@ -62,17 +62,16 @@ def test_c_caller_output_matches_oracle(variant):
             assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max(), call
 
 
-# ---- the reference's OWN callers (test/perf_xlating.c, test/test_xlating.c), compiled where they lie against the
-# reference's own headers and linked to libxlating_hip.so by tests/c/Makefile -> tests/c/_refbin/ (shipped to the GPU box)
-REFBIN = os.path.join(ROOT, "tests", "c", "_refbin")
+# ---- the reference's OWN callers (test/perf_xlating.c, test/test_xlating.c), compiled by build() where they lie against the
+# reference's own headers and linked to libxlating_hip.so (oracle/Makefile) -> oracle/_ref/, which travels with the built tree
+REFBIN = os.path.join(ROOT, "oracle", "_ref")
+REFBIN_MISSING = "oracle/_ref has no reference callers (the reference's sources were absent when build() ran)"
 API = ["create_low_pass_filter", "create_frequency_xlating_filter", "process_native_cu8_cf32",
        "process_optimized_cu8_cf32", "process_native_cu8_cs16", "process_optimized_cu8_cs16"]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/test/perf_xlating.c"), reason="build container only (needs /root/reference)")
+@pytest.mark.skipif(not all(os.path.exists(os.path.join(REFBIN, e)) for e in ("perf_xlating_hip", "test_xlating_hip")), reason=REFBIN_MISSING)
 def test_reference_callers_link_against_the_library():
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "c")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
     perf, unit = os.path.join(REFBIN, "perf_xlating_hip"), os.path.join(REFBIN, "test_xlating_hip")
     und = subprocess.run(["nm", "-u", perf], capture_output=True, text=True).stdout
     for sym in API:
@@ -93,7 +92,7 @@ def test_reference_unit_test_passes_against_the_library():
     """test/test_xlating.c (Unity): its three tests with the reference's expected arrays, run unmodified on the GPU."""
     exe = os.path.join(REFBIN, "test_xlating_hip")
     if not os.path.exists(exe):
-        pytest.skip("tests/c/_refbin not built (needs the build container)")
+        pytest.skip(REFBIN_MISSING)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert "3 Tests 0 Failures 0 Ignored" in r.stdout, r.stdout[-2000:]
@@ -104,7 +103,7 @@ def test_reference_perf_program_runs_against_the_library():
     """test/perf_xlating.c: 4 x 1000 calls of 200000 bytes through the drop-in API; prints SIMD_STATUS and four timings."""
     exe = os.path.join(REFBIN, "perf_xlating_hip")
     if not os.path.exists(exe):
-        pytest.skip("tests/c/_refbin not built (needs the build container)")
+        pytest.skip(REFBIN_MISSING)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-1000:]
     assert "SIMD optimization: HIP gfx950" in r.stdout

@@ -18,9 +18,9 @@ for step in "$@"; do
             tail -4 $OUT/pytest_gpu.txt ;;
     testsx) timeout 1200 python -m pytest tests -m gpu -q -x --timeout=600 > $OUT/pytest_gpu.txt 2>&1; tail -15 $OUT/pytest_gpu.txt ;;
     smoke)  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tee $OUT/smoke.txt | tail -3 ;;
-    bench)  ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_stdout.txt 2> $OUT/bench.err ) 2>&1 | grep real
+    bench)  ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_stdout.txt 2> $OUT/bench.err ) 2>&1 | grep real
             tail -3 $OUT/bench.err; wc -c $OUT/bench_stdout.txt; tail -1 $OUT/bench_stdout.txt
-            cp profiles/bench_last_full.json $OUT/bench_full.json 2>/dev/null ;;
+            cp bench_out/bench_last_full.json $OUT/bench_full.json 2>/dev/null ;;
     stats)  stats bench python $GRAFT_REPO_ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-variants --no-spot --no-pmc ;;
     stats5) stats config5_1024clients python $GRAFT_REPO_ROOT/tools/group_sweep.py --shape config5 --clients 1024 --groups 8 --modes optimized --blocks 640
             grep optimized $OUT/prof_config5_1024clients.log ;;
