@@ -13,7 +13,8 @@
  *
  * Semantics kept from the reference (file:line are into /root/reference/src/xlating.c):
  *  - create takes OWNERSHIP of `taps` on success and on EVERY failure (-ENOMEM like the reference, and this
- *    library's -ENODEV no usable device / -EINVAL bad shape / -EIO HIP error: the caller, dsp_worker.c:98-107,
+ *    library's -ENODEV no usable device / -EINVAL null taps or filter pointer, decimation 0 / -EIO HIP error; every
+ *    (decimation, taps_len) is accepted, as in the reference: the caller, dsp_worker.c:98-107,
  *    assumes the hand-over whenever taps_len != 0); returns -1 for taps_len == 0 WITHOUT consuming taps
  *    (:496-498, :508, :600-602).
  *  - `input_len` counts scalar elements of the input type: bytes for cu8/cs8, int16 values for cs16

@@ -64,7 +64,7 @@ int xlating_batch_create(uint32_t sampling_freq, int input_format, uint32_t max_
 int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint32_t max_input_buffer_length,
                                  unsigned max_group_blocks, int device, xlating_batch **batch);
 
-/* Plan options (result-neutral: every setting passes the same parity tests).  Six of them; name / value:
+/* Plan options (result-neutral: every setting passes the same parity tests).  Seven of them; name / value:
  *   "polyphase"         -1 by the size rule (default: classes of >= 32 clients with >= 2 taps per polyphase branch), 0 never, 1
  *                       whenever the shape allows: which classes take the polyphase overlap-save path in XL_MODE_OPTIMIZED
  *   "polyphase_m"       0 by the size rule, 64, 128, 256: its transform length (the rule: 64 points for classes of more than 64 branches with up
@@ -94,7 +94,12 @@ int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint3
  *                       it runs in rounds on half, a third, ... as many CUs), not for the clients joined so far -- the reservation then never grows while clients
  *                       join up to that number (growing it re-creates two streams: ~25 ms, once per 512 clients); until then the
  *                       launches run on correspondingly fewer CUs
- * Returns 0, -ENOENT (unknown name), -EINVAL.  The plan is rebuilt at the next call.
+ *   "max_window"        an ADMISSION setting: 0 (default) = clients with T - 1 + D <= 16384 samples, or 16385 .. 1048576 = the largest
+ *                       T - 1 + D admitted.  A client whose window image fits no LDS tile of the direct kernel (D > ~1075 with the
+ *                       server's own filter) is filtered by the wide direct kernel (csrc/xl_wide.hip) in a launch of its own; with a
+ *                       value set, those clients read a second raw history of that many samples (max_window x bytes per sample x 2 of
+ *                       device memory, allocated when the option is set).  Settable only while the engine has no clients (-EBUSY)
+ * Returns 0, -ENOENT (unknown name), -EINVAL, -EBUSY ("max_window" with clients), -ENOMEM.  The plan is rebuilt at the next call.
  * (Launch-shaping knobs of the tuning sessions -- tile heights, riders, slices, passes per workgroup, calls per chain launch, the
  * size rule's client threshold -- are not options: they are read from XL_EXP_* environment variables when an engine is created,
  * csrc/xl_batch.cpp, and ONLY when the process also sets XL_TESTING=1 (tests and tools do) or in -DXL_TUNING builds: a plain process
@@ -104,7 +109,8 @@ int xlating_batch_set_option(xlating_batch *batch, const char *name, long value)
 
 /* Add a client whose stream starts with the NEXT block (like dsp_worker_start, dsp_worker.c:90-108).
  * `taps` is the real low-pass prototype (lpf.h); it is COPIED (unlike create_frequency_xlating_filter
- * the caller keeps ownership).  Returns a client id >= 0, or -1 (taps_len == 0), -EINVAL, -ENOMEM. */
+ * the caller keeps ownership).  Every (D, T) with T - 1 + D <= 16384 (option "max_window": up to its value) is admitted.  Returns a
+ * client id >= 0, or -1 (taps_len == 0), -EINVAL (no taps / D == 0 / T - 1 + D over that capacity), -ENOMEM. */
 int xlating_batch_add_client(xlating_batch *batch, uint32_t decimation, const float *taps, size_t taps_len,
                              int32_t center_freq);
 

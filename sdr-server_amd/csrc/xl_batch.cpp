@@ -45,6 +45,7 @@
 #include "xl_mixf_layout.h"
 #include "xl_polyphase.h"
 #include "xl_taps.h"
+#include "xl_wide.h"
 
 #define XL_NLAUNCH 7
 #define XL_GROUP_MAX 64u  // most blocks per call
@@ -71,6 +72,7 @@ struct Client {
   uint32_t last_K = 0;
   std::vector<uint32_t> last_Kg;  // outputs per block of the latest call
   bool planned_mature = false;
+  bool wide = false;  // no LDS tile of the direct kernel fits its window image (xl_wide.h), or its window exceeds XL_HCAP: the wide kernel
 };
 
 // every window of the client's next outputs lies inside its own stream (no zeros below its join point are needed)
@@ -224,6 +226,17 @@ struct xlating_batch_t {
                                    // that issues matrix instructions hosts the role; the inverse launch is the longer one: 31 % | 69 %
                                    // keeps both slices inside their launches at 4096 clients with the scalar role step)
   std::vector<XlNcoClient> nco;
+  // Wide clients (xl_wide.hip): outside the classes and launch sets above, one launch of their own per call, after the others.
+  std::vector<XlWideClient> wide;
+  XlWideClient *d_wide = nullptr;
+  float2 *d_wtaps = nullptr;    // [client][Tpad] reversed taps
+  double *d_wqtaps = nullptr;   // [client][T] Q15 taps as (re, im) doubles (integer input formats)
+  uint32_t wide_tpad_max = 0;
+  bool exp_wide = false;        // XL_EXP_WIDE (tests): every client joins as a wide client
+  // option "max_window": 0 = wide clients read the XL_HCAP ring d_hist; else the largest T - 1 + D admitted, and every wide client reads
+  // d_whist, a second ring of max_window raw samples rolled each call (allocated when the option is set, without clients)
+  uint32_t max_window = 0;
+  void *d_whist[2] = {nullptr, nullptr};
   size_t out_total = 0;
   uint64_t ncalls = 0;  // calls processed
 
@@ -382,6 +395,12 @@ static void xl_batch_free_plan(xlating_batch *b, bool all) {
   xl_plan_release(b, b->d_qtaps);
   xl_plan_release(b, b->d_qinc);
   xl_plan_release(b, b->d_nco);
+  xl_plan_release(b, b->d_wide);
+  xl_plan_release(b, b->d_wtaps);
+  xl_plan_release(b, b->d_wqtaps);
+  b->d_wide = nullptr;
+  b->d_wtaps = nullptr;
+  b->d_wqtaps = nullptr;
   b->d_taps = b->d_taps_rest = nullptr;
   b->d_qtaps = nullptr;
   b->d_qinc = nullptr;
@@ -394,7 +413,7 @@ extern "C" void xlating_batch_destroy(xlating_batch *b) {
   xl_batch_sync_all(b);
   xl_batch_free_plan(b, true);
   xl_plan_trim(b);
-  void *dev[] = {b->d_hist[0], b->d_hist[1], b->d_block, b->d_out[0], b->d_out[1], b->d_W, b->d_phase_run, b->d_qphase, b->d_qphtab};
+  void *dev[] = {b->d_hist[0], b->d_hist[1], b->d_whist[0], b->d_whist[1], b->d_block, b->d_out[0], b->d_out[1], b->d_W, b->d_phase_run, b->d_qphase, b->d_qphtab};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   for (int i = 0; i < XL_NTAB; ++i) {
@@ -475,6 +494,30 @@ extern "C" int xlating_batch_set_option(xlating_batch *b, const char *name, long
   } else if (n == "nco_side_stream") {
     if (value < -1 || value > 1) return -EINVAL;
     b->nco_side = (int)value;
+  } else if (n == "max_window") {  // an admission setting: the ring's size is fixed while clients read it
+    if (value != 0 && (value <= (long)XL_HCAP || value > (1l << 20))) return -EINVAL;
+    if (b->nalive > 0) return -EBUSY;
+    if (hipSetDevice(b->device) != hipSuccess) return -EIO;
+    xl_batch_sync_all(b);
+    for (int i = 0; i < 2; ++i) {
+      if (b->d_whist[i]) (void)hipFree(b->d_whist[i]);
+      b->d_whist[i] = nullptr;
+    }
+    b->max_window = 0;
+    if (value != 0) {
+      const size_t bytes = (size_t)value * b->bps;
+      for (int i = 0; i < 2; ++i) {
+        if (hipMalloc(&b->d_whist[i], bytes) != hipSuccess || hipMemset(b->d_whist[i], 0, bytes) != hipSuccess) {
+          (void)hipGetLastError();
+          for (int j = 0; j < 2; ++j) {
+            if (b->d_whist[j]) (void)hipFree(b->d_whist[j]);
+            b->d_whist[j] = nullptr;
+          }
+          return -ENOMEM;
+        }
+      }
+      b->max_window = (uint32_t)value;
+    }
   } else {
     return -ENOENT;
   }
@@ -544,6 +587,7 @@ extern "C" int xlating_batch_create_grouped(uint32_t sampling_freq, int input_fo
   if (xl_exp_getenv("XL_EXP_INVSKIP")) b->inv_skip_at = (uint32_t)atoi(xl_exp_getenv("XL_EXP_INVSKIP"));
   if (xl_exp_getenv("XL_EXP_NCOPRIO")) b->nco_prio = (uint32_t)atoi(xl_exp_getenv("XL_EXP_NCOPRIO")) & 3u;
   if (xl_exp_getenv("XL_EXP_FLATPRIO")) b->exp_flags |= 2u;
+  b->exp_wide = xl_exp_getenv("XL_EXP_WIDE") != nullptr;
 #ifdef XL_TUNING
   b->exp_trace = xl_exp_getenv("XL_EXP_TRACE");
   b->exp_nofuse = xl_exp_getenv("XL_EXP_NOFUSE") != nullptr;
@@ -607,16 +651,15 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
                                         int32_t center_freq) {
   if (taps_len == 0) return -1;  // like create_frequency_xlating_filter (xlating.c:496-498)
   if (b == nullptr || taps == nullptr || decimation == 0) return -EINVAL;
-  if (taps_len - 1 + decimation > XL_HCAP) {
-    XL_LOG_ERR("%zu taps at decimation %u exceed the engine's history capacity (%u samples)", taps_len, decimation, XL_HCAP);
+  const uint32_t wcap = b->max_window ? b->max_window : XL_HCAP;  // option "max_window"
+  if (taps_len - 1 + decimation > wcap) {
+    XL_LOG_ERR("%zu taps at decimation %u exceed the engine's history capacity (%u samples; option \"max_window\")", taps_len, decimation, wcap);
     return -EINVAL;
   }
   const uint32_t Tpad = xl_roundup((uint32_t)taps_len, XL_TAP_UNROLL);
-  if (xl_fir_pick_ota(decimation, xl_roundup((uint32_t)taps_len, 12), 160 * 1024) == 0) {
-    XL_LOG_ERR("decimation %u with %zu taps needs a %zu-byte window image even for 8 outputs per wave (> 160 KiB LDS)",
-               decimation, taps_len, xl_fir_lds_bytes_ota(decimation, Tpad, 8));
-    return -EINVAL;
-  }
+  // no LDS tile of the direct kernel fits (xl_wide.h; checked at the largest tap step of its tile heights), or the window reaches
+  // past XL_HCAP: the wide kernel
+  const bool wide = xl_fir_needs_wide(decimation, (uint32_t)taps_len, 12u) || taps_len - 1 + decimation > XL_HCAP || b->exp_wide;
   int id = -1;
   for (size_t i = 0; i < b->clients.size(); ++i)
     if (!b->clients[i].alive) {
@@ -634,6 +677,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   c.D = decimation;
   c.T = (uint32_t)taps_len;
   c.Tpad = Tpad;
+  c.wide = wide;
   c.rt.assign(2 * (size_t)Tpad, 0.0f);
   c.rtq.assign(2 * taps_len, 0);
   xl_prepare_taps(taps, taps_len, center_freq, b->fs, decimation, c.rt.data(), c.rtq.data(), c.incr, c.qincr);
@@ -1123,6 +1167,8 @@ static int xl_batch_plan(xlating_batch *b) {
   b->classes.clear();
   b->classes_rest.clear();
   b->nco.clear();
+  b->wide.clear();
+  b->wide_tpad_max = 0;
   b->trel = 0;
   b->calls_since_plan = 0;
   b->planned_immature = 0;
@@ -1142,12 +1188,29 @@ static int xl_batch_plan(xlating_batch *b) {
     nc.D = c.D;
     nc.rem0 = (uint32_t)(c.consumed % c.D);
     b->nco.push_back(nc);
+    if (c.wide) {
+      const uint32_t hcap = b->max_window ? b->max_window : XL_HCAP;
+      XlWideClient w;
+      memset(&w, 0, sizeof(w));
+      w.D = c.D;
+      w.T = c.T;
+      w.Tpad = c.Tpad;
+      w.out_off = c.out_off;
+      w.rem0 = nc.rem0;
+      w.hv0 = (uint32_t)std::min<uint64_t>(c.consumed, hcap);
+      w.incr = nc.incr;
+      w.qincr = (uint32_t)(uint16_t)c.qincr[0] | ((uint32_t)(uint16_t)c.qincr[1] << 16);
+      b->wide.push_back(w);
+      b->wide_tpad_max = std::max(b->wide_tpad_max, c.Tpad);
+    }
   }
   b->out_total = b->rows_end;
 
   // ---- polyphase classes (optimized mode): all mature clients of one (D, T) -- many clients (its lanes are client
   // columns and its cost per client does not depend on the tap count) with a filter long enough to be worth it
   std::vector<bool> all_use(b->clients.size(), true), rest_use(b->clients.size(), true);
+  for (size_t i = 0; i < b->clients.size(); ++i)
+    if (b->clients[i].wide) all_use[i] = rest_use[i] = false;
   std::vector<PolyClass> next_poly;
   struct Pending {
     size_t idx;
@@ -1160,7 +1223,7 @@ static int xl_batch_plan(xlating_batch *b) {
     std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<int>> by_shape;
     for (size_t i = 0; i < b->clients.size(); ++i) {
       const Client &c = b->clients[i];
-      if (c.alive) by_shape[std::make_tuple(c.D, c.T, c.planned_mature ? XL_HCAP : (uint32_t)c.consumed)].push_back((int)i);
+      if (c.alive && !c.wide) by_shape[std::make_tuple(c.D, c.T, c.planned_mature ? XL_HCAP : (uint32_t)c.consumed)].push_back((int)i);
     }
     for (auto &kv : by_shape) {
       const uint32_t D = std::get<0>(kv.first), T = std::get<1>(kv.first), hv0 = std::get<2>(kv.first);
@@ -1433,6 +1496,29 @@ static int xl_batch_plan(xlating_batch *b) {
   }
   XL_TRY(xl_plan_alloc(b, (void **)&b->d_nco, b->nco.size() * sizeof(XlNcoClient)));
   XL_TRY(hipMemcpy(b->d_nco, b->nco.data(), b->nco.size() * sizeof(XlNcoClient), hipMemcpyHostToDevice));
+  if (!b->wide.empty()) {  // wide clients: descriptors and tap images
+    std::vector<float> wt;
+    std::vector<double> wq;
+    size_t k = 0;
+    for (size_t i = 0; i < b->clients.size(); ++i) {
+      const Client &c = b->clients[i];
+      if (!c.alive || !c.wide) continue;
+      XlWideClient &w = b->wide[k++];
+      w.tap_off = (uint32_t)(wt.size() / 2);
+      wt.insert(wt.end(), c.rt.begin(), c.rt.end());
+      w.qtap_off = (uint32_t)(wq.size() / 2);
+      if (b->fmt != XL_FMT_CF32)
+        for (int16_t q : c.rtq) wq.push_back((double)q);
+    }
+    XL_TRY(xl_plan_alloc(b, (void **)&b->d_wide, b->wide.size() * sizeof(XlWideClient)));
+    XL_TRY(hipMemcpy(b->d_wide, b->wide.data(), b->wide.size() * sizeof(XlWideClient), hipMemcpyHostToDevice));
+    XL_TRY(xl_plan_alloc(b, (void **)&b->d_wtaps, wt.size() * sizeof(float)));
+    XL_TRY(hipMemcpy(b->d_wtaps, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!wq.empty()) {
+      XL_TRY(xl_plan_alloc(b, (void **)&b->d_wqtaps, wq.size() * sizeof(double)));
+      XL_TRY(hipMemcpy(b->d_wqtaps, wq.data(), wq.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
   if (!b->poly.empty()) {
     if (xl_upload_launch_set(b, b->launches_rest, image_rest, &b->d_taps_rest, nullptr) != 0) goto fail;
   }
@@ -1533,6 +1619,38 @@ static hipError_t xl_dump_trace(const char *path, const unsigned long long *d, s
 }
 #endif
 
+// The wide clients' outputs of a call (the most any of them produces) and their launch, behind the call's other launches on the same
+// stream: windows from [ring | blocks] (the XL_HCAP ring, or the max_window ring), phases from table `phtab` (Q15: d_qphtab).
+static uint32_t xl_batch_wide_maxk(const xlating_batch *b, const XlPos &pos) {
+  const uint32_t hcap = b->max_window ? b->max_window : XL_HCAP;
+  uint32_t k = 0;
+  for (const XlWideClient &w : b->wide) k = std::max(k, xl_grid_dyn_cap(w.D, w.T, w.rem0, w.hv0, pos, hcap).K);
+  return k;
+}
+
+static hipError_t xl_batch_wide_launch(xlating_batch *b, int mode, const void *d_blocks, uint32_t N, int hb, const XlPos &pos,
+                                       uint32_t maxKw, const float2 *phtab, float2 *out, hipStream_t s) {
+  XlWideArgs w;
+  memset(&w, 0, sizeof(w));
+  const bool big = b->max_window != 0;
+  w.in0 = big ? b->d_whist[hb] : b->d_hist[hb];
+  w.n0 = w.hcap = big ? b->max_window : XL_HCAP;
+  w.in1 = d_blocks;
+  w.n1 = N;
+  w.fmt = b->fmt;
+  w.pos = pos;
+  w.clients = b->d_wide;
+  w.nclients = (uint32_t)b->wide.size();
+  w.xtiles = (maxKw + 63u) / 64u;
+  w.parts = mode == XL_MODE_OPTIMIZED ? xl_wide_parts(b->wide_tpad_max) : 1u;
+  w.taps = b->d_wtaps;
+  w.phtab = phtab;
+  w.out = out;
+  w.qtaps = b->d_wqtaps;
+  w.qphtab = b->d_qphtab;
+  return xl_launch_wide(mode == XL_MODE_Q15 ? 2 : (mode == XL_MODE_OPTIMIZED ? 1 : 0), w, s);
+}
+
 // One call: G blocks of S samples each, contiguous at d_blocks.
 #define XL_STREAM_ENGINE_P (reinterpret_cast<hipStream_t>((intptr_t)-1))
 
@@ -1584,6 +1702,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
   // branch samples whatever the call holds)
   uint32_t maxK = 0;  // the most outputs any client produces in this call
   for (const DirectClass &cs : b->classes) maxK = std::max(maxK, xl_grid_dyn(cs.D, cs.T, cs.rem0, cs.hv0, pos).K);
+  const uint32_t maxKw = xl_batch_wide_maxk(b, pos);  // (the wide clients: a launch of their own)
   const bool use_poly = mode == XL_MODE_OPTIMIZED && !b->poly.empty() && maxK >= 2 * XLP_M_MAX;
   if (!use_poly && !b->nco.empty()) {  // this call runs the all-clients launch set: build it if the plan has not yet
     int rc = xl_batch_build_all_set(b);
@@ -1649,6 +1768,8 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
       XL_TRY(xl_launch_fir_q15_batch(L.ct, L.nw, a, b->d_qtaps, b->d_qphtab, L.lds, s));
     }
     if (!rolled) XL_TRY(xl_launch_update_history(b->d_hist[hb], d_blocks, XL_HCAP, N, b->bps, b->d_hist[hn], s));
+    if (maxKw > 0) XL_TRY(xl_batch_wide_launch(b, XL_MODE_Q15, d_blocks, N, hb, pos, maxKw, nullptr, b->d_out[p], s));
+    if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[hb], d_blocks, b->max_window, N, b->bps, b->d_whist[hn], s));
     if (record_ev) XL_TRY(hipEventRecord(record_ev, s));
     b->poisoned = false;
     for (Client &c : b->clients) {
@@ -1770,7 +1891,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
     // d_out[p]; the first launch also rolls the raw history into d_hist[hn], and the launches tabulate table[tab ^ 1]
     // for the next call
     hipEvent_t f0 = nullptr, f1 = nullptr;
-    if (b->timing && maxK > 0 && b->ncalls % b->timing_every == 0) {
+    if (b->timing && (maxK > 0 || maxKw > 0) && b->ncalls % b->timing_every == 0) {
       for (int i = 0; i < 2; ++i) {
         hipEvent_t ev;
         XL_TRY(xl_batch_timing_event(b, &ev));
@@ -1786,8 +1907,8 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
     const bool want_done = (side || b->last_nco != nullptr) && (!side || launched_n > 0);
     bool record_attached = false;  // the caller's record_ev rides on the last launch instead (no ev_done wanted there)
     Launch *const Ls = use_poly ? b->launches_rest : b->launches;
+    if (f0) XL_TRY(hipEventRecord(f0, s));
     if (maxK > 0) {
-      if (f0) XL_TRY(hipEventRecord(f0, s));
       for (int lq = 0; lq < XL_NLAUNCH; ++lq) {
         Launch &L = Ls[lq];
         if (L.groups.empty()) continue;
@@ -1939,7 +2060,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
             XL_TRY(hipEventRecord(pe[0], s));
           }
           // the call's last launch carries the "table has been read" event the side stream waits for
-          const bool last_launch = side && rolled && &pc == &b->poly.back();
+          const bool last_launch = side && rolled && &pc == &b->poly.back() && maxKw == 0;  // (a wide launch follows: it reads the table too)
 #ifdef XL_TUNING
           const bool trace_fwd = b->poly_trace && xl_exp_getenv("XL_EXP_POLY_TRACE_FWD");  // (the forward launch instead)
           if (trace_fwd) {
@@ -2020,10 +2141,19 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
           if (pe[3]) XL_TRY(hipEventRecord(pe[3], s));
         }
       }
-      if (f1) XL_TRY(hipEventRecord(f1, s));
     }
+    if (maxKw > 0) {  // the wide clients, behind the launches above on the same stream
+      if (chain_wait) {
+        XL_TRY(hipStreamWaitEvent(s, b->ev_chain[chain_ev], 0));
+        chain_wait = false;
+        b->waited_valid = true, b->waited_ev = chain_ev, b->waited_stream = s;
+      }
+      XL_TRY(xl_batch_wide_launch(b, mode, d_blocks, N, hb, pos, maxKw, b->d_phtab[tab], b->d_out[p], s));
+    }
+    if (f1) XL_TRY(hipEventRecord(f1, s));
     if (!rolled)  // no client produced output in this call (tiny block): roll the history on its own
       XL_TRY(xl_launch_update_history(b->d_hist[hb], d_blocks, XL_HCAP, N, b->bps, b->d_hist[hn], s));
+    if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[hb], d_blocks, b->max_window, N, b->bps, b->d_whist[hn], s));
     // table[tab] has been read by everything enqueued so far (only the side stream ever waits for this)
     // -- and a LATER side-stream chain launch may find this slot in its ring even when this call ran no side stream
     // (alternating modes, alternating caller streams, nco_calls_per_launch < 4): once a side stream has been used the
@@ -2123,6 +2253,10 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
         any = true;
       }
     if (!any) d += " none";
+  }
+  if (!b->wide.empty()) {
+    d += " | wide: " + std::to_string(b->wide.size()) + " clients";
+    if (b->max_window) d += " window<=" + std::to_string(b->max_window);
   }
   if (b->reserve_r) d += " | side kernel: " + std::to_string(8u * b->reserve_r) + " CUs reserved";
   if (pending) d += " | re-plan pending (client set or options changed: the next process call plans again)";

@@ -37,6 +37,27 @@ XL_DEV v2f xl_sample(const void *__restrict__ p, int fmt, uint32_t i) {
   return r;
 }
 
+// xlating.c:417-432: the Q15 family's samples as integers (held exactly in float32); shared by xl_kernels.hip and xl_wide.hip
+XL_DEV v2f xl_sample_q15(const void *__restrict__ p, int fmt, uint32_t i) {
+  v2f r;
+  if (fmt == XLF_CU8) {  // xlating.c:418: ((int16_t) u8 - 128) << 8
+    const uint32_t v = reinterpret_cast<const uint16_t *>(p)[i];
+    r.x = (float)(((int32_t)(v & 0xFFu) - 128) * 256);
+    r.y = (float)(((int32_t)(v >> 8) - 128) * 256);
+  } else if (fmt == XLF_CS8) {  // :425: s8 << 8
+    const int32_t v = reinterpret_cast<const int16_t *>(p)[i];
+    r.x = (float)((int32_t)(int8_t)(v & 0xFF) * 256);
+    r.y = (float)((v >> 8) * 256);
+  } else {  // :432: the int16 samples as they are
+    const int32_t v = reinterpret_cast<const int32_t *>(p)[i];
+    r.x = (float)(int32_t)(int16_t)(v & 0xFFFF);
+    r.y = (float)(v >> 16);
+  }
+  return r;
+}
+
+XL_DEV int32_t xl_sat16(int32_t v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }  // xlating.c:85-90
+
 // ------------------------------------------------------------------------------------------- complex arithmetic
 // One complex accumulator per (output, client).
 // MODE 0 (native): the reference's scalar expression tree, xlating.c:68 `temp += x * h` in C99 complex float:

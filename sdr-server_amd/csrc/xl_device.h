@@ -161,6 +161,46 @@ hipError_t xl_launch_nco_q15_batch(const XlNcoClient *clients, const uint32_t *q
 hipError_t xl_launch_fir_q15_batch(int ct, int nw, const XlFirArgs &a, const double *qtaps, const short2 *qphtab,
                                    size_t lds_bytes, hipStream_t s);
 
+// ---- wide direct FIR (xl_wide.hip): clients whose window image fits no LDS tile (xl_wide.h: xl_fir_needs_wide).  Lane =
+// one output, windows read straight from global memory, taps wave-uniform; one client per workgroup row (blockIdx.y).
+struct XlWideClient {
+  uint32_t D, T, Tpad;
+  uint32_t tap_off;   // float2 index into the wide tap image: the client's Tpad reversed taps (xl_prepare_taps), zero padded
+  uint32_t qtap_off;  // index of (re, im) double pairs into the wide Q15 tap image: the client's T taps (XL_MODE_Q15)
+  uint32_t out_off;   // float2 index of the client's output row; / XL_PH_STRIDE into the phase tables
+  uint32_t rem0, hv0; // plan-time record (xl_grid_dyn_cap with the launch's history capacity)
+  float2 incr;        // NCO phase increment (xlating.c:544)
+  uint32_t qincr;     // Q15 phase increment, packed like XlTile::qincr
+  uint32_t pad;
+};
+
+#define XL_WIDE_PARTS_MAX 16u  // waves per 64-output tile that split the tap range (optimized mode)
+
+struct XlWideArgs {
+  const void *in0;      // [in0 | in1]: n0 samples of history (batch: the ring of hcap samples), then n1 new samples
+  const void *in1;
+  uint32_t n0, n1;
+  int fmt;              // XLF_*
+  uint32_t hcap;        // history capacity the windows are counted in (xl_grid_dyn_cap); batch: n0
+  XlPos pos;
+  uint32_t explicit_dyn;  // 1: single-filter path -- dyn1 as given (one client, one block)
+  XlDyn dyn1;
+  const XlWideClient *clients;
+  uint32_t nclients;
+  uint32_t xtiles;      // 64-output tiles per client: ceil(max K / 64)
+  uint32_t parts;       // waves per tile splitting the tap range: 1 (native and Q15: every lane sums in tap order) .. XL_WIDE_PARTS_MAX
+  uint32_t flags;       // bit 0: 16-byte window reads -- cf32 samples in in0 only, every window start even, in0 16-byte aligned
+  const float2 *taps;   // wide tap image
+  const float2 *phtab;  // NCO phase table (every XL_PH_STRIDE-th phase)
+  float2 *out;          // outputs (Q15: short2 rows at the addresses of the float2 rows)
+  const double *qtaps;  // Q15: wide Q15 tap image, (re, im) doubles
+  const short2 *qphtab; // Q15: phase table
+};
+// mode: 0 native, 1 optimized, 2 Q15.  The launch covers a.xtiles x a.nclients workgroups of 64 * a.parts threads.
+hipError_t xl_launch_wide(int mode, const XlWideArgs &a, hipStream_t s);
+// waves per tile for an optimized launch whose longest filter has `tpad` taps
+uint32_t xl_wide_parts(uint32_t tpad);
+
 // window image bytes for `ota` outputs per tile
 size_t xl_fir_lds_bytes_ota(uint32_t D, uint32_t Tpad, uint32_t ota);
 // largest outputs-per-wave in {64, 32, 16, 8} whose window image fits `budget` bytes of LDS; 0 if none

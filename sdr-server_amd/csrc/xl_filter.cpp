@@ -20,6 +20,7 @@
 #include "xl_common.h"
 #include "xl_device.h"
 #include "xl_taps.h"
+#include "xl_wide.h"
 
 struct xlating_t {
   uint32_t D = 0;
@@ -38,6 +39,7 @@ struct xlating_t {
                            // 2 = and take the FMA-contracted phase step of an -mfma build (xl_grid.h: XL_POS_FMA_STEP)
   uint32_t spec_flags = 0; // XlPos flags the look-ahead table was tabulated with
   uint32_t ota = 64;       // outputs per wave (64 unless the window image would not fit the LDS)
+  bool wide = false;       // no LDS tile fits the window image (xl_wide.h): the wide direct kernel (xl_wide.hip) filters
 
   void *d_raw = nullptr;
   float2 *d_work_f = nullptr;
@@ -64,6 +66,7 @@ struct xlating_t {
   short2 *d_qtaps = nullptr;
   XlGroup *d_group = nullptr;
   XlNcoClient *d_nco = nullptr;
+  XlWideClient *d_wide = nullptr;
 
   bool zero_copy = true;  // kernels read the pinned input / write the pinned output over PCIe (XL_EXP_DROPIN_COPY=1: staged copies)
   void *h_in = nullptr;
@@ -78,7 +81,7 @@ static void xl_filter_free(xlating *f) {
   if (f->stream_nco) (void)hipStreamSynchronize(f->stream_nco);
   void *dev[] = {f->d_phtab_next, f->d_phase_next, f->d_qphtab_next, f->d_qphase_next,
                  f->d_raw,   f->d_work_f, f->d_work_q, f->d_out_f, f->d_out_q, f->d_phtab, f->d_qphtab,
-                 f->d_phase, f->d_qphase, f->d_taps,   f->d_qtaps, f->d_group, f->d_nco};
+                 f->d_phase, f->d_qphase, f->d_taps,   f->d_qtaps, f->d_group, f->d_nco, f->d_wide};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   void *host[] = {f->h_in, f->h_out_f, f->h_out_q};
@@ -190,12 +193,19 @@ extern "C" int create_frequency_xlating_filter(uint32_t decimation, float *taps,
   XL_TRY(hipMemcpyAsync(f->d_phase, &one, sizeof(one), hipMemcpyHostToDevice, f->stream));
   XL_TRY(hipMemcpyAsync(f->d_qphase, &qone, sizeof(qone), hipMemcpyHostToDevice, f->stream));
   XL_TRY(hipStreamSynchronize(f->stream));
-  f->ota = xl_fir_pick_ota(decimation, f->Tpad, 160 * 1024);
-  if (f->ota == 0) {
-    XL_LOG_ERR("decimation %u with %zu taps needs a %zu-byte window image even for 8 outputs per wave (> 160 KiB LDS)",
-               decimation, taps_len, xl_fir_lds_bytes_ota(decimation, f->Tpad, 8));
-    xl_filter_free(f);
-    return -EINVAL;
+  // XL_EXP_WIDE (tests): every shape takes the wide kernel
+  f->wide = xl_fir_needs_wide(decimation, (uint32_t)taps_len, XL_TAP_UNROLL) || xl_exp_getenv("XL_EXP_WIDE") != nullptr;
+  if (f->wide) {
+    XlWideClient w;
+    memset(&w, 0, sizeof(w));
+    w.D = decimation;
+    w.T = (uint32_t)taps_len;
+    w.Tpad = f->Tpad;
+    w.incr = nc.incr;
+    XL_TRY(hipMalloc((void **)&f->d_wide, sizeof(XlWideClient)));
+    XL_TRY(hipMemcpy(f->d_wide, &w, sizeof(w), hipMemcpyHostToDevice));
+  } else {
+    f->ota = xl_fir_pick_ota(decimation, f->Tpad, 160 * 1024);
   }
   *filter = f;
   return 0;
@@ -313,7 +323,28 @@ static void xl_run_cf32(xlating *f, const void *input, size_t input_len, int fmt
     a.taps = f->d_taps;
     a.phtab = f->d_phtab;
     a.out = f->zero_copy ? f->h_out_f : f->d_out_f;  // (the K outputs go straight to the pinned result buffer)
-    XL_TRY(xl_launch_fir(1, mode, XL_NW_DEFAULT, a, xl_fir_lds_bytes_ota(f->D, f->Tpad, f->ota), f->stream));
+    if (f->wide) {
+      XlWideArgs w;
+      memset(&w, 0, sizeof(w));
+      w.in0 = a.in0;
+      w.n0 = a.n0;
+      w.fmt = XLF_CF32;
+      w.hcap = 0;  // (explicit: dyn1 holds the call's numbers)
+      w.pos = pos;
+      w.explicit_dyn = 1;
+      w.dyn1 = a.dyn1;
+      w.clients = f->d_wide;
+      w.nclients = 1;
+      w.xtiles = (uint32_t)((K + 63) / 64);
+      w.parts = mode == 1 ? xl_wide_parts(f->Tpad) : 1u;
+      w.flags = f->D % 2 == 0 ? 1u : 0u;  // every window starts at an even sample of the 256-byte aligned work image
+      w.taps = f->d_taps;
+      w.phtab = f->d_phtab;
+      w.out = a.out;
+      XL_TRY(xl_launch_wide(mode, w, f->stream));
+    } else {
+      XL_TRY(xl_launch_fir(1, mode, XL_NW_DEFAULT, a, xl_fir_lds_bytes_ota(f->D, f->Tpad, f->ota), f->stream));
+    }
     if (!f->zero_copy) XL_TRY(hipMemcpyAsync(f->h_out_f, f->d_out_f, K * sizeof(float2), hipMemcpyDeviceToHost, f->stream));
   }
   {

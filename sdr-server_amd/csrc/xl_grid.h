@@ -44,19 +44,25 @@ typedef struct XlDyn {
   uint32_t j0;         /* call-local position of output 0's newest sample */
 } XlDyn;
 
-/* per-call numbers of a class from its plan-time record */
-XL_HD XlDyn xl_grid_dyn(uint32_t D, uint32_t T, uint32_t rem0, uint32_t hv0, XlPos p) {
+/* per-call numbers of a class from its plan-time record, for a raw history of `hcap` samples in front of the call's blocks
+ * (hv0 = min(consumed, hcap) at plan time).  The wide direct kernel (xl_wide.hip) may read a history longer than XL_HCAP. */
+XL_HD XlDyn xl_grid_dyn_cap(uint32_t D, uint32_t T, uint32_t rem0, uint32_t hv0, XlPos p, uint32_t hcap) {
   const uint32_t rem = (rem0 % D + p.trel % D) % D;
   const uint32_t j0 = (D - rem) % D;
   const uint32_t N = p.S * p.G;
-  uint32_t hv = hv0 + (p.trel < XL_HCAP ? p.trel : XL_HCAP);
+  uint32_t hv = hv0 + (p.trel < hcap ? p.trel : hcap);
   XlDyn d;
-  if (hv > XL_HCAP) hv = XL_HCAP;
+  if (hv > hcap) hv = hcap;
   d.j0 = j0;
   d.K = N > j0 ? (N - j0 + D - 1u) / D : 0u;
-  d.base = XL_HCAP - (T - 1u) + j0;
-  d.zero_below = XL_HCAP - hv;
+  d.base = hcap - (T - 1u) + j0;
+  d.zero_below = hcap - hv;
   return d;
+}
+
+/* the same for the XL_HCAP history every other kernel reads */
+XL_HD XlDyn xl_grid_dyn(uint32_t D, uint32_t T, uint32_t rem0, uint32_t hv0, XlPos p) {
+  return xl_grid_dyn_cap(D, T, rem0, hv0, p, XL_HCAP);
 }
 
 /* stream position of the NEXT call if it has the same shape (the guess the NCO look-ahead makes) */

@@ -755,7 +755,6 @@ hipError_t xl_launch_update_history(const void *hist, const void *block, uint32_
 }
 
 // ------------------------------------------------------------------------------------------- Q15 family
-XL_DEV int32_t xl_sat16(int32_t v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }  // xlating.c:85-90
 
 // xlating.c:126-129: truncating Q15 phase recurrence, never renormalised.  One thread (one filter).
 // One step of the Q15 phase recurrence (xlating.c:126-129): (pr + j pi) * (ir + j ii) >> 15, truncating, saturated --
@@ -854,23 +853,6 @@ hipError_t xl_launch_fir_q15(const short2 *work, const short2 *taps, uint32_t T,
 // exact, so the result IS the integer sum) -- v_fma_f64 runs at half the FP32 rate, an int64 multiply-add at a quarter
 // or less.  Window image: the block's samples as Q15 integers held in float32 (exact), shared by the 4 tiles of a group;
 // taps: wave-uniform doubles through scalar loads, SGPR operands of the FMAs, like the float kernel.
-XL_DEV v2f xl_sample_q15(const void *__restrict__ p, int fmt, uint32_t i) {
-  v2f r;
-  if (fmt == XLF_CU8) {  // xlating.c:418: ((int16_t) u8 - 128) << 8
-    const uint32_t v = reinterpret_cast<const uint16_t *>(p)[i];
-    r.x = (float)(((int32_t)(v & 0xFFu) - 128) * 256);
-    r.y = (float)(((int32_t)(v >> 8) - 128) * 256);
-  } else if (fmt == XLF_CS8) {  // :425: s8 << 8
-    const int32_t v = reinterpret_cast<const int16_t *>(p)[i];
-    r.x = (float)((int32_t)(int8_t)(v & 0xFF) * 256);
-    r.y = (float)((v >> 8) * 256);
-  } else {  // :432: the int16 samples as they are
-    const int32_t v = reinterpret_cast<const int32_t *>(p)[i];
-    r.x = (float)(int32_t)(int16_t)(v & 0xFFFF);
-    r.y = (float)(v >> 16);
-  }
-  return r;
-}
 
 // one lane per client: the truncating Q15 phase recurrence (xlating.c:126-129), every XL_PH_STRIDE-th phase tabulated
 __global__ __launch_bounds__(64) void xl_nco_q15_batch_kernel(const XlNcoClient *__restrict__ cl, const uint32_t *__restrict__ qinc,
