@@ -60,6 +60,21 @@ def test_needs_wide_boundary_shapes(tmp_path):
     assert not lib.needs(2925, 1, 4) and lib.needs(2926, 1, 4)
 
 
+def test_tap_multiples_4_and_12_band(tmp_path):
+    """The drop-in decides at 4 taps, the batch engine at 12: a shape the drop-in sends wide is wide in the batch engine too (no T with
+    needs(D, T, 4) and not needs(D, T, 12)), and the band between them is a few taps wide -- at D = 1000 exactly T = 13477 .. 13480
+    (xl_fir_kernel with the LDS exactly full at 8 outputs per wave in the drop-in, the wide kernel in the batch engine)."""
+    lib = _lib(tmp_path)
+    for D in list(range(1, 60)) + list(range(900, 2927, 13)) + [1000, 1075, 2925, 2926]:
+        edge = max(1, 20480 - 7 * D)  # (7 D + Tpad) * 8 > 160 KiB  <=>  Tpad > 20480 - 7 D
+        for T in range(max(1, edge - 40), edge + 40):
+            assert not (lib.needs(D, T, 4) and not lib.needs(D, T, 12)), (D, T)
+    band = [T for T in range(13000, 14000) if lib.needs(1000, T, 12) and not lib.needs(1000, T, 4)]
+    assert band == [13477, 13478, 13479, 13480], band
+    assert pick_ota(1000, rnd(13480, 4)) == 8 and ((8 - 1) * 1000 + 13480) * 8 == 160 * 1024  # (exactly full)
+    assert not lib.needs(1000, 13476, 12) and lib.needs(1000, 13481, 4)
+
+
 def rnd(t, m):
     return -(-t // m) * m
 
