@@ -1,0 +1,58 @@
+/*
+ * Streaming spectrogram on the GPU: the waterfall of the reference's sdr_spectrogram (src/spectrogram/spectrogram.c:84-168) as an
+ * object that consumes I/Q samples in pieces of any length, from host memory or in place from device memory -- for example the
+ * blocks the batch engine already holds (xlating_batch_process_device).  Plain C ABI, no HIP header: streams are void *.
+ * Library: lib/libxlating_spectrum.so.
+ *
+ * Rows: row r covers stream samples r * sampling_rate ..; it is the bin-wise maximum of the power spectra of its
+ * F = sampling_rate / width transforms of `width` consecutive samples (the S = sampling_rate % width samples after them are skipped,
+ * never transformed).  Power = re^2 + im^2 + 1e-20f with re, im the forward DFT's components times 1.0f / width; a row's value is
+ * 10 log10f(max), the two halves of half = width / 2 bins swapped so that DC is in the middle (an odd width's last bin stays last),
+ * and its pixel is (int)(dB + 255) clamped to [0, 255] (png_util.c:53-63).
+ * A row is complete once its F-th transform is in (its skipped tail need not have been fed).  Any split of the same input into feeds
+ * gives bit-identical rows.
+ */
+#ifndef XLATING_SPECTRUM_H_
+#define XLATING_SPECTRUM_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* sample formats: the values of XL_FMT_CU8 / XL_FMT_CS16 / XL_FMT_CF32 of xlating_batch.h (cs8 is not a spectrogram format) */
+enum { XLATING_SPECTRUM_CU8 = 0, XLATING_SPECTRUM_CS16 = 2, XLATING_SPECTRUM_CF32 = 3 };
+
+#define XLATING_SPECTRUM_MAX_WIDTH 8192
+
+typedef struct xlating_spectrum xlating_spectrum;
+
+/* 0 on success.  -EINVAL: width <= 0, width > XLATING_SPECTRUM_MAX_WIDTH, sampling_rate == 0, width > sampling_rate, an unknown
+ * format or out == NULL.  -ENODEV (with a "<3>" line on stderr): no usable HIP device -- there is no CPU path.  -ENOMEM. */
+int xlating_spectrum_create(uint32_t sampling_rate, int width, int format, xlating_spectrum **out);
+
+/* Consume n samples (complex samples: n * 2 bytes of cu8, n * 4 of cs16, n * 8 of cf32) from host memory.  The caller's buffer is
+ * copied before the call returns.  0, or a negative errno (-EIO after a HIP failure; the object is then unusable). */
+int xlating_spectrum_feed_host(xlating_spectrum *s, const void *samples, size_t n);
+
+/* The same from device memory, read in place and stream-ordered on `hip_stream` (NULL: the default stream), like
+ * xlating_batch_process_device: the buffer must stay valid until that stream has passed this call's work; the call does not wait
+ * for it.  Consecutive feeds may use different streams: each is ordered behind the previous feed's work. */
+int xlating_spectrum_feed_device(xlating_spectrum *s, const void *dev_samples, size_t n, void *hip_stream);
+
+/* Copy up to max_rows completed rows, oldest first, and drop them from the object: `width` floats (dB) per row to db and `width`
+ * bytes (pixels) per row to pixels; either pointer may be NULL.  Waits for the feeds' work.  Returns the number of rows copied
+ * (0 when none is complete), or a negative errno.  Rows are never lost or reordered: un-taken rows accumulate and the object's
+ * row store GROWS to hold them (a feed fails with -ENOMEM only if that growth cannot be allocated, and then consumes nothing);
+ * a long-lived caller takes rows regularly. */
+int xlating_spectrum_take_rows(xlating_spectrum *s, float *db, uint8_t *pixels, size_t max_rows);
+
+void xlating_spectrum_destroy(xlating_spectrum *s);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* XLATING_SPECTRUM_H_ */

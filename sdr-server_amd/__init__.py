@@ -696,3 +696,107 @@ def wire_admit(req, band_sampling_rate, current_band_freq=0, lpf_cutoff_rate=5):
 
 def wire_add_client(engine, adm, band_sampling_rate):
     return lib().xlating_wire_add_client(engine.h, C.byref(adm), band_sampling_rate)
+
+
+# ------------------------------------------------------------------------------------------------- spectrogram (libxlating_spectrum.so)
+SPECTRUM_SYMBOLS = ["xlating_spectrum_create", "xlating_spectrum_feed_host", "xlating_spectrum_feed_device", "xlating_spectrum_take_rows",
+                    "xlating_spectrum_destroy", "spectrogram_main", "spectrogram_sighandler"]
+SPECTRUM_FMT = {"cu8": 0, "cs16": 2, "cf32": 3}
+_SPEC_NP = {"cu8": np.uint8, "cs16": np.int16, "cf32": np.float32}
+_slib = None
+
+
+def spectrum_library_path():
+    return os.path.join(os.path.dirname(library_path()), "libxlating_spectrum.so")
+
+
+def spectrum_lib():
+    """include/xlating_spectrum.h and include/spectrogram.h: the GPU spectrogram."""
+    global _slib
+    if _slib is not None:
+        return _slib
+    lib()  # (torch's HIP runtime first, see lib())
+    path = spectrum_library_path()
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    S = C.CDLL(path)
+    S.xlating_spectrum_create.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    S.xlating_spectrum_create.restype = C.c_int
+    S.xlating_spectrum_feed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    S.xlating_spectrum_feed_host.restype = C.c_int
+    S.xlating_spectrum_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    S.xlating_spectrum_feed_device.restype = C.c_int
+    S.xlating_spectrum_take_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    S.xlating_spectrum_take_rows.restype = C.c_int
+    S.xlating_spectrum_destroy.argtypes = [C.c_void_p]
+    S.xlating_spectrum_destroy.restype = None
+    S.spectrogram_main.argtypes = [C.c_void_p]
+    S.spectrogram_main.restype = C.c_int
+    _slib = S
+    return S
+
+
+class Spectrum:
+    """One `xlating_spectrum *` (include/xlating_spectrum.h): feed samples in pieces, take completed waterfall rows."""
+
+    def __init__(self, sampling_rate, width, fmt="cu8"):
+        S = spectrum_lib()
+        if fmt not in SPECTRUM_FMT:
+            raise XlatingError("xlating_spectrum_create", -22)
+        h = C.c_void_p()
+        code = S.xlating_spectrum_create(sampling_rate, width, SPECTRUM_FMT[fmt], C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_spectrum_create", code)
+        self.h, self.W, self.fmt = h, width, fmt
+
+    def feed(self, x, n=None, stream=0):
+        """x: a numpy array of scalar elements (I, Q interleaved; cu8 uint8, cs16 int16, cf32 float32), or a device pointer (int)
+        with n = its number of complex samples, read in place on `stream`."""
+        if isinstance(x, int):
+            code = spectrum_lib().xlating_spectrum_feed_device(self.h, x, n, stream)
+        else:
+            x = np.ascontiguousarray(x, dtype=_SPEC_NP[self.fmt])
+            code = spectrum_lib().xlating_spectrum_feed_host(self.h, x.ctypes.data, x.size // 2)
+        if code != 0:
+            raise XlatingError("xlating_spectrum_feed", code)
+
+    def take_rows(self, max_rows=1 << 20):
+        """-> (db float32 [R, W], pixels uint8 [R, W]): every completed row not taken yet, oldest first."""
+        S, parts_db, parts_px = spectrum_lib(), [], []
+        while True:
+            n = 256
+            db = np.empty((n, self.W), np.float32)
+            px = np.empty((n, self.W), np.uint8)
+            got = S.xlating_spectrum_take_rows(self.h, db.ctypes.data, px.ctypes.data, min(n, max_rows))
+            if got < 0:
+                raise XlatingError("xlating_spectrum_take_rows", got)
+            parts_db.append(db[:got])
+            parts_px.append(px[:got])
+            max_rows -= got
+            if got < n or max_rows <= 0:
+                break
+        return np.concatenate(parts_db), np.concatenate(parts_px)
+
+    def close(self):
+        if getattr(self, "h", None):
+            spectrum_lib().xlating_spectrum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpectrogramRequest(C.Structure):
+    """include/spectrogram.h `spectrogram` (the reference's six request fields, then reserved space)"""
+    _fields_ = [("sampling_rate", C.c_uint32), ("width", C.c_int), ("data_format", C.c_char_p), ("input_file", C.c_char_p),
+                ("output_file", C.c_char_p), ("fftw_flags", C.c_char_p), ("xl_private", C.c_void_p * 6)]
+
+
+def spectrogram_main(input_file, output_file, width=1024, sampling_rate=48000, data_format="cu8", fftw_flags="FFTW_MEASURE"):
+    """spectrogram_main() of include/spectrogram.h -> its return code.  None leaves a pointer field NULL."""
+    enc = lambda v: None if v is None else str(v).encode()  # noqa: E731
+    req = SpectrogramRequest(sampling_rate, width, enc(data_format), enc(input_file), enc(output_file), enc(fftw_flags))
+    return spectrum_lib().spectrogram_main(C.byref(req))

@@ -1,0 +1,390 @@
+// xl_spectrum.cpp -- the streaming spectrogram (include/xlating_spectrum.h): the state carried across feeds and the launches of
+// xl_spectrum.hip.  Reference: src/spectrogram/spectrogram.c:84-168 (one row), iq_file.c (sample formats).
+//
+// State across feeds: P, the number of samples consumed (row r starts at r * sr; its transform k covers r * sr + k W .. + W); the raw
+// samples of the transform that straddles two feeds (at most W - 1, in d_carry, stream-ordered device copies); the per-row maxima in
+// a ring of `cap` row slots (d_max, float bits, zero between rows).  A span of a feed is cut into: the straddling transform (completed
+// from the carry), the transforms that lie wholly inside the span (one launch over the span in place), and the start of the next
+// straddling one (into the carry).  Skipped samples are never transformed.  Every row whose F-th transform is in gets one finishing
+// launch (dB, shift, pixel into d_db / d_px of its slot) and a copy into the pinned host ring; take_rows waits for the latest feed.
+// Any split gives bit-identical rows: every transform sees the same samples and the same code, and max is exact.
+#include "../../include/xlating_spectrum.h"
+
+#include <errno.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <complex>
+#include <new>
+#include <vector>
+
+#include "xl_common.h"
+#include "xl_device.h"
+#include "xl_spectrum.h"
+#include "xl_spectrum_core.h"
+
+#define XL_SPEC_SPAN_MAX ((int64_t)1 << 30)  // samples per span: keeps every in-launch offset within 32 bits
+
+struct xlating_spectrum {
+  uint32_t sr = 0, W = 0, F = 0, N = 0, ssz = 0;
+  int fmt = 0;
+  bool blue = false;
+  int device = 0;
+  hipStream_t stream = nullptr;  // host feeds
+  hipEvent_t last = nullptr;     // behind the latest feed's work
+  bool fed = false, broken = false;
+  float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bspec = nullptr;
+  uint8_t *d_carry = nullptr;
+  uint32_t cap = 0;
+  uint32_t *d_max = nullptr;
+  float *d_db = nullptr, *h_db = nullptr;
+  uint8_t *d_px = nullptr, *h_px = nullptr;
+  int64_t P = 0, rows_finished = 0, rows_taken = 0;
+  size_t chunk = 0;  // samples per host staging buffer
+  void *h_stage[2] = {nullptr, nullptr}, *d_stage[2] = {nullptr, nullptr};
+  hipEvent_t stage_ev[2] = {nullptr, nullptr};
+  bool stage_used[2] = {false, false};
+  int stage_i = 0;
+};
+
+#define XL_SPEC_TRY(expr)                                                                                         \
+  do {                                                                                                            \
+    hipError_t xl_e_ = (hipError_t)(expr);                                                                        \
+    if (xl_e_ != hipSuccess) {                                                                                    \
+      xl_last_hip_error = xl_e_;                                                                                  \
+      XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__);                   \
+      return xl_e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                                                       \
+    }                                                                                                             \
+  } while (0)
+
+// ---------------------------------------------------------------------------------------------------------- host tables (double)
+static void xl_fft_double(std::vector<std::complex<double>> &a) {  // in-place radix-2 forward DFT, size a power of two
+  const size_t n = a.size();
+  for (size_t i = 1, j = 0; i < n; ++i) {
+    size_t bit = n >> 1;
+    for (; j & bit; bit >>= 1) j ^= bit;
+    j ^= bit;
+    if (i < j) std::swap(a[i], a[j]);
+  }
+  for (size_t len = 2; len <= n; len <<= 1)
+    for (size_t i = 0; i < n; i += len)
+      for (size_t k = 0; k < len / 2; ++k) {
+        const double ang = -2.0 * M_PI * (double)k / (double)len;
+        const std::complex<double> w(cos(ang), sin(ang));
+        const std::complex<double> u = a[i + k], v = a[i + k + len / 2] * w;
+        a[i + k] = u + v;
+        a[i + k + len / 2] = u - v;
+      }
+}
+
+static int xl_spec_tables(xlating_spectrum *s) {
+  const uint32_t W = s->W, N = s->N;
+  std::vector<float2> tw(N);
+  for (uint32_t m = 0; m < N; ++m) {
+    const double ang = -2.0 * M_PI * (double)m / (double)N;
+    tw[m] = make_float2((float)cos(ang), (float)sin(ang));
+  }
+  XL_SPEC_TRY(hipMalloc(&s->d_tw, sizeof(float2) * N));
+  XL_SPEC_TRY(hipMemcpy(s->d_tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+  if (!s->blue) return 0;
+  // chirp c[n] = exp(-i pi (n^2 mod 2W) / W); the filter b[m] = conj(c[|m|]) on -(W-1) .. W-1, wrapped into L
+  std::vector<std::complex<double>> c(W), b(N, 0.0);
+  for (uint32_t n = 0; n < W; ++n) {
+    const uint64_t q = (uint64_t)n * n % (2ull * W);
+    const double ang = -M_PI * (double)q / (double)W;
+    c[n] = std::complex<double>(cos(ang), sin(ang));
+  }
+  b[0] = std::conj(c[0]);
+  for (uint32_t m = 1; m < W; ++m) b[m] = b[N - m] = std::conj(c[m]);
+  xl_fft_double(b);
+  std::vector<float2> ch(W), bs(N);
+  for (uint32_t n = 0; n < W; ++n) ch[n] = make_float2((float)c[n].real(), (float)c[n].imag());
+  for (uint32_t m = 0; m < N; ++m) bs[m] = make_float2((float)(b[m].real() / N), (float)(b[m].imag() / N));
+  XL_SPEC_TRY(hipMalloc(&s->d_chirp, sizeof(float2) * W));
+  XL_SPEC_TRY(hipMemcpy(s->d_chirp, ch.data(), sizeof(float2) * W, hipMemcpyHostToDevice));
+  XL_SPEC_TRY(hipMalloc(&s->d_bspec, sizeof(float2) * N));
+  XL_SPEC_TRY(hipMemcpy(s->d_bspec, bs.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------- row ring
+static void xl_spec_free_rows(uint32_t *d_max, float *d_db, uint8_t *d_px, float *h_db, uint8_t *h_px) {
+  if (d_max) (void)hipFree(d_max);
+  if (d_db) (void)hipFree(d_db);
+  if (d_px) (void)hipFree(d_px);
+  if (h_db) (void)hipHostFree(h_db);
+  if (h_px) (void)hipHostFree(h_px);
+}
+
+// a ring of `cap` slots, replacing the current one: the un-taken finished rows (host) and the rows in progress (device maxima) move
+// to their slots in the new ring.  Everything queued so far has completed (the caller waited for `last`).
+static int xl_spec_rows_alloc(xlating_spectrum *s, uint32_t cap) {
+  const size_t W = s->W;
+  uint32_t *d_max = nullptr;
+  float *d_db = nullptr, *h_db = nullptr;
+  uint8_t *d_px = nullptr, *h_px = nullptr;
+  hipError_t e = hipMalloc(&d_max, sizeof(uint32_t) * W * cap);
+  if (e == hipSuccess) e = hipMemset(d_max, 0, sizeof(uint32_t) * W * cap);
+  if (e == hipSuccess) e = hipMalloc(&d_db, sizeof(float) * W * cap);
+  if (e == hipSuccess) e = hipMalloc(&d_px, W * cap);
+  if (e == hipSuccess) e = hipHostMalloc(&h_db, sizeof(float) * W * cap, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc(&h_px, W * cap, hipHostMallocDefault);
+  if (e == hipSuccess && s->cap > 0) {
+    for (int64_t r = s->rows_taken; r < s->rows_finished; ++r) {
+      const size_t o = (size_t)(r % s->cap) * W, n = (size_t)(r % cap) * W;
+      memcpy(h_db + n, s->h_db + o, sizeof(float) * W);
+      memcpy(h_px + n, s->h_px + o, W);
+    }
+    const int64_t rows_started = s->P > 0 ? (s->P - 1) / s->sr + 1 : 0;
+    for (int64_t r = s->rows_finished; r < rows_started && e == hipSuccess; ++r)
+      e = hipMemcpy(d_max + (size_t)(r % cap) * W, s->d_max + (size_t)(r % s->cap) * W, sizeof(uint32_t) * W,
+                    hipMemcpyDeviceToDevice);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the memset and copies ran on the null stream; the feeds do not)
+  if (e != hipSuccess) {
+    xl_last_hip_error = e;
+    XL_LOG_ERR("spectrum row store of %u rows x %zu bins: %s", cap, W, hipGetErrorString(e));
+    xl_spec_free_rows(d_max, d_db, d_px, h_db, h_px);
+    return e == hipErrorOutOfMemory ? -ENOMEM : -EIO;
+  }
+  xl_spec_free_rows(s->d_max, s->d_db, s->d_px, s->h_db, s->h_px);
+  s->d_max = d_max, s->d_db = d_db, s->d_px = d_px, s->h_db = h_db, s->h_px = h_px, s->cap = cap;
+  return 0;
+}
+
+// room for every row from the oldest un-taken one through the row of sample P1 - 1
+static int xl_spec_reserve(xlating_spectrum *s, int64_t P1, hipStream_t st) {
+  const int64_t need = (P1 - 1) / s->sr - s->rows_taken + 1;
+  if (need <= (int64_t)s->cap) return 0;
+  if (need > (int64_t)1 << 30) return -ENOMEM;
+  uint32_t cap = s->cap * 2;
+  while ((int64_t)cap < need) cap *= 2;
+  if (s->fed) XL_SPEC_TRY(hipEventSynchronize(s->last));
+  XL_SPEC_TRY(hipStreamSynchronize(st));  // (this feed's earlier spans: `last` is recorded at the end of a feed)
+  return xl_spec_rows_alloc(s, cap);
+}
+
+// ---------------------------------------------------------------------------------------------------------- one span
+static int xl_spec_launch_t(xlating_spectrum *s, const void *in, int64_t base, int64_t g0, int64_t T, hipStream_t st) {
+  XlSpecArgs a;
+  a.in = in, a.base = base, a.g0 = g0, a.T = (uint32_t)T, a.F = s->F, a.sr = s->sr, a.W = s->W, a.cap = s->cap;
+  a.rowmax = s->d_max, a.tw = s->d_tw, a.chirp = s->d_chirp, a.bspec = s->d_bspec, a.norm = 1.0f / (float)s->W;
+  XL_SPEC_TRY(xl_spec_launch(a, s->N, s->blue, s->fmt, st));
+  return 0;
+}
+
+// n (<= XL_SPEC_SPAN_MAX) samples at device address `in`: stream samples P .. P + n - 1
+static int xl_spec_span(xlating_spectrum *s, const uint8_t *in, int64_t n, hipStream_t st) {
+  const int64_t sr = s->sr, W = s->W, F = s->F, FW = F * W, ssz = s->ssz;
+  const int64_t P0 = s->P, P1 = P0 + n;
+  int rc = xl_spec_reserve(s, P1, st);
+  if (rc != 0) return rc;
+  const int64_t row0 = P0 / sr, pos0 = P0 % sr;
+  // the transform that straddles P0: its first samples are in the carry
+  if (pos0 < FW && pos0 % W != 0) {
+    const int64_t k = pos0 / W, t0 = row0 * sr + k * W, t1 = t0 + W;
+    const int64_t m = std::min(t1, P1) - P0;
+    XL_SPEC_TRY(hipMemcpyAsync(s->d_carry + (P0 - t0) * ssz, in, (size_t)(m * ssz), hipMemcpyDeviceToDevice, st));
+    if (P0 + m == t1 && (rc = xl_spec_launch_t(s, s->d_carry, t0, row0 * F + k, 1, st)) != 0) return rc;
+  }
+  // the transforms wholly inside the span, in place
+  const int64_t kc = (pos0 + W - 1) / W;
+  const int64_t g_first = kc >= F ? (row0 + 1) * F : row0 * F + kc;
+  const int64_t row1 = P1 / sr, pos1 = P1 % sr;
+  const int64_t g_end = row1 * F + std::min(F, pos1 / W);
+  if (g_end > g_first && (rc = xl_spec_launch_t(s, in, P0, g_first, g_end - g_first, st)) != 0) return rc;
+  // the transform that straddles P1 and starts inside the span: its start into the carry
+  if (pos1 < FW && pos1 % W != 0) {
+    const int64_t t0 = row1 * sr + (pos1 / W) * W;
+    if (t0 >= P0)
+      XL_SPEC_TRY(hipMemcpyAsync(s->d_carry, in + (t0 - P0) * ssz, (size_t)((P1 - t0) * ssz), hipMemcpyDeviceToDevice, st));
+  }
+  s->P = P1;
+  // rows whose F-th transform is in: finish, and copy to the host ring
+  const int64_t done = P1 >= FW ? (P1 - FW) / sr + 1 : 0;
+  for (int64_t r = s->rows_finished; r < done;) {
+    const int64_t slot = r % s->cap;
+    const int64_t nr = std::min<int64_t>({done - r, (int64_t)s->cap - slot, 65535});
+    XL_SPEC_TRY(xl_spec_finish(s->d_max, s->d_db, s->d_px, s->W, s->cap, r, (uint32_t)nr, st));
+    const size_t o = (size_t)slot * W;
+    XL_SPEC_TRY(hipMemcpyAsync(s->h_db + o, s->d_db + o, sizeof(float) * W * nr, hipMemcpyDeviceToHost, st));
+    XL_SPEC_TRY(hipMemcpyAsync(s->h_px + o, s->d_px + o, (size_t)(W * nr), hipMemcpyDeviceToHost, st));
+    r += nr;
+  }
+  s->rows_finished = std::max(s->rows_finished, done);
+  return 0;
+}
+
+static int xl_spec_begin(xlating_spectrum *s, hipStream_t st) {
+  if (s->broken) return -EIO;
+  XL_SPEC_TRY(hipSetDevice(s->device));
+  if (s->fed) XL_SPEC_TRY(hipStreamWaitEvent(st, s->last, 0));
+  return 0;
+}
+
+static int xl_spec_end(xlating_spectrum *s, hipStream_t st, int rc) {
+  if (rc != 0) {
+    s->broken = true;
+    return rc;
+  }
+  XL_SPEC_TRY(hipEventRecord(s->last, st));
+  s->fed = true;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------- C API
+extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int format, xlating_spectrum **out) {
+  if (out == nullptr || width <= 0 || width > XLATING_SPECTRUM_MAX_WIDTH || sampling_rate == 0 || (uint32_t)width > sampling_rate ||
+      (format != XLATING_SPECTRUM_CU8 && format != XLATING_SPECTRUM_CS16 && format != XLATING_SPECTRUM_CF32))
+    return -EINVAL;
+  *out = nullptr;
+  const int dev = xl_hip_select_device(-1);
+  if (dev < 0) {
+    XL_LOG_ERR("xlating_spectrum_create: no usable HIP device (%s); there is no CPU path", xlating_hip_device_info());
+    return -ENODEV;
+  }
+  xlating_spectrum *s = new (std::nothrow) xlating_spectrum();
+  if (s == nullptr) return -ENOMEM;
+  s->sr = sampling_rate, s->W = (uint32_t)width, s->F = sampling_rate / (uint32_t)width, s->fmt = format, s->device = dev;
+  s->ssz = xl_bytes_per_sample(format);  // (bytes per complex sample)
+  s->blue = (s->W & (s->W - 1u)) != 0;
+  s->N = 1;
+  if (s->blue)
+    while (s->N < 2u * s->W - 1u) s->N <<= 1;
+  else
+    s->N = s->W;
+  s->chunk = ((size_t)16 << 20) / s->ssz;
+  if (const char *e = xl_exp_getenv("XL_EXP_SPEC_CHUNK")) {  // test knob: host staging size in samples
+    const long v = strtol(e, nullptr, 10);
+    if (v > 0) s->chunk = (size_t)v;
+  }
+  int rc = 0;
+  hipError_t e = hipSetDevice(dev);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming);
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+    e = hipEventCreateWithFlags(&s->stage_ev[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipHostMalloc(&s->h_stage[i], s->chunk * s->ssz, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc(&s->d_stage[i], s->chunk * s->ssz);
+  }
+  if (e == hipSuccess) e = hipMalloc(&s->d_carry, (size_t)s->W * s->ssz);
+  if (e != hipSuccess) {
+    xl_last_hip_error = e;
+    XL_LOG_ERR("xlating_spectrum_create: %s", hipGetErrorString(e));
+    rc = xl_errno_of_last_hip_error();
+  }
+  if (rc == 0) rc = xl_spec_tables(s);
+  // room for the rows one staging buffer can complete, and two more
+  if (rc == 0) rc = xl_spec_rows_alloc(s, (uint32_t)std::min<size_t>(s->chunk / s->sr + 3, 1u << 16));
+  if (rc != 0) {
+    xlating_spectrum_destroy(s);
+    return rc;
+  }
+  *out = s;
+  return 0;
+}
+
+// host samples: through the two pinned staging buffers (or, pinned_src, straight from the caller's pinned memory, which it keeps
+// until take_rows has returned) into device staging, one span per chunk
+int xl_spectrum_feed_staged(xlating_spectrum *s, const void *samples, size_t n, bool pinned_src) {
+  if (s == nullptr || (samples == nullptr && n > 0)) return -EINVAL;
+  if (n == 0) return 0;
+  hipStream_t st = s->stream;
+  int rc = xl_spec_begin(s, st);
+  if (rc != 0) return rc;
+  const uint8_t *src = static_cast<const uint8_t *>(samples);
+  for (size_t i = 0; i < n && rc == 0;) {
+    const size_t m = std::min(s->chunk, n - i), bytes = m * s->ssz;
+    const int k = s->stage_i;
+    hipError_t e = hipSuccess;
+    if (s->stage_used[k]) e = hipEventSynchronize(s->stage_ev[k]);
+    const void *h = src + i * s->ssz;
+    if (e == hipSuccess && !pinned_src) {
+      memcpy(s->h_stage[k], h, bytes);
+      h = s->h_stage[k];
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_stage[k], h, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(s->stage_ev[k], st);
+    if (e != hipSuccess) {
+      xl_last_hip_error = e;
+      XL_LOG_ERR("xlating_spectrum_feed_host: %s", hipGetErrorString(e));
+      rc = -EIO;
+      break;
+    }
+    s->stage_used[k] = true;
+    s->stage_i ^= 1;
+    rc = xl_spec_span(s, static_cast<const uint8_t *>(s->d_stage[k]), (int64_t)m, st);
+    i += m;
+  }
+  return xl_spec_end(s, st, rc);
+}
+
+extern "C" int xlating_spectrum_feed_host(xlating_spectrum *s, const void *samples, size_t n) {
+  return xl_spectrum_feed_staged(s, samples, n, false);
+}
+
+extern "C" int xlating_spectrum_feed_device(xlating_spectrum *s, const void *dev_samples, size_t n, void *hip_stream) {
+  if (s == nullptr || (dev_samples == nullptr && n > 0)) return -EINVAL;
+  if (n == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  int rc = xl_spec_begin(s, st);
+  if (rc != 0) return rc;
+  const uint8_t *src = static_cast<const uint8_t *>(dev_samples);
+  for (size_t i = 0; i < n && rc == 0;) {
+    const size_t m = std::min<size_t>((size_t)XL_SPEC_SPAN_MAX, n - i);
+    rc = xl_spec_span(s, src + i * s->ssz, (int64_t)m, st);
+    i += m;
+  }
+  return xl_spec_end(s, st, rc);
+}
+
+extern "C" int xlating_spectrum_take_rows(xlating_spectrum *s, float *db, uint8_t *pixels, size_t max_rows) {
+  if (s == nullptr) return -EINVAL;
+  if (s->broken) return -EIO;
+  if (s->fed) {
+    XL_SPEC_TRY(hipSetDevice(s->device));
+    XL_SPEC_TRY(hipEventSynchronize(s->last));
+  }
+  const int64_t n = std::min<int64_t>((int64_t)std::min<size_t>(max_rows, 1u << 30), s->rows_finished - s->rows_taken);
+  const size_t W = s->W;
+  for (int64_t i = 0; i < n; ++i) {
+    const size_t o = (size_t)((s->rows_taken + i) % s->cap) * W;
+    if (db != nullptr) memcpy(db + (size_t)i * W, s->h_db + o, sizeof(float) * W);
+    if (pixels != nullptr) memcpy(pixels + (size_t)i * W, s->h_px + o, W);
+  }
+  s->rows_taken += n;
+  return (int)n;
+}
+
+extern "C" void xlating_spectrum_destroy(xlating_spectrum *s) {
+  if (s == nullptr) return;
+  (void)hipSetDevice(s->device);
+  if (s->fed) (void)hipEventSynchronize(s->last);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  xl_spec_free_rows(s->d_max, s->d_db, s->d_px, s->h_db, s->h_px);
+  for (int i = 0; i < 2; ++i) {
+    if (s->h_stage[i]) (void)hipHostFree(s->h_stage[i]);
+    if (s->d_stage[i]) (void)hipFree(s->d_stage[i]);
+    if (s->stage_ev[i]) (void)hipEventDestroy(s->stage_ev[i]);
+  }
+  if (s->d_carry) (void)hipFree(s->d_carry);
+  if (s->d_tw) (void)hipFree(s->d_tw);
+  if (s->d_chirp) (void)hipFree(s->d_chirp);
+  if (s->d_bspec) (void)hipFree(s->d_bspec);
+  if (s->last) (void)hipEventDestroy(s->last);
+  if (s->stream) (void)hipStreamDestroy(s->stream);
+  delete s;
+}
+
+// spectrogram_main's view (xl_spectrum_core.h)
+size_t xl_spectrum_chunk(const xlating_spectrum *s) { return s->chunk; }
+uint32_t xl_spectrum_bytes_per_sample(const xlating_spectrum *s) { return s->ssz; }
+void *xl_spectrum_pinned_alloc(size_t bytes) {
+  void *p = nullptr;
+  return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+void xl_spectrum_pinned_free(void *p) {
+  if (p) (void)hipHostFree(p);
+}

@@ -1,0 +1,40 @@
+// xl_spectrum.h -- the spectrogram's launches (xl_spectrum.hip) as the streaming core (xl_spectrum.cpp) calls them.
+// Internal to libxlating_spectrum.so; the public interface is include/xlating_spectrum.h.
+#ifndef XL_SPECTRUM_INTERNAL_H_
+#define XL_SPECTRUM_INTERNAL_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define XL_SPEC_MAX_W 8192
+#define XL_SPEC_MAX_L 16384  // Bluestein length for W = 8191: the power of two >= 2 W - 1
+
+// One launch: transforms g0 .. g0 + T - 1 of the stream (transform g = row g / F, k = g % F; its samples start at stream index
+// (g / F) * sr + (g % F) * W).  `in` holds stream samples base .. : every transform of the launch lies inside it, so that the relative
+// offsets fit 32 bits (the core cuts spans to XL_SPEC_SPAN_MAX samples).  Per bin, the power's maximum over a row's transforms goes
+// to rowmax[(row % cap) * W + bin] by an unsigned atomicMax on the float's bits (every power is positive, so the bit order is the
+// value order, and max is exact: the result does not depend on the work split or on arrival order).
+struct XlSpecArgs {
+  const void *in;
+  int64_t base;
+  int64_t g0;
+  uint32_t T;
+  uint32_t F;
+  uint32_t sr;
+  uint32_t W;
+  uint32_t cap;
+  uint32_t *rowmax;
+  const float2 *tw;     // N-point twiddles exp(-2 pi i m / N), m < N (N = W, or L for Bluestein)
+  const float2 *chirp;  // Bluestein: exp(-i pi (n^2 mod 2W) / W), n < W
+  const float2 *bspec;  // Bluestein: FFT_L of the chirp filter, times 1 / L
+  float norm;           // 1.0f / W (spectrogram.c:104)
+};
+
+// N: the transform length (W for a power of two, else the Bluestein L); fmt: XLF_CU8 / XLF_CS16 / XLF_CF32.  0 or a hipError_t.
+int xl_spec_launch(const XlSpecArgs &a, uint32_t N, bool bluestein, int fmt, hipStream_t st);
+
+// Rows r0 .. r0 + nrows - 1 (ring slots row % cap): 10 log10f, the half swap (odd W: the last bin stays), the pixel; writes W floats to
+// db[slot * W ..] and W bytes to px[slot * W ..], and zeroes the slot's maxima for the row that reuses it.
+int xl_spec_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t cap, int64_t r0, uint32_t nrows, hipStream_t st);
+
+#endif
