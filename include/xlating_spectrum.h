@@ -51,6 +51,48 @@ int xlating_spectrum_take_rows(xlating_spectrum *s, float *db, uint8_t *pixels, 
 
 void xlating_spectrum_destroy(xlating_spectrum *s);
 
+/*
+ * The spectrum bank: MANY independent streams of one common width and sample format, each with its own sampling_rate (for example
+ * every client of a batch engine at its output rate), all advanced by ONE feed call whose number of kernel launches and copies does
+ * not depend on how many streams it carries.  Per stream the rows are, bit for bit, the rows an xlating_spectrum of the same
+ * (sampling_rate, width, format) produces from the same samples: everything above about rows, their completion and splits holds per
+ * stream.
+ */
+typedef struct xlating_spectrum_bank xlating_spectrum_bank;
+
+/* width and format as xlating_spectrum_create.  0, -EINVAL, -ENODEV (with a "<3>" line on stderr), -ENOMEM. */
+int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out);
+
+/* A new stream whose sample 0 is the first sample it is fed.  Returns its stream id >= 0 (ids of removed streams are reused), -EINVAL
+ * (sampling_rate == 0 or < width) or -ENOMEM.  Streams may be added and removed between any two feeds; the per-stream device state
+ * grows as streams are added (growing, and removing a stream that has consumed samples, wait for the feeds' work).
+ * remove drops the stream's un-taken rows. */
+int xlating_spectrum_bank_add(xlating_spectrum_bank *b, uint32_t sampling_rate);
+int xlating_spectrum_bank_remove(xlating_spectrum_bank *b, int stream_id);
+
+/* Advance n streams at once: stream ids[i] consumes counts[i] complex samples, read in place from device address dev_samples[i].
+ * ids, dev_samples and counts are HOST arrays, read before the call returns.  An id may appear at most once per call and must be a
+ * live stream, and a count may not exceed 2^30: -EINVAL otherwise, and nothing is consumed.  counts[i] == 0 is allowed.
+ * Stream-ordered on hip_stream (NULL: the default stream) exactly like xlating_spectrum_feed_device: the buffers stay valid until
+ * that stream has passed this call's work, the call does not wait, consecutive feeds may use different streams.
+ * 0, or a negative errno (-EIO after a HIP failure, -ENOMEM; the bank is then unusable). */
+int xlating_spectrum_bank_feed_device(xlating_spectrum_bank *b, size_t n, const int *ids, const void *const *dev_samples,
+                                      const size_t *counts, void *hip_stream);
+
+/* Per stream, like xlating_spectrum_take_rows: up to max_rows completed rows, oldest first; rows are never lost or reordered.  Waits
+ * for the feeds' work only when rows of this stream are still on their way. */
+int xlating_spectrum_bank_take_rows(xlating_spectrum_bank *b, int stream_id, float *db, uint8_t *pixels, size_t max_rows);
+/* Without waiting for the device: the rows of that stream whose work has been queued and that have not been taken. */
+int xlating_spectrum_bank_rows_pending(const xlating_spectrum_bank *b, int stream_id);
+
+/* What the latest feed issued: kernel launches and memory copies (for tests, logs and benchmarks).  A feed is a few launches (carry
+ * appends, one ragged transform launch, carry saves, one finishing launch when rows complete) and one to three copies, times the
+ * number of rounds: a feed that takes a stream through more rows than the bank keeps row slots per stream (2 .. 16 by width) is cut
+ * into rounds. */
+int xlating_spectrum_bank_last_feed_ops(const xlating_spectrum_bank *b, unsigned *launches, unsigned *copies);
+
+void xlating_spectrum_bank_destroy(xlating_spectrum_bank *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -444,6 +444,16 @@ class BatchEngine:
         if code != 0:
             raise XlatingError("xlating_batch_sync", code)
 
+    def record_event(self, event):
+        """Record `event` (a hipEvent_t value, e.g. torch.cuda.Event().cuda_event after a first record) behind the latest call's
+        launches, on the stream(s) they ran on: how another stream waits for a call made on stream="engine"."""
+        L = lib()
+        L.xlating_batch_record_event.argtypes = [C.c_void_p, C.c_void_p]
+        L.xlating_batch_record_event.restype = C.c_int
+        code = L.xlating_batch_record_event(self.h, C.c_void_p(event))
+        if code != 0:
+            raise XlatingError("xlating_batch_record_event", code)
+
     def timing(self, enable):
         """False/0 off, True/1 bracket every block's launches, 2 also time the three polyphase launches separately."""
         lib().xlating_batch_timing(self.h, int(enable))
@@ -700,7 +710,10 @@ def wire_add_client(engine, adm, band_sampling_rate):
 
 # ------------------------------------------------------------------------------------------------- spectrogram (libxlating_spectrum.so)
 SPECTRUM_SYMBOLS = ["xlating_spectrum_create", "xlating_spectrum_feed_host", "xlating_spectrum_feed_device", "xlating_spectrum_take_rows",
-                    "xlating_spectrum_destroy", "spectrogram_main", "spectrogram_sighandler"]
+                    "xlating_spectrum_destroy", "spectrogram_main", "spectrogram_sighandler",
+                    "xlating_spectrum_bank_create", "xlating_spectrum_bank_add", "xlating_spectrum_bank_remove",
+                    "xlating_spectrum_bank_feed_device", "xlating_spectrum_bank_take_rows", "xlating_spectrum_bank_rows_pending",
+                    "xlating_spectrum_bank_last_feed_ops", "xlating_spectrum_bank_destroy"]
 SPECTRUM_FMT = {"cu8": 0, "cs16": 2, "cf32": 3}
 _SPEC_NP = {"cu8": np.uint8, "cs16": np.int16, "cf32": np.float32}
 _slib = None
@@ -732,6 +745,22 @@ def spectrum_lib():
     S.xlating_spectrum_destroy.restype = None
     S.spectrogram_main.argtypes = [C.c_void_p]
     S.spectrogram_main.restype = C.c_int
+    S.xlating_spectrum_bank_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    S.xlating_spectrum_bank_create.restype = C.c_int
+    S.xlating_spectrum_bank_add.argtypes = [C.c_void_p, C.c_uint32]
+    S.xlating_spectrum_bank_add.restype = C.c_int
+    S.xlating_spectrum_bank_remove.argtypes = [C.c_void_p, C.c_int]
+    S.xlating_spectrum_bank_remove.restype = C.c_int
+    S.xlating_spectrum_bank_feed_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    S.xlating_spectrum_bank_feed_device.restype = C.c_int
+    S.xlating_spectrum_bank_take_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    S.xlating_spectrum_bank_take_rows.restype = C.c_int
+    S.xlating_spectrum_bank_rows_pending.argtypes = [C.c_void_p, C.c_int]
+    S.xlating_spectrum_bank_rows_pending.restype = C.c_int
+    S.xlating_spectrum_bank_last_feed_ops.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    S.xlating_spectrum_bank_last_feed_ops.restype = C.c_int
+    S.xlating_spectrum_bank_destroy.argtypes = [C.c_void_p]
+    S.xlating_spectrum_bank_destroy.restype = None
     _slib = S
     return S
 
@@ -780,6 +809,95 @@ class Spectrum:
     def close(self):
         if getattr(self, "h", None):
             spectrum_lib().xlating_spectrum_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpectrumBank:
+    """One `xlating_spectrum_bank *` (include/xlating_spectrum.h): many streams of one width and format, each with its own
+    sampling_rate, advanced together by one feed of device buffers; rows are taken per stream."""
+
+    def __init__(self, width, fmt="cf32"):
+        S = spectrum_lib()
+        if fmt not in SPECTRUM_FMT:
+            raise XlatingError("xlating_spectrum_bank_create", -22)
+        h = C.c_void_p()
+        code = S.xlating_spectrum_bank_create(width, SPECTRUM_FMT[fmt], C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_spectrum_bank_create", code)
+        self.h, self.W, self.fmt = h, width, fmt
+
+    def add(self, sampling_rate):
+        sid = spectrum_lib().xlating_spectrum_bank_add(self.h, sampling_rate)
+        if sid < 0:
+            raise XlatingError("xlating_spectrum_bank_add", sid)
+        return sid
+
+    def remove(self, stream_id):
+        code = spectrum_lib().xlating_spectrum_bank_remove(self.h, stream_id)
+        if code != 0:
+            raise XlatingError("xlating_spectrum_bank_remove", code)
+
+    def feed(self, ids, ptrs, counts, stream=0):
+        """stream ids[i] consumes counts[i] complex samples from device address ptrs[i], in place, ordered on `stream`."""
+        a = np.ascontiguousarray(ids, dtype=np.intc)
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        assert a.size == p.size == c.size
+        code = spectrum_lib().xlating_spectrum_bank_feed_device(self.h, a.size, a.ctypes.data, p.ctypes.data, c.ctypes.data, stream)
+        if code != 0:
+            raise XlatingError("xlating_spectrum_bank_feed_device", code)
+
+    def feed_engine(self, engine, streams, stream=0):
+        """streams: {client id of `engine`: stream id}.  Feeds every listed client's output of the engine's latest call
+        (xlating_batch_output_device: a host-side lookup) in one call.  The caller orders `stream` behind the engine's call (the
+        same stream, or BatchEngine.record_event and a wait when the call ran on stream="engine") and feeds before the next call,
+        which reuses the rows."""
+        self.feed(*self.gather_engine(engine, streams), stream)
+
+    @staticmethod
+    def gather_engine(engine, streams):
+        """-> (stream ids, device pointers, counts) of the listed clients' outputs of the engine's latest call"""
+        ids, ptrs, counts = [], [], []
+        for cid, sid in streams.items():
+            p, n = engine.output_device(cid)
+            ids.append(sid)
+            ptrs.append(p or 0)
+            counts.append(n)
+        return ids, ptrs, counts
+
+    def take_rows(self, stream_id, max_rows=1 << 20):
+        """-> (db float32 [R, W], pixels uint8 [R, W]): the stream's completed rows not taken yet, oldest first."""
+        S = spectrum_lib()
+        n = self.rows_pending(stream_id)
+        n = min(max(n, 0), max_rows)
+        db = np.empty((n, self.W), np.float32)
+        px = np.empty((n, self.W), np.uint8)
+        got = S.xlating_spectrum_bank_take_rows(self.h, stream_id, db.ctypes.data, px.ctypes.data, n) if n else 0
+        if got < 0:
+            raise XlatingError("xlating_spectrum_bank_take_rows", got)
+        return db[:got], px[:got]
+
+    def rows_pending(self, stream_id):
+        n = spectrum_lib().xlating_spectrum_bank_rows_pending(self.h, stream_id)
+        if n < 0:
+            raise XlatingError("xlating_spectrum_bank_rows_pending", n)
+        return n
+
+    def last_feed_ops(self):
+        """-> (kernel launches, memory copies) the latest feed issued"""
+        a, b = C.c_uint(0), C.c_uint(0)
+        spectrum_lib().xlating_spectrum_bank_last_feed_ops(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            spectrum_lib().xlating_spectrum_bank_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -49,16 +49,6 @@ struct xlating_spectrum {
   int stage_i = 0;
 };
 
-#define XL_SPEC_TRY(expr)                                                                                         \
-  do {                                                                                                            \
-    hipError_t xl_e_ = (hipError_t)(expr);                                                                        \
-    if (xl_e_ != hipSuccess) {                                                                                    \
-      xl_last_hip_error = xl_e_;                                                                                  \
-      XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__);                   \
-      return xl_e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                                                       \
-    }                                                                                                             \
-  } while (0)
-
 // ---------------------------------------------------------------------------------------------------------- host tables (double)
 static void xl_fft_double(std::vector<std::complex<double>> &a) {  // in-place radix-2 forward DFT, size a power of two
   const size_t n = a.size();
@@ -79,16 +69,15 @@ static void xl_fft_double(std::vector<std::complex<double>> &a) {  // in-place r
       }
 }
 
-static int xl_spec_tables(xlating_spectrum *s) {
-  const uint32_t W = s->W, N = s->N;
+int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_chirp, float2 **d_bspec) {
   std::vector<float2> tw(N);
   for (uint32_t m = 0; m < N; ++m) {
     const double ang = -2.0 * M_PI * (double)m / (double)N;
     tw[m] = make_float2((float)cos(ang), (float)sin(ang));
   }
-  XL_SPEC_TRY(hipMalloc(&s->d_tw, sizeof(float2) * N));
-  XL_SPEC_TRY(hipMemcpy(s->d_tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
-  if (!s->blue) return 0;
+  XL_SPEC_TRY(hipMalloc(d_tw, sizeof(float2) * N));
+  XL_SPEC_TRY(hipMemcpy(*d_tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+  if (!blue) return 0;
   // chirp c[n] = exp(-i pi (n^2 mod 2W) / W); the filter b[m] = conj(c[|m|]) on -(W-1) .. W-1, wrapped into L
   std::vector<std::complex<double>> c(W), b(N, 0.0);
   for (uint32_t n = 0; n < W; ++n) {
@@ -102,10 +91,10 @@ static int xl_spec_tables(xlating_spectrum *s) {
   std::vector<float2> ch(W), bs(N);
   for (uint32_t n = 0; n < W; ++n) ch[n] = make_float2((float)c[n].real(), (float)c[n].imag());
   for (uint32_t m = 0; m < N; ++m) bs[m] = make_float2((float)(b[m].real() / N), (float)(b[m].imag() / N));
-  XL_SPEC_TRY(hipMalloc(&s->d_chirp, sizeof(float2) * W));
-  XL_SPEC_TRY(hipMemcpy(s->d_chirp, ch.data(), sizeof(float2) * W, hipMemcpyHostToDevice));
-  XL_SPEC_TRY(hipMalloc(&s->d_bspec, sizeof(float2) * N));
-  XL_SPEC_TRY(hipMemcpy(s->d_bspec, bs.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+  XL_SPEC_TRY(hipMalloc(d_chirp, sizeof(float2) * W));
+  XL_SPEC_TRY(hipMemcpy(*d_chirp, ch.data(), sizeof(float2) * W, hipMemcpyHostToDevice));
+  XL_SPEC_TRY(hipMalloc(d_bspec, sizeof(float2) * N));
+  XL_SPEC_TRY(hipMemcpy(*d_bspec, bs.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -275,7 +264,7 @@ extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int fo
     XL_LOG_ERR("xlating_spectrum_create: %s", hipGetErrorString(e));
     rc = xl_errno_of_last_hip_error();
   }
-  if (rc == 0) rc = xl_spec_tables(s);
+  if (rc == 0) rc = xl_spec_tables(s->W, s->N, s->blue, &s->d_tw, &s->d_chirp, &s->d_bspec);
   // room for the rows one staging buffer can complete, and two more
   if (rc == 0) rc = xl_spec_rows_alloc(s, (uint32_t)std::min<size_t>(s->chunk / s->sr + 3, 1u << 16));
   if (rc != 0) {

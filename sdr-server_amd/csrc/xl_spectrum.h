@@ -37,4 +37,19 @@ int xl_spec_launch(const XlSpecArgs &a, uint32_t N, bool bluestein, int fmt, hip
 // db[slot * W ..] and W bytes to px[slot * W ..], and zeroes the slot's maxima for the row that reuses it.
 int xl_spec_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t cap, int64_t r0, uint32_t nrows, hipStream_t st);
 
+// The tables of a width (host, double, rounded to float): N-point twiddles, and for Bluestein the chirp and the chirp filter's spectrum.
+// Device allocations the caller frees.  0 or a negative errno.
+int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_chirp, float2 **d_bspec);
+
+// (needs xl_common.h at the place of use)
+#define XL_SPEC_TRY(expr)                                                                                         \
+  do {                                                                                                            \
+    hipError_t xl_e_ = (hipError_t)(expr);                                                                        \
+    if (xl_e_ != hipSuccess) {                                                                                    \
+      xl_last_hip_error = xl_e_;                                                                                  \
+      XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__);                   \
+      return xl_e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                                                       \
+    }                                                                                                             \
+  } while (0)
+
 #endif

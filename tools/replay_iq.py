@@ -9,10 +9,14 @@ src/sdr/*_device.c, src/tcp_server.c:257-271).
          --client 460112000:48000 --client 460050000:96000 [--gzip] [--variant optimized]
 
 Every --client CENTER_HZ:RATE_HZ goes through the 15-byte wire request, the admission rules and
-xlating_wire_add_client, and ends up as <out>/<id>.cf32[.gz]."""
+xlating_wire_add_client, and ends up as <out>/<id>.cf32[.gz].  With --waterfall-width W every admitted client also gets a stream of a
+spectrum bank (include/xlating_spectrum.h) at its own rate, fed from the engine's device rows after every block, and <out>/<id>.png:
+the 8-bit gray waterfall sdr_spectrogram makes from that client's .cf32 (-w W -s RATE -d cf32)."""
 import argparse
 import os
+import struct
 import sys
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,11 +27,27 @@ import sdr_server_amd as xl  # noqa: E402
 DTYPES = {"cu8": np.uint8, "cs8": np.int8, "cs16": np.int16}
 
 
+def write_gray_png(path, pixels):
+    """pixels: uint8 [H, W] -> an 8-bit grayscale PNG (filter type 0 on every line)"""
+    h, w = pixels.shape
+
+    def chunk(typ, body):
+        return struct.pack(">I", len(body)) + typ + body + struct.pack(">I", zlib.crc32(typ + body) & 0xFFFFFFFF)
+
+    lines = np.concatenate([np.zeros((h, 1), np.uint8), np.ascontiguousarray(pixels, dtype=np.uint8)], axis=1)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(lines.tobytes())) + chunk(b"IEND", b""))
+
+
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
-           gzip=False, writer_threads=2):
-    """clients: [(center_hz, rate_hz)].  Returns {client_id: (center_hz, rate_hz)} of the admitted ones and the list of
-    (center, rate, failure_details) of the rejected ones."""
+           gzip=False, writer_threads=2, waterfall_width=None):
+    """clients: [(center_hz, rate_hz)].  Returns {client_id: (center_hz, rate_hz)} of the admitted ones, the list of
+    (center, rate, failure_details) of the rejected ones and the run's counters.  waterfall_width: also write <out>/<id>.png per
+    admitted client whose output holds at least one row (rate samples)."""
     os.makedirs(out_dir, exist_ok=True)
+    bank = xl.SpectrumBank(waterfall_width, "cf32") if waterfall_width else None
+    streams, rows, samples = {}, {}, {}  # client id -> bank stream, its rows so far, its output samples so far
     eng = xl.BatchEngine(band_rate, fmt, buffer_size)
     sinks = xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
     admitted, rejected = {}, []
@@ -44,6 +64,8 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             continue
         assert sinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
         admitted[cid] = (center, rate)
+        if bank is not None and rate >= waterfall_width:
+            streams[cid], rows[cid], samples[cid] = bank.add(rate), [], 0
     elem = np.dtype(DTYPES[fmt]).itemsize
     per_block = buffer_size // elem  # the devices deliver buffer_size BYTES per callback
     data = np.fromfile(path, dtype=DTYPES[fmt])
@@ -57,12 +79,27 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
         eng.process_host(blk, variant)
         eng.fetch()
         sinks.submit(eng)
+        if streams:  # (fetch has waited for the block; the device rows hold until the next process call)
+            bank.feed_engine(eng, streams)
+            for cid, sid in streams.items():
+                samples[cid] += eng.output_len(cid)
+                if bank.rows_pending(sid):
+                    rows[cid].append(bank.take_rows(sid)[1])
         for cid in sinks.failed():
             sinks.detach(cid)
             eng.remove_client(cid)
             admitted.pop(cid, None)
+            if cid in streams:
+                bank.remove(streams.pop(cid))
         nblocks += 1
     sinks.flush()
+    for cid, sid in streams.items():
+        rows[cid].append(bank.take_rows(sid)[1])
+        px = np.concatenate(rows[cid])[:samples[cid] // admitted[cid][1]]  # (a last row whose skipped tail never came is no row)
+        if px.shape[0] > 0:
+            write_gray_png(os.path.join(out_dir, f"{cid}.png"), px)
+    if bank is not None:
+        bank.close()
     for cid in list(admitted):
         sinks.detach(cid)
     written, dropped = sinks.stats()
@@ -83,10 +120,11 @@ def main():
     ap.add_argument("--lpf-cutoff-rate", type=int, default=5)
     ap.add_argument("--variant", default="optimized", choices=["native", "optimized"])
     ap.add_argument("--gzip", action="store_true")
+    ap.add_argument("--waterfall-width", type=int, default=None, help="also write <id>.png: each client's waterfall, this many bins wide")
     a = ap.parse_args()
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate,
-                          a.variant, a.gzip)
+                          a.variant, a.gzip, waterfall_width=a.waterfall_width)
     for cid, (c, r) in adm.items():
         print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.cf32{'.gz' if a.gzip else ''}")
     for c, r, why in rej:

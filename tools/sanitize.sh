@@ -1,7 +1,8 @@
 #!/bin/bash
 # tools/sanitize.sh -- the memory-checker pass over the HOST code of the library (stand-in for the reference's valgrind runs,
 # test/resources/run_tests.sh:8; no valgrind in this image).  Builds the host-side sources a second time with
-#   -fsanitize=address,undefined   (lpf.c, xl_taps.c, xl_wire.c, xl_sinks.cpp; xl_grid.h through tests/test_grid.py's shim)
+#   -fsanitize=address,undefined   (lpf.c, xl_taps.c, xl_wire.c, xl_sinks.cpp; xl_grid.h through tests/test_grid.py's shim and
+#                                   xl_spectrum_cut.h through tests/test_spectrum_bank_cpu.py's)
 #   -fsanitize=thread              (xl_sinks.cpp: writer threads, bounded queues; + the C sources it is linked with)
 # into sdr-server_amd/build/sanitize/libxlating_host_{asan,tsan}.so and drives them with the EXISTING CPU tests
 # (tests/test_sinks.py, test_wire.py, test_grid.py, the lpf / tap-preparation tests of test_capi_boundary.py).  Symbols of
@@ -14,9 +15,10 @@ CS=$ROOT/sdr-server_amd/csrc
 B=$ROOT/sdr-server_amd/build/sanitize
 REAL=$ROOT/sdr-server_amd/lib/libxlating_hip.so
 mkdir -p $B $ROOT/profiles
-TESTS="tests/test_sinks.py tests/test_wire.py tests/test_grid.py tests/test_capi_boundary.py"
-# (left out: tests of the GPU library's symbol table / device probe, and the one that calls create_frequency_xlating_filter)
-KEXPR="not test_library_exists and not every_declared and not exported_list and not no_oracle and not fails_loudly and not rejects_empty"
+TESTS="tests/test_sinks.py tests/test_wire.py tests/test_grid.py tests/test_capi_boundary.py tests/test_spectrum_bank_cpu.py"
+# (left out: tests of the GPU library's symbol table / device probe, the one that calls create_frequency_xlating_filter, and the
+# spectrum bank's tests other than those of the feed cutting, which need libxlating_spectrum.so)
+KEXPR="not test_library_exists and not every_declared and not exported_list and not no_oracle and not fails_loudly and not rejects_empty and not test_bank_"
 build() {  # $1 = tag, $2 = sanitizer flags
   local tag=$1 flags=$2 d=$B/$1
   rm -rf $d
