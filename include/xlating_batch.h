@@ -64,7 +64,7 @@ int xlating_batch_create(uint32_t sampling_freq, int input_format, uint32_t max_
 int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint32_t max_input_buffer_length,
                                  unsigned max_group_blocks, int device, xlating_batch **batch);
 
-/* Plan options (result-neutral: every setting passes the same parity tests).  Seven of them; name / value:
+/* Plan options (result-neutral: every setting passes the same parity tests).  Eight of them; name / value:
  *   "polyphase"         -1 by the size rule (default: classes of >= 32 clients with >= 2 taps per polyphase branch), 0 never, 1
  *                       whenever the shape allows: which classes take the polyphase overlap-save path in XL_MODE_OPTIMIZED
  *   "polyphase_m"       0 by the size rule, 64, 128, 256: its transform length (the rule: 64 points for classes of more than 64 branches with up
@@ -78,6 +78,12 @@ int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint3
  *                       product, undone exactly) -- for classes of up to 112 branches (decimation <= 112); larger decimations
  *                       multiply float32 operands (v_mfma_f32_32x32x2_f32: exactly the float32 FMA chain).  3: float32 operands for
  *                       EVERY class -- the all-float32 arithmetic of the path, ~40 % slower in the mix launch.  Same 1e-5 bar
+ *   "mix_operand_image" two-half mix of an integer input format, decimation <= 64: the forward launch writes the shared spectra once
+ *                       in the mix launch's operand form (scaled, split in halves, four branches per 16 bytes; the same bytes as the
+ *                       float32 spectra) and the mix launch copies them, instead of every group of 128 clients converting the
+ *                       float32 spectra again.  -1 (default) by the size rule (classes of 768 .. 1088 clients in engines whose calls
+ *                       cover four blocks or more: +3-4 % there, level or behind elsewhere), 0 never, 1 wherever the form exists.
+ *                       The same halves reach the same matrix instructions: outputs identical bit for bit
  *   "inverse_kernel"    128-point polyphase classes: the inverse launch's transform -- in the registers of EIGHT lanes per client
  *                       column as 16 x 8 points with one exchange through LDS (5: xl_inv8.hip), in the registers of FOUR lanes per
  *                       column as 32 x 4 points -- whole-line loads, 256-byte store runs (6: xl_inv32.hip) --, or staged in LDS on

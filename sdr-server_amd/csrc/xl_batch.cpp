@@ -46,6 +46,7 @@
 #include "xl_polyphase.h"
 #include "xl_taps.h"
 #include "xl_wide.h"
+#include "xl_xop_layout.h"
 
 #define XL_NLAUNCH 7
 #define XL_GROUP_MAX 64u  // most blocks per call
@@ -124,6 +125,8 @@ struct PolyClass {
   std::vector<float> col_scale;
   float *d_cscale = nullptr;
   float2 *d_X = nullptr;     // shared spectra [passes][Dpad][M][16]
+  bool ximg = false;         // ... instead in the two-half mix's A-operand form (xl_xop_layout.h: the forward launch converts each value once;
+                             // option "mix_operand_image"): [passes][M][2][2 nkb][16] 16-byte slots in the same buffer
   // two-half mix of a cf32 stream: per segment the largest component of its shared spectra, found by the forward launch (XlpArgs::segmax):
   // two buffers of seg_cap entries, a call uses buffer seg_par; lives and dies with d_X
   uint32_t *d_segmax = nullptr;
@@ -219,6 +222,10 @@ struct xlating_batch_t {
   uint32_t mix_kernel = 1;    // option "mix_kernel": 1 (default) = two-half float16 operands on the matrix cores where the class allows them
                               // (integer input format, D <= 64), float32 operands on the matrix cores everywhere else (cf32 input,
                               // D > 64); 3 = float32 operands for every class (the all-float32 arithmetic of the path)
+  int mix_img = -1;           // option "mix_operand_image": classes on the two-half kernel of up to 8 k-blocks with an integer input format
+                              // (xlp_ximg_eligible) get their shared spectra from the forward launch in the mix's operand form -- -1
+                              // (default) by the size rule (xlp_ximg_pays), 1 wherever the form exists; 0 = float32 spectra, converted
+                              // by every column group's staging
   uint32_t mix_pp = 0;        // XL_EXP_MIX_PP (tuning): passes per workgroup of the mix launch; 0 = the launcher's default
   uint32_t inv_skip_at = 256;  // inverse launch (4-wave workgroups, dealt per CU): one workgroup slot kept empty on the chain CUs
   uint32_t poly_exp = 0;     // XL_TUNING builds: tuning switches of the mix kernel
@@ -488,6 +495,9 @@ extern "C" int xlating_batch_set_option(xlating_batch *b, const char *name, long
   } else if (n == "mix_kernel") {
     if (value != 1 && value != 3) return -EINVAL;
     b->mix_kernel = (uint32_t)value;
+  } else if (n == "mix_operand_image") {
+    if (value < -1 || value > 1) return -EINVAL;
+    b->mix_img = (int)value;
   } else if (n == "expected_clients") {
     if (value < 0 || value > 8192) return -EINVAL;
     b->expected_clients = (uint32_t)value;
@@ -572,6 +582,7 @@ extern "C" int xlating_batch_create_grouped(uint32_t sampling_freq, int input_fo
       bool documented;
     } knobs[] = {{"XL_EXP_POLY", "polyphase", true},          {"XL_EXP_POLY_M", "polyphase_m", true},
                  {"XL_EXP_INV", "inverse_kernel", true},      {"XL_EXP_MIX", "mix_kernel", true},
+                 {"XL_EXP_MIX_IMG", "mix_operand_image", true},
                  {"XL_EXP_NCO_SIDE", "nco_side_stream", true}, {"XL_EXP_EXPECTED", "expected_clients", true},
                  {"XL_EXP_POLY_MIN", "polyphase_min_clients", false}, {"XL_EXP_MIX_PP", "mix_passes_per_workgroup", false},
                  {"XL_EXP_H", "tile_height", false},          {"XL_EXP_RIDERS", "riders", false},
@@ -1008,6 +1019,14 @@ static uint32_t xl_poly_mix_kind(const xlating_batch *b, uint32_t D) {
   return (b->mix_kernel == 3u || !halves_ok) ? 3u : 1u;
 }
 
+// Whether a class's shared spectra are kept in the two-half mix's operand form (PolyClass::ximg, option "mix_operand_image"): where
+// the form exists (xlp_ximg_eligible: a constant scale and xlp_mix_mfma_kernel as the only reader) and, unless the option forces it,
+// where it measured ahead (xlp_ximg_pays, xl_plan_rules.h).
+static bool xl_poly_ximg(const xlating_batch *b, uint32_t D, uint32_t M, size_t members) {
+  if (b->mix_img == 0 || !xlp_ximg_eligible((uint32_t)b->fmt, xl_poly_mix_kind(b, D), (D + 7u) / 8u, M)) return false;
+  return b->mix_img > 0 || xlp_ximg_pays((uint32_t)members, b->gcap);
+}
+
 // Power-of-two scale of a column's branch spectra for the matrix-core mix: every component of R_b[m] = sum_a r_b[a] e^{..} is at
 // most L = max_b sum_a |r_b[a]| (the same for the delayed taps: a delay permutes the branches); scale = 2^floor(log2(RMAX / L)).
 static float xl_poly_col_scale(const Client &c, uint32_t D, uint32_t T) {
@@ -1058,7 +1077,8 @@ static int xl_poly_sync_device(xlating_batch *b, PolyClass &pc, const std::vecto
       xl_plan_release(b, pc.d_X);
       pc.d_X = nullptr;
       // (X: the padding branches and the unused segment slots of the last pass must be finite: cleared once)
-      const size_t xbytes = (size_t)passes * pc.Dpad * pc.M * XLP_XS * sizeof(float2);
+      // (the operand form: groups of four branches beyond the last one the forward launch writes likewise)
+      const size_t xbytes = pc.ximg ? xop_bytes(passes, pc.M, pc.nkb) : (size_t)passes * pc.Dpad * pc.M * XLP_XS * sizeof(float2);
       XL_TRY(xl_plan_alloc(b, (void **)&pc.d_X, xbytes));
       XL_TRY(hipMemsetAsync(pc.d_X, 0, xbytes, b->own_stream));
       xl_plan_release(b, pc.d_segmax);
@@ -1250,7 +1270,8 @@ static int xl_batch_plan(xlating_batch *b) {
         ref = (old->rem_ref0 + advanced % D) % D;
         for (uint32_t r : distinct) dmax = std::max(dmax, (ref + D - r) % D);
         const uint32_t A = (T + dmax + D - 1) / D;
-        reuse = A == old->A && xl_poly_pick_m(b, A, m.size(), D) == old->M && xl_poly_mix_kind(b, D) == old->mix_kind;
+        reuse = A == old->A && xl_poly_pick_m(b, A, m.size(), D) == old->M && xl_poly_mix_kind(b, D) == old->mix_kind &&
+                xl_poly_ximg(b, D, old->M, m.size()) == old->ximg;
       }
       if (!reuse) {
         // the shared grid's reference: the member offset that keeps the largest delay of a member smallest
@@ -1316,6 +1337,7 @@ static int xl_batch_plan(xlating_batch *b) {
         pc.V = M - A + 1;
         pc.mix_kind = xl_poly_mix_kind(b, D);
         pc.nkb = (D + 7u) / 8u;
+        pc.ximg = xl_poly_ximg(b, D, M, m.size());
       }
       pc.keep = false;
       pc.rem_ref0 = ref;
@@ -2031,6 +2053,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
           pc.seg_par ^= 1u;  // (a failed call leaves stale maxima behind at worst: a smaller scale than necessary, never a wrong one)
           pa.W = b->d_W;
           pa.X = pc.d_X;
+          pa.ximg = pc.ximg ? 1u : 0u;
           pa.Y = pc.d_Y;
           pa.cols = pc.d_cols;
           pa.phtab = b->d_phtab[tab];
@@ -2235,7 +2258,7 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
     d += " cls" + std::to_string(k) + " D" + std::to_string(pc.D) + " T" + std::to_string(pc.T) + " cols" +
          std::to_string(pc.members.size()) + " V" + std::to_string(pc.V) + " M" + std::to_string(pc.M);
     if (pc.dmax) d += " offsets<=" + std::to_string(pc.dmax);
-    d += pc.mix_kind == 3u ? " mix=mf32" : " mix=mfma";
+    d += pc.mix_kind == 3u ? " mix=mf32" : (pc.ximg ? " mix=mfma/img" : " mix=mfma");
     if (pc.M == 128u) {
       // (before the class's first launch: what the size rule picks for a call of the plan's full size -- gcap blocks of max_samples)
       const uint32_t kq_full = (uint32_t)(((uint64_t)b->max_samples * b->gcap + pc.D - 1u) / pc.D) + 1u;

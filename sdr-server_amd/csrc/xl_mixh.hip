@@ -15,6 +15,7 @@
 
 #include "xl_poly_dev.h"
 #include "xl_mix_layout.h"
+#include "xl_xop_layout.h"
 
 #include <hip/hip_ext.h>
 
@@ -25,7 +26,7 @@
 //   cols   j = client column c                       B[k][j]                       ( R.re, -R.im )
 //   D[(s, re)][c] = sum_b X.re R.re - X.im R.im      D[(s, im)][c] = sum_b X.im R.re + X.re R.im
 //
-// on v_mfma_f32_32x32x16_f16 (32 rows = the 14 segments of a pass + 2 idle, 32 columns, 16 k = 8 branches per instruction; FP32
+// on v_mfma_f32_32x32x16_f16 (32 rows = the XLP_SEG = 16 segments of a pass x (re, im), 32 columns, 16 k = 8 branches per instruction; FP32
 // accumulation) with every float32 operand v carried as TWO halves, v * scale = h1 + h2 + O(2^-22 |v|):
 //
 //   X R ~ (X1 R1) + (X1 R2 + X2 R1)        three matrix instructions per k-block; the dropped X2 R2 is 2^-22 relative.
@@ -34,7 +35,8 @@
 // 8e-8 of max|y| against 1.9e-7 for the chain: the products are exact in FP32 and the small terms are summed on their own) --
 // and costs 12 half-precision MACs per complex MAC on units 16 x faster than the packed FP32 FMAs the other kernel saturates.
 // The scales are powers of two: XLP_H_XSCALE for the spectra of the INTEGER input formats (bounded: |X| <= M sqrt 2; a cf32
-// stream has no bound, its classes keep xlp_mix_kernel) and per column the one that brings the bound of its branch spectra
+// stream has no a-priori bound: its segments are scaled by what the forward launch found, SEG below) and per column the one that
+// brings the bound of its branch spectra
 // under XLP_H_RMAX (xl_batch.cpp); the sums are multiplied by 1 / (both) before they are stored.  Halves in the subnormal
 // range only ever carry 2^-24 of the operand scale.
 //
@@ -62,12 +64,25 @@
 // inverse.  The float32 matrix instruction (xl_mixf32.hip) remains for D > 112 and as the exact-float32 option (mix_kernel = 3).
 // waves per SIMD: 4 up to 6 k-blocks (122-126 VGPRs; with the segment scales up to 4), 3 up to XLP_NKB_4W = 8 (no spills: at 4 waves
 // 7 / 8 k-blocks spilled 10 / 42 registers); wider classes: xlp_mix_mfma_wide_kernel (xl_mixh2.hip), 2 waves
+//
+// IMG (integer formats; option "mix_operand_image": by the plan's size rule xlp_ximg_pays): the forward launch has written the spectra
+// ONCE in this kernel's A-operand form -- scaled, split, four branches per 16-byte slot, the re rows (xl_xop_layout.h) -- and the staging
+// is a copy plus the im row's rotate and sign flip: NKB / 4 16-byte loads and NKB / 2 16-byte LDS writes per lane and pass instead of
+// one load, four splits, eight packs and sixteen 4-byte LDS writes per round.  The conversion is otherwise repeated by every column
+// group (8 times per call at 1024 clients); the same halves reach the same matrix instructions in the same order, so the results are
+// bit for bit those of the converting staging, which stays as the other arm of the option and for the SEG classes (their scale is
+// known only behind the forward launch).  Measured (profiles/mix_operand_image.txt): a third of the launch's vector instructions gone
+// and the launch itself NOT faster (68.7 -> 71.6 us at 1024 clients: it is bound by its streams) -- what gains is the call where the
+// recurrence kernel bounds it beside these launches (1024 clients x 8 blocks: +3.4 %), hence the size rule.  The copy is load +
+// ds_write_b128 through registers: a direct-to-LDS load of pass p + 2 would land in the buffer pass p still reads, so keeping the
+// request a whole pass ahead of its wait (below) needs a third buffer -- not tried.
 constexpr int xlp_mix_waves(const int nkb, const bool seg) { return nkb > (seg ? 4 : 6) ? 3 : 4; }
 
-template <int NKB, bool SEG>
+template <int NKB, bool SEG, bool IMG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(xlp_mix_waves(NKB, SEG), xlp_mix_waves(NKB, SEG))))
 void xlp_mix_mfma_kernel(const XlpArgs a) {
   static_assert(NKB <= (int)XLP_NKB_4W, "wider classes: xl_mixh2.hip");
+  static_assert(!(SEG && IMG), "the operand image carries the constant scale of the integer formats");
   // A operands of one pass: [term][k-block][lane][8 halves]; two buffers (one barrier per pass: a buffer is rewritten two
   // barriers after it was read)
   __shared__ uint4 xs[2][2][NKB][64];
@@ -90,9 +105,21 @@ void xlp_mix_mfma_kernel(const XlpArgs a) {
   const v4f *__restrict__ Xm = reinterpret_cast<const v4f *>(a.X) + (size_t)m * (XLP_XS / 2u) + sp;
   const size_t xrow = (size_t)M * (XLP_XS / 2u);  // v4f per branch row
   v4f g[ROUNDS];
+  // IMG: the bin's part of the image, xop_bin_slots(NKB) 16-byte slots per pass -- re rows; slot tid + 256 q goes to xs[buf] twice
+  constexpr uint32_t NSL = 2u * 2u * NKB * XOP_SEG;
+  constexpr int CROUNDS = (int)((NSL + 255u) / 256u);
+  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+  const v4u *__restrict__ Xi = reinterpret_cast<const v4u *>(a.X) + xop_bin_base(M, NKB, 0u, m) + tid;
+  v4u gi[CROUNDS];
   uint32_t smx[2] = {0u, 0u};  // SEG: the largest components of this lane's two segments of the requested pass
   const uint32_t *__restrict__ segmax = SEG ? a.segmax + ((size_t)a.seg_par * a.seg_cap + 2u * sp) * XLP_SEGMAX_STRIDE : nullptr;
   auto request = [&](const uint32_t pass) __attribute__((always_inline)) {
+    if (IMG) {
+#pragma unroll
+      for (int q = 0; q < CROUNDS; ++q)  // (an odd NKB leaves waves 2, 3 out of the last round: they load their first slot again)
+        gi[q] = Xi[xop_bin_base(M, NKB, pass, 0u) + (tid + 256u * (uint32_t)q < NSL ? 256u * (uint32_t)q : 0u)];
+      return;
+    }
     if (SEG) smx[0] = segmax[(size_t)pass * XLP_SEG * XLP_SEGMAX_STRIDE], smx[1] = segmax[((size_t)pass * XLP_SEG + 1u) * XLP_SEGMAX_STRIDE];
 #pragma unroll
     for (int q = 0; q < ROUNDS; ++q) {
@@ -102,6 +129,16 @@ void xlp_mix_mfma_kernel(const XlpArgs a) {
     }
   };
   auto stage = [&](const uint32_t buf) __attribute__((always_inline)) {
+    if (IMG) {
+#pragma unroll
+      for (int q = 0; q < CROUNDS; ++q)
+        if (tid + 256u * (uint32_t)q < NSL) {  // (wave-uniform)
+          v4u *const x = reinterpret_cast<v4u *>(&xs[buf][0][0][0]);
+          x[xop_lds_index(tid + 256u * (uint32_t)q, 0u)] = gi[q];
+          x[xop_lds_index(tid + 256u * (uint32_t)q, 1u)] = (v4u){xop_im_dword(gi[q].x), xop_im_dword(gi[q].y), xop_im_dword(gi[q].z), xop_im_dword(gi[q].w)};
+        }
+      return;
+    }
     const float sx0 = SEG ? xlp_seg_scale(smx[0]) : XLP_H_XSCALE, sx1 = SEG ? xlp_seg_scale(smx[1]) : XLP_H_XSCALE;
     if (SEG && tid < 8u) sinv[buf][2u * sp] = xlp_seg_unscale(smx[0]), sinv[buf][2u * sp + 1u] = xlp_seg_unscale(smx[1]);
 #pragma unroll
@@ -219,6 +256,7 @@ static bool xlp_valid_m(uint32_t M) { return M == 64u || M == 128u || M == 256u;
 template <int NKB>
 static void xlp_launch_mix_mfma_n(const XlpArgs &a, const dim3 grid, hipStream_t s) {
   if (a.segmax != nullptr) hipLaunchKernelGGL((xlp_mix_mfma_kernel<NKB, true>), grid, dim3(256), 0, s, a);
+  else if (a.ximg) hipLaunchKernelGGL((xlp_mix_mfma_kernel<NKB, false, true>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((xlp_mix_mfma_kernel<NKB, false>), grid, dim3(256), 0, s, a);
 }
 
@@ -228,11 +266,14 @@ hipError_t xlp_launch_mix(const XlpArgs &a0, hipStream_t s) {
   a.nco_skip = 0u;
   a.nco_skip_at = 0xFFFFFFFFu;
   a.mix_passes = (a0.nseg + XLP_SEG - 1) / XLP_SEG;
+  // (the spectra in operand form: constant scale, the two-half kernel of up to XLP_NKB_4W k-blocks -- nobody else reads that image)
+  if (a0.ximg && (a0.mix_kind != 1u || a0.segmax != nullptr || a0.fmt == XLF_CF32 || a0.nkb > XLP_NKB_4W)) return hipErrorInvalidValue;
   if (a0.mix_kind == 3u) return xlp_launch_mix_f32(a, s);  // float32 operands (xl_mixf32.hip)
   // (a cf32 stream's spectra are unbounded: only with the per-segment scales)
   if (a0.mix_kind != 1u || a0.nkb == 0u || a0.nkb > XLP_NKB_MAX || a0.D > 8u * a0.nkb || a0.Rh == nullptr || a0.cscale == nullptr ||
       (a0.fmt == XLF_CF32 && a0.segmax == nullptr) || (a0.segmax != nullptr && a0.seg_cap < a.mix_passes * XLP_SEG))
     return hipErrorInvalidValue;
+
   // (all passes of an 8-block call in one workgroup: the operands are fetched once; A/B at 4096 clients, passes per
   // workgroup 4 / 8 / 16: 42.5 / 38.5 / 34.8 us per block, at 1024 clients 10.3 / 9.3 / 10.0)
   // (64-point classes: twice the segments for the same samples -- 32 passes, so that a call of the same length still is one run)

@@ -1,6 +1,6 @@
-/* xl_plan_rules.h -- the two SIZE RULES of the engine's plan that were set from measurements of round 5, as plain C so that the
- * CPU suite can pin them (tests/test_plan_rules.py): which inverse kernel a polyphase launch takes, and how many CUs the side-stream
- * recurrence kernel gets.  No HIP types. */
+/* xl_plan_rules.h -- the SIZE RULES of the engine's plan that were set from measurements, as plain C so that the
+ * CPU suite can pin them (tests/test_plan_rules.py): which inverse kernel a polyphase launch takes, how many CUs the side-stream
+ * recurrence kernel gets, and which classes keep their shared spectra in the mix launch's operand form.  No HIP types. */
 #ifndef XL_PLAN_RULES_H_
 #define XL_PLAN_RULES_H_
 #include <stdint.h>
@@ -21,6 +21,22 @@ static inline uint32_t xlp_inverse_pick(uint32_t M, uint32_t inv_reg, uint32_t t
   if (M != 128u) return 3u;
   if (inv_reg == 3u || inv_reg == 5u || inv_reg == 6u) return inv_reg;
   return tiles <= 2048u ? 5u : (tiles <= 8192u ? 3u : 6u);
+}
+
+/* Which classes of `members` clients, in an engine whose calls cover up to `blocks_per_call` blocks, get their shared spectra from the
+ * forward launch in the two-half mix's operand form (xl_xop_layout.h; option "mix_operand_image": -1 = this rule, 0 never, 1 wherever
+ * the form exists).  The form takes a third of the mix launch's vector instructions away (8.98 M -> 6.04 M per call at 1024 clients)
+ * and makes BOTH launches a little slower on their own (rocprofv3, 1024 clients x 8 blocks: mix 68.7 -> 71.6 us, forward 12.3 -> 13.8:
+ * the mix launch is bound by its streams, the staging was never on its critical path; four branches per forward workgroup are a
+ * quarter of the workgroups).  What it buys is the call period where the recurrence kernel bounds the call on a chip the launches keep
+ * busy -- bench.py, same box, alternating, us per block without / with (profiles/mix_operand_image.txt):
+ *     256 clients 22.64 / 22.92    512: 23.82 / 23.84    768: 24.67 / 24.35    896: 25.42 / 24.39    1024: 25.0 / 24.1 (+3.4 %)
+ *     1152: 27.58 / 27.53    1280: 27.90 / 28.00    1536: 32.4 / 32.8    2048, 3072, 4096: level within the runs' spread
+ *   1024 clients by blocks per call (tools/group_sweep.py): 1 block 42.7 / 47.2, 2 blocks 32.6 / 33.8, 4 blocks 30.3 / 29.8
+ * -- ahead from 768 to 1024 clients, level at 1152, behind where the launches bound the call (few blocks per call: the forward
+ * launch's 22 workgroups; 1280+ clients) and where the chip is not busy (256 clients).  So: 768 .. 1088 clients, four blocks or more. */
+static inline int xlp_ximg_pays(uint32_t members, uint32_t blocks_per_call) {
+  return members >= 768u && members <= 1088u && blocks_per_call >= 4u;
 }
 
 /* CUs per XCD reserved for the side-stream recurrence (chain) kernel, whose workgroups -- one per 64 clients -- each own a CU

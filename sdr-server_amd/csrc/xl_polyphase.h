@@ -44,6 +44,12 @@
 #define XLP_FWD_GROUP_MIN_WGS 96u  // forward launch, cf32 streams: groups of adjacent branches per workgroup from this many workgroups on
 #define XLP_BSTEP 2u   // the branch count is padded to a multiple of this in the shared-spectrum image (rows D .. Dpad - 1: zeros)
 
+// Which classes may carry their shared spectra in operand form (option "mix_operand_image"): the scale must be a constant (integer
+// formats), the consumer xlp_mix_mfma_kernel (mix_kind 1, up to XLP_NKB_4W k-blocks); 64-point classes exist for wider ones only
+static inline bool xlp_ximg_eligible(uint32_t fmt, uint32_t mix_kind, uint32_t nkb, uint32_t M) {
+  return fmt != XLF_CF32 && mix_kind == 1u && nkb >= 1u && nkb <= XLP_NKB_4W && (M == 128u || M == 256u);
+}
+
 // Columns of one tile of the mixed spectra Y = [cg][segment][sub][bin M][CW columns] (one inverse workgroup's tile, M x CW x 8 bytes =
 // 32 KB contiguous): 16 (M = 256), 32 (M = 128), 64 (M = 64)
 static inline __host__ __device__ uint32_t xlp_tile_columns(uint32_t M) { return M == 256u ? 16u : (M == 64u ? 64u : 32u); }
@@ -90,6 +96,9 @@ struct XlpArgs {
   unsigned long long *trace;  // tuning only: [0..2] min start / max end of the work waves, [8 + 4 i ..] per NCO wave: start, loaded, end
   const float2 *W;     // e^{-2 pi j n / 256}, n < 256
   float2 *X;           // shared spectra   [pass][Dpad][M][XLP_XS]
+  uint32_t ximg;       // 1: X is instead the re rows of the two-half mix's A operands, [pass][M][term 2][group 2 nkb][segment 16][8 halves]
+                       // (xl_xop_layout.h): written by xlp_forward_kernel<M, 4, true>, staged by xlp_mix_mfma_kernel<NKB, false, true>;
+                       // integer formats, M >= 128, nkb <= XLP_NKB_4W (xlp_ximg_eligible)
   const void *Rh;      // branch spectra in the mix launch's B-operand order.  mix_kind 1: scaled per column and split in two halves,
                        //   [cg][M][32-column quarter][term 2][k-block nkb][lane 64][8 halves] (see xlp_mix_mfma_kernel)
                        // mix_kind 3: the same values as float32 (R.re, -R.im) in v_mfma_f32_32x32x2_f32's B-operand order

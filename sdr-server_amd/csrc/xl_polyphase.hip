@@ -3,10 +3,12 @@
 //
 // Three launches per call and class (stream order is the only synchronisation):
 //   xlp_forward_kernel  one workgroup per (pass of 16 segments, branch): raw samples -> cf32 (xlating.c:357-378, exact)
-//                       -> M-point DFT of the branch per segment -> shared spectra X[pass][b][m][s], stored as whole rows.
+//                       -> M-point DFT of the branch per segment -> shared spectra X[pass][b][m][s], stored as whole rows; for the
+//                       two-half mix of an integer format (D <= 64) instead one workgroup per (pass, FOUR branches), and the spectra
+//                       leave scaled and split, in that mix kernel's A-operand form (xl_xop_layout.h; option "mix_operand_image").
 //   xlp_mix_mfma_kernel (xl_mixh.hip; 9 .. 14 k-blocks: xl_mixh2.hip) Y[c][s][m] = sum_b X[s][b][m] * R[c][b][m] on the matrix cores: one real matrix product per bin m (rows =
 //                       (segment, re / im), columns = clients, k = (branch, re / im)) with every float32 operand carried as two
-//                       halves, v_mfma_f32_32x32x16_f16, FP32 accumulation.  Integer input formats, D <= 64 (the default there).
+//                       halves, v_mfma_f32_32x32x16_f16, FP32 accumulation.  D <= 112; cf32 streams with a scale per segment.
 //   xlp_mix_f32_kernel  (xl_mixf32.hip) the same sums with float32 operands on v_mfma_f32_32x32x2_f32 -- the float32 FMA chain itself:
 //                       cf32 input, D > 64, and every class on request (option "mix_kernel" = 3).
 //   xlp_inverse8_kernel (xl_inv8.hip) / xlp_inverse32_kernel (xl_inv32.hip) (128-point classes: small / big launches) /
@@ -20,6 +22,7 @@
 
 #include "xl_poly_dev.h"
 #include "xl_mix_layout.h"
+#include "xl_xop_layout.h"
 
 #include <hip/hip_ext.h>
 
@@ -39,6 +42,16 @@
 // short calls need (one block per call: 84 workgroups -> 22, 8.7 -> 13.5 us): they keep NB = 1.
 // The spectra go through LDS once more so that the image rows X[pass][b][m][0..15] -- what the mix kernel fetches as one 128-byte
 // row -- leave as whole lines: 8 lanes x 16 bytes per row, a branch's 16 KB (M = 128) back to back.
+//
+// IMG (integer formats whose mix launch is xlp_mix_mfma_kernel<NKB, false, true>): NB = 4 -- a 16-byte slot of that kernel's A operand
+// holds four adjacent branches of one row --, and each value leaves ONCE as what every column group's staging used to make of it:
+// times XLP_H_XSCALE, split by xlp_split_h, (re, im) packed as the segment's re row (the mix's staging derives the im row: bits),
+// first halves into term 0 and second halves into term 1.  A lane holds all four branches of its (segment, bin), i.e. whole slots; they
+// cross LDS once (64 KB = 2 terms x 128 bins x 16 segments, rotated by the bin so that neither side meets a bank twice) and leave as
+// 256-byte runs (xop_in_bin).  For cu8 the four 2-byte gathers of a point also become one 8-byte load.  M = 256: the four transforms
+// run two and two (the rows are the transforms' scratch, and four rows of 320 would not leave room for two workgroups per CU).
+// A quarter of the workgroups: 13.8 against 12.3 us per call of 8 blocks, and calls of one or two blocks lose more than the mix launch
+// gains -- the plan takes this form by a size rule (xlp_ximg_pays, xl_plan_rules.h).
 //
 // NB adjacent samples i .. i + NB - 1 of a raw buffer -> cf32 (xl_sample's maps, xlating.c:357-378: exact), one load (the address is
 // aligned to the SAMPLE, not to the load: global loads take any alignment on this target)
@@ -103,11 +116,14 @@ XL_DEV void xlp_samples(const void *__restrict__ p, const int fmt, const uint32_
   }
 }
 
-template <int M, int NB>
+template <int M, int NB, bool IMG = false>
 __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpArgs a) {
   constexpr uint32_t L = M / 4, NT = XLP_SEG * L;
-  static_assert(XLP_SEG * NB * XLP_ROW(M) * 8 <= 80 * 1024, "two workgroups' rows in a CU's LDS");
-  __shared__ v2f lds[XLP_SEG][NB][XLP_ROW(M)];
+  constexpr int NBD = IMG && M == 256 ? 2 : NB;  // transforms a lane runs side by side
+  static_assert(XLP_SEG * NBD * XLP_ROW(M) * 8 <= 80 * 1024, "two workgroups' rows in a CU's LDS");
+  static_assert(!IMG || (NB == (int)XOP_GROUP && M >= 128 && XLP_SEG * NBD * XLP_ROW(M) * 8 >= 128 * 32 * 16),
+                "operand image: four branches per slot, 2 terms x 128 bins x 16 segments of slots staged at a time");
+  __shared__ v2f lds[XLP_SEG][NBD][XLP_ROW(M)];
   // (cf32 streams on the two-half mix: float bits of the largest |component| of each segment's transforms -- in the one element of a
   // segment's first row that XLP_POS never addresses, so that two workgroups' 80 KB fit a CU's LDS exactly)
   static_assert(XLP_POS(M - 1) < XLP_ROW(M) - 1, "the last element of a padded row is free");
@@ -200,16 +216,52 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
     __builtin_amdgcn_s_waitcnt(0);  // (tuning only: samples and twiddles have arrived)
     t_loaded = wall_clock64();
   }
-  {
-    v2f *bufs[NB];
-    uint32_t rs0[NB];
 #pragma unroll
-    for (int n = 0; n < NB; ++n) bufs[n] = lds[h][n], rs0[n] = 0u;
-    v2f *const(&cb)[NB] = bufs;
-    const uint32_t(&crs)[NB] = rs0;
+  for (int c0 = 0; c0 < NB; c0 += NBD) {  // (one round unless IMG, M = 256; a wave's LDS operations execute in order: the rows are free again)
+    v2f *bufs[NBD];
+    uint32_t rs0[NBD];
+#pragma unroll
+    for (int n = 0; n < NBD; ++n) bufs[n] = lds[h][n], rs0[n] = 0u;
+    v2f *const(&cb)[NBD] = bufs;
+    const uint32_t(&crs)[NBD] = rs0;
 #ifndef XLP_EXP_FWD_NODFT  // (anatomy: wrong results)
-    xlp_dft<-1, NB, M>(u, cb, tw, l, crs);
+    xlp_dft<-1, NBD, M>(*reinterpret_cast<v2f(*)[NBD][4]>(&u[c0]), cb, tw, l, crs);
 #endif
+  }
+  if (IMG) {
+    // ---- operand form.  hp[term][n][r]: the halves of (re, im) of branch b0 + n at bin l + L r, packed; branches >= D: zeros
+    uint32_t hp[2][NB][4];
+#pragma unroll
+    for (int n = 0; n < NB; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        _Float16 r1, r2, i1, i2;
+        xlp_split_h(u[n][r].x * XLP_H_XSCALE, r1, r2);
+        xlp_split_h(u[n][r].y * XLP_H_XSCALE, i1, i2);
+        const bool real = b0 + (uint32_t)n < a.D;
+        hp[0][n][r] = real ? xlp_pack_h(r1, i1) : 0u;  // (= xop_re_dword of the halves' bits)
+        hp[1][n][r] = real ? xlp_pack_h(r2, i2) : 0u;
+      }
+    uint4 *const stg = reinterpret_cast<uint4 *>(&lds[0][0][0]);  // [term][128 bins][16 segments, rotated by the bin]: 64 KB
+    uint4 *__restrict__ const img = reinterpret_cast<uint4 *>(a.X);
+    constexpr int RC = M == 256 ? 2 : 4;  // a lane's bins per 128-bin chunk (bins l + L r, r = rc .. rc + RC - 1)
+#pragma unroll
+    for (int rc = 0; rc < 4; rc += RC) {
+      __syncthreads();  // the transforms' scratch / the previous chunk has been read
+#pragma unroll
+      for (int term = 0; term < 2; ++term)
+#pragma unroll
+        for (int r = rc; r < rc + RC; ++r) {
+          const uint32_t ml = l + L * (uint32_t)(r - rc);  // bin within the chunk
+          stg[((uint32_t)term * 128u + ml) * XOP_SEG + (h ^ (ml & 15u))] = (uint4){hp[term][0][r], hp[term][1][r], hp[term][2][r], hp[term][3][r]};
+        }
+      __syncthreads();
+      for (uint32_t i = j; i < 2u * 128u * XOP_SEG; i += NT) {
+        const uint32_t ml = (i >> 4) & 127u, term = i >> 11, sl = (i & 15u) ^ (ml & 15u);
+        img[xop_bin_base(M, a.nkb, pass, ml + L * (uint32_t)rc) + xop_in_bin(a.nkb, term, grp, sl)] = stg[i];
+      }
+    }
+    return;
   }
   if (a.segmax != nullptr) {
     // cf32 stream on the two-half mix: the segment's largest spectrum component, over all branches -- these transforms' share of it
@@ -226,7 +278,7 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
   }
   // the transforms' rows, natural order (their own scratch: the LDS operations of a wave execute in order)
 #pragma unroll
-  for (int n = 0; n < NB; ++n)
+  for (int n = 0; n < NBD; ++n)  // (NBD = NB here)
 #pragma unroll
     for (int r = 0; r < 4; ++r) lds[h][n][l + L * r] = u[n][r];
   __syncthreads();
@@ -236,7 +288,7 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
   static_assert(XLP_XS == 16u && XLP_SEG <= XLP_XS, "image rows of 16 complex = 8 x 16 bytes");
   unsigned long long t_xf = 0ull;
 #pragma unroll
-  for (int n = 0; n < NB; ++n) {
+  for (int n = 0; n < NBD; ++n) {
     if (b0 + (uint32_t)n >= a.D) break;  // (workgroup-uniform; rows D .. Dpad - 1 of the image stay zero)
     v4f *__restrict__ X = reinterpret_cast<v4f *>(a.X) + ((size_t)pass * a.Dpad + b0 + (uint32_t)n) * M * (XLP_XS / 2u);
     for (uint32_t i = j; i < (uint32_t)M * (XLP_XS / 2u); i += NT) {
@@ -442,6 +494,13 @@ hipError_t xlp_launch_forward(const XlpArgs &a, hipStream_t s) {
   const uint32_t nb = a.M == 256u ? 2u : 4u;  // branches per workgroup of the grouped form (two: level, profiles/r06_forward_groups.txt)
   const uint32_t ngrp = (a.D + nb - 1u) / nb;
   const bool grouped = a.fmt == XLF_CF32 && passes * ngrp >= XLP_FWD_GROUP_MIN_WGS;
+  if (a.ximg) {  // the spectra in the two-half mix's operand form: (pass, four branches) per workgroup, whatever the launch's size
+    if (!xlp_ximg_eligible(a.fmt, a.mix_kind, a.nkb, a.M) || a.D > 8u * a.nkb || a.segmax != nullptr) return hipErrorInvalidValue;
+    const dim3 gridi(a.nco_blocks + passes * ((a.D + XOP_GROUP - 1u) / XOP_GROUP) + a.roll_blocks);
+    if (a.M == 256u) hipLaunchKernelGGL((xlp_forward_kernel<256, 4, true>), gridi, dim3(XLP_SEG * 64u), 0, s, a);
+    else hipLaunchKernelGGL((xlp_forward_kernel<128, 4, true>), gridi, dim3(XLP_SEG * 32u), 0, s, a);
+    return hipGetLastError();
+  }
   const dim3 grid(a.nco_blocks + passes * (grouped ? ngrp : a.D) + a.roll_blocks);
   if (a.M == 256u) {
     if (grouped) hipLaunchKernelGGL((xlp_forward_kernel<256, 2>), grid, dim3(XLP_SEG * 64u), 0, s, a);
