@@ -131,7 +131,7 @@ struct PolyClass {
   // two buffers of seg_cap entries, a call uses buffer seg_par; lives and dies with d_X
   uint32_t *d_segmax = nullptr;
   uint32_t seg_cap = 0, seg_par = 0;
-  float2 *d_Y = nullptr;     // mixed spectra  [ncg][nseg_cap][M][128]
+  float2 *d_Y = nullptr;     // mixed spectra  [cg][nseg_cap][sub][bin M][CW columns] (xl_y_layout.h)
   XlpCol *d_cols = nullptr;  // per column: output row, grid offset, NCO increment
   int last_inv = -1;         // which inverse kernel the class's latest launch took (describe; xlp_inverse_pick): 3 / 5 / 6, -1 = none yet
 };
@@ -1063,7 +1063,7 @@ static int xl_poly_sync_device(xlating_batch *b, PolyClass &pc, const std::vecto
     if (old_bytes) XL_TRY(hipMemcpyAsync(nRh, pc.d_Rh, old_bytes, hipMemcpyDeviceToDevice, b->own_stream));
     XL_TRY(hipMemsetAsync((char *)nRh + old_bytes, 0, (size_t)cap * per_cg - old_bytes, b->own_stream));
     XL_TRY(xl_plan_alloc(b, (void **)&ncs, (size_t)cap * XLP_COLS * sizeof(float)));
-    XL_TRY(xl_plan_alloc(b, (void **)&nY, (size_t)cap * nseg_cap * pc.M * XLP_COLS * sizeof(float2)));
+    XL_TRY(xl_plan_alloc(b, (void **)&nY, xly_bytes(cap, nseg_cap, pc.M)));
     XL_TRY(xl_plan_alloc(b, (void **)&ncols, (size_t)cap * XLP_COLS * sizeof(XlpCol)));
     XL_TRY(hipStreamSynchronize(b->own_stream));
     xl_plan_release(b, pc.d_Rh);

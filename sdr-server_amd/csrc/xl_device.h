@@ -36,8 +36,8 @@
 
 enum { XLF_CU8 = 0, XLF_CS8 = 1, XLF_CS16 = 2, XLF_CF32 = 3 };
 
-#define XL_PH_STRIDE 16u  // the NCO phase table holds every 16th phase: entry (out_off + m) / 16 = phase of output m,
-#define XL_PH_SHIFT 4u    // m = 0 mod 16; the consumers expand the phases in between themselves with the same three IEEE
+// XL_PH_STRIDE = 16, XL_PH_SHIFT (xl_grid.h): the NCO phase table holds every 16th phase: entry (out_off + m) / 16 = phase of output m,
+                          // m = 0 mod 16; the consumers expand the phases in between themselves with the same three IEEE
                           // operations (bit-identical), cooperatively through LDS.  Why: the recurrence is a dependent
                           // chain that caps the block rate, and on a memory-saturated chip every table store blocks
                           // the chain wave ~350 ns, while the bare chain is indifferent to VALU/LDS work sharing its

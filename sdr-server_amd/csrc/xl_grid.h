@@ -1,7 +1,7 @@
 /* xl_grid.h -- the integer bookkeeping of the streaming rule, shared by host code, device code and the CPU tests
  * (tests/test_grid.py compiles this header with gcc and checks it against brute force).
  *
- * Reference: /root/reference/src/xlating.c:52-83.  A filter created at stream position `join` produces output k from
+ * Reference: src/xlating.c:52-83.  A filter created at stream position `join` produces output k from
  * the T samples that END at sample k*D of ITS stream (the reference's working buffer starts with T-1 zeros,
  * xlating.c:552-559), in the process_* call during which that newest sample arrives, and renormalises its NCO phase
  * once at the end of every call that produced output (xlating.c:73).
@@ -20,6 +20,8 @@
 #include <stdint.h>
 
 #define XL_HCAP 16384u /* raw history kept on the device, in samples; T - 1 + D <= XL_HCAP */
+#define XL_PH_STRIDE 16u /* the NCO phase table holds every 16th phase (xl_device.h says why): entry (out_off + m) / 16 = phase of */
+#define XL_PH_SHIFT 4u   /* output m, m = 0 mod 16 */
 
 #if defined(__HIPCC__)
 #define XL_HD __host__ __device__ static inline
@@ -110,5 +112,40 @@ XL_HD uint32_t xl_merge_j0(uint32_t j0_ref, uint32_t delta, uint32_t D) {
 XL_HD uint32_t xl_merge_shift(uint32_t j0_ref, uint32_t delta, uint32_t D) { return j0_ref + delta >= D ? 0u : 1u; }
 /* shared points a call must evaluate so that every member gets all its outputs (q < Kq) */
 XL_HD uint32_t xl_merge_points(uint32_t D, XlPos p) { return (p.S * p.G + D - 1u) / D + 1u; }
+/* outputs a member owns in the call: one more than floor(N / D) when its j0 < N mod D (= XlDyn::K of its own grid) */
+XL_HD uint32_t xl_merge_outputs(uint32_t j0_ref, uint32_t delta, uint32_t D, XlPos p) {
+  const uint32_t N = p.S * p.G, Ka = N / D;
+  return Ka + (xl_merge_j0(j0_ref, delta, D) < N - Ka * D ? 1u : 0u);
+}
+
+/* Phase expansion duty of the inverse launches, per (member column, segment s of V shared points, group g of XL_PH_STRIDE points):
+ * the phases of the column's outputs that are the shared points s V + 16 g .. + 15, walked from ONE entry of the phase table. */
+typedef struct XlColDuty {
+  XlBnd bnd;      /* the column's block boundaries in this call (K: the outputs it owns, whether vacant or not) */
+  uint32_t shift; /* q - k of the column */
+  uint32_t ibeg;  /* 1: the group's first shared point is nobody's output (shared point 0 of a column with shift 1) */
+  uint32_t m0;    /* the column's output index of the first phase to expand */
+  uint32_t ok;    /* 0: nothing to expand (vacant column, group beyond V, outputs beyond K) */
+  uint32_t tab;   /* entry of the column's part of the phase table the walk starts from, m0 / 16 (0 when there is nothing to expand) */
+} XlColDuty;
+XL_HD XlColDuty xl_col_duty(uint32_t j0_ref, uint32_t delta, uint32_t D, XlPos p, uint32_t V, uint32_t s, uint32_t g, int vacant) {
+  XlColDuty d;
+  uint32_t q0;
+  d.bnd.j0 = xl_merge_j0(j0_ref, delta, D), d.bnd.D = D, d.bnd.S = p.S, d.bnd.G = p.G, d.bnd.flags = p.pad;
+  d.bnd.K = xl_merge_outputs(j0_ref, delta, D, p);
+  d.shift = xl_merge_shift(j0_ref, delta, D);
+  q0 = s * V + g * XL_PH_STRIDE;
+  d.ibeg = q0 < d.shift ? 1u : 0u;
+  d.m0 = q0 + d.ibeg - d.shift;
+  d.ok = !vacant && g * XL_PH_STRIDE < V && d.m0 < d.bnd.K ? 1u : 0u;
+  d.tab = d.ok ? d.m0 >> XL_PH_SHIFT : 0u;
+  return d;
+}
+/* phases to expand from output m0 on: to the end of the group or of the column's outputs; 0 when there is nothing to expand.  (A
+ * function of the duty, not a field: a kernel takes it where the walk starts and does not carry it through its transforms.) */
+XL_HD uint32_t xl_col_duty_count(XlColDuty d) {
+  const uint32_t left = d.bnd.K - d.m0, span = XL_PH_STRIDE - d.ibeg;
+  return d.ok ? (left < span ? left : span) : 0u;
+}
 
 #endif /* XL_GRID_H_ */

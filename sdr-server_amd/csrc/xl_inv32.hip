@@ -31,12 +31,8 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(64 * XLI32_WAVES) __attribute__((amdgpu_waves_per_eu(XLI32_WPE, XLI32_WPE))) void xlp_inverse32_kernel(const XlpArgs a) {
   constexpr uint32_t WAVES = XLI32_WAVES, M = 128u, CW = 32u, NSUB = XLP_COLS / CW;
   __shared__ __attribute__((aligned(16))) unsigned char region[WAVES][XLI32_WAVE_BYTES];
-  if (blockIdx.x < a.nco_blocks) {
-    xlp_nco_role(a);
-    return;
-  }
-  if (blockIdx.x >= a.nco_skip_at && blockIdx.x < a.nco_skip_at + a.nco_skip) return;  // (as in xlp_inverse_kernel)
-  const uint32_t bid = blockIdx.x - a.nco_blocks - (blockIdx.x >= a.nco_skip_at ? a.nco_skip : 0u);
+  uint32_t bid;
+  if (!xlp_work_block(a, bid)) return;
   const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = threadIdx.x & 63u;
   const uint32_t unit = bid * WAVES + w;  // half tiles, in the tiles' order (sub fastest, then column group, then segment)
   const uint32_t half = unit & 1u, sub = (unit >> 1) % NSUB;
@@ -63,7 +59,7 @@ __global__ __launch_bounds__(64 * XLI32_WAVES) __attribute__((amdgpu_waves_per_e
   // ---- role 1: lane (m1, c) takes bins m1 + 4 m2, m2 < 32, of column c: four whole lines per instruction
   v2f z[32];
   {
-    const v2f *__restrict__ tile = reinterpret_cast<const v2f *>(a.Y) + ((((size_t)cg * a.nseg_cap + s) * NSUB + sub) * M) * CW;
+    const v2f *__restrict__ tile = reinterpret_cast<const v2f *>(a.Y) + xly_tile(a.nseg_cap, M, cg, s, sub);
     const uint32_t o0 = xli32_load(half, j, 0u);
 #pragma unroll
     for (int m2 = 0; m2 < 32; ++m2) z[m2] = tile[o0 + m2 * 4u * CW];
@@ -79,26 +75,17 @@ __global__ __launch_bounds__(64 * XLI32_WAVES) __attribute__((amdgpu_waves_per_e
 #pragma unroll
   for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(z[i]));  // (all 32 outputs now, not the last stage's operands: fewer registers)
   // ---- what the walk and the stores need of the two columns, and the walk's table entries (the table holds every 16th phase)
-  const uint32_t N = a.pos.S * a.pos.G;
-  const uint32_t Ka = N / a.D, Nr = N - Ka * a.D;  // a column with j0 < Nr owns Ka + 1 outputs, else Ka
   const uint32_t gq = xli32_walk_gq(j);
   XlBnd ebnd[2];
   uint32_t m0[2], cnt[2];  // the column's output index of the first phase to expand, phases to expand (0: none)
   v2f pe[2];
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
-    ebnd[r].j0 = xl_merge_j0(a.j0_ref, ce[r].delta, a.D), ebnd[r].D = a.D, ebnd[r].S = a.pos.S, ebnd[r].G = a.pos.G, ebnd[r].flags = a.pos.pad;
-    ebnd[r].K = ce[r].out_off != 0xFFFFFFFFu ? Ka + (ebnd[r].j0 < Nr ? 1u : 0u) : 0u;
-    const uint32_t esh = xl_merge_shift(a.j0_ref, ce[r].delta, a.D);
-    const uint32_t q0 = s * a.V + gq * XL_PH_STRIDE;
-    const uint32_t ibeg = q0 < esh ? 1u : 0u;  // (shared point 0 of a column with shift 1 is nobody's output)
-    m0[r] = q0 + ibeg - esh;
-    const bool eok = gq * XL_PH_STRIDE < a.V && m0[r] < ebnd[r].K;
-    const uint32_t left = ebnd[r].K - m0[r], span = XL_PH_STRIDE - ibeg;
-    cnt[r] = eok ? (left < span ? left : span) : 0u;
-    pe[r] = reinterpret_cast<const v2f *>(a.phtab)[eok ? (ce[r].out_off >> XL_PH_SHIFT) + (m0[r] >> XL_PH_SHIFT) : 0u];
-    if (gq == 0u) *reinterpret_cast<v4u *>(reg + xli32_meta(8u * r + xli32_walk_c8(j))) = (v4u){ce[r].out_off, esh, ebnd[r].K, ibeg};
-    m0[r] |= ibeg << 31;  // (kept for the walk's LDS address)
+    const XlColDuty du = xl_col_duty(a.j0_ref, ce[r].delta, a.D, a.pos, a.V, s, gq, ce[r].out_off == 0xFFFFFFFFu);
+    ebnd[r] = du.bnd, cnt[r] = xl_col_duty_count(du);
+    pe[r] = reinterpret_cast<const v2f *>(a.phtab)[du.ok ? (ce[r].out_off >> XL_PH_SHIFT) + du.tab : 0u];
+    if (gq == 0u) *reinterpret_cast<v4u *>(reg + xli32_meta(8u * r + xli32_walk_c8(j))) = (v4u){ce[r].out_off, du.shift, ce[r].out_off != 0xFFFFFFFFu ? du.bnd.K : 0u, du.ibeg};
+    m0[r] = du.m0 | du.ibeg << 31;  // (ibeg kept for the walk's LDS address)
   }
   {
     const unsigned char *const twp = reg + xli32_tw(0u, xli32_load_m1(j));

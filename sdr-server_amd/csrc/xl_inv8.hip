@@ -27,21 +27,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr uint32_t M = 128u, CW = 32u, NSUB = XLP_COLS / CW;
   __shared__ __attribute__((aligned(16))) unsigned char region[4][XLI8_WAVE_BYTES];
   __shared__ v2f twl[16][8];  // e^{+2 pi j m1 t / 128}, [t][m1]
-  if (blockIdx.x < a.nco_blocks) {
-    xlp_nco_role(a);
-    return;
-  }
-  if (blockIdx.x >= a.nco_skip_at && blockIdx.x < a.nco_skip_at + a.nco_skip) return;  // (as in xlp_mix_kernel)
-  const uint32_t bid = blockIdx.x - a.nco_blocks - (blockIdx.x >= a.nco_skip_at ? a.nco_skip : 0u);
-#ifdef XLI8_EXP_SFAST  // experiment: consecutive workgroups = consecutive segments of the same 32 columns
-  const uint32_t s = bid % a.nseg;
-  const uint32_t q = bid / a.nseg;
-  const uint32_t sub = q % NSUB, cg = q / NSUB;
-#else
+  uint32_t bid;
+  if (!xlp_work_block(a, bid)) return;
   const uint32_t sub = bid % NSUB;
   const uint32_t q = bid / NSUB;
   const uint32_t cg = q % a.ncg, s = q / a.ncg;
-#endif
   const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), j = threadIdx.x & 63u;
   // ---- role 1: lane (m1, c8) takes bins m1 + 8 m2, m2 < 16, of column 8 w + c8: element (w * 16 + m2) * 64 + j of the tile
   v2f z[16];
@@ -50,15 +40,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // columns), the other halves of the same lines being the neighbour wave's.  (A tile order of its own -- [wave][m2][m1][c8],
     // 512 contiguous bytes per instruction -- was built and measured: the inverse launch gains 2 %, the mix launch, whose stores
     // then go out in 64-byte runs, loses 21 %: profiles/r04_inverse8.txt)
-    const v2f *__restrict__ tile = reinterpret_cast<const v2f *>(a.Y) + ((((size_t)cg * a.nseg_cap + s) * NSUB + sub) * M) * CW;
+    const v2f *__restrict__ tile = reinterpret_cast<const v2f *>(a.Y) + xly_tile(a.nseg_cap, M, cg, s, sub);
     const uint32_t o0 = xli8_load(w, j, 0u);
     constexpr uint32_t os = 8u * CW;  // = xli8_load(w, j, 1) - xli8_load(w, j, 0)
 #pragma unroll
-#ifdef XLI8_EXP_NOLOAD
-    for (int m2 = 0; m2 < 16; ++m2) z[m2] = (v2f){(float)(o0 + m2 * os), 1.0f};
-#else
     for (int m2 = 0; m2 < 16; ++m2) z[m2] = tile[o0 + m2 * os];
-#endif
   }
   if (threadIdx.x < 128u) {  // the twiddle table: a.W = e^{-2 pi j n / 256}
     v2f tv = reinterpret_cast<const v2f *>(a.W)[(2u * (threadIdx.x & 7u) * (threadIdx.x >> 3)) & 255u];
@@ -71,48 +57,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // of the segment, from the one table entry requested here (the table holds every XL_PH_STRIDE-th phase).
   static_assert(XL_PH_STRIDE == 16u, "one table entry per lane: 8 entries per column and segment");
   const uint32_t c8 = xli8_col(j), u = xli8_u(j);
-#ifdef XLI8_EXP_NOMETA  // experiment: no column record, no phase-table entry (synthetic rows of 199936 bytes)
-  XlpCol ce;
-  ce.out_off = (cg * XLP_COLS + sub * CW + 8u * w + c8) * 24992u, ce.delta = 0u, ce.incr = make_float2(1.0f, 0.0f);
-#else
   const XlpCol ce = a.cols[cg * XLP_COLS + sub * CW + 8u * w + c8];
-#endif
-  const uint32_t N = a.pos.S * a.pos.G;
-  const uint32_t Ka = N / a.D, Nr = N - Ka * a.D;  // a column with j0 < Nr owns Ka + 1 outputs, else Ka
-  XlBnd ebnd;
-  ebnd.j0 = xl_merge_j0(a.j0_ref, ce.delta, a.D), ebnd.D = a.D, ebnd.S = a.pos.S, ebnd.G = a.pos.G, ebnd.flags = a.pos.pad;
-  ebnd.K = Ka + (ebnd.j0 < Nr ? 1u : 0u);
-  const uint32_t esh = xl_merge_shift(a.j0_ref, ce.delta, a.D);
-  const uint32_t q0 = s * a.V + u * XL_PH_STRIDE;
-  const uint32_t ibeg = q0 < esh ? 1u : 0u;  // (shared point 0 of a column with shift 1 is nobody's output)
-  const uint32_t m0 = q0 + ibeg - esh;       // the column's output index of the first phase to expand
-  const bool eok = ce.out_off != 0xFFFFFFFFu && u * XL_PH_STRIDE < a.V && m0 < ebnd.K;
-#ifdef XLI8_EXP_NOMETA
-  const v2f pe = {1.0f, eok ? 0.0f : 1.0f};
-#else
-  const v2f pe = reinterpret_cast<const v2f *>(a.phtab)[eok ? (ce.out_off >> XL_PH_SHIFT) + (m0 >> XL_PH_SHIFT) : 0u];
-#endif
+  const XlColDuty du = xl_col_duty(a.j0_ref, ce.delta, a.D, a.pos, a.V, s, u, ce.out_off == 0xFFFFFFFFu);
+  const v2f pe = reinterpret_cast<const v2f *>(a.phtab)[du.ok ? (ce.out_off >> XL_PH_SHIFT) + du.tab : 0u];
   __syncthreads();  // (the table; the tile loads are still travelling)
   unsigned char *const reg = region[w];
-#ifdef XLI8_EXP_COPY  // experiment (wrong results): the launch's memory traffic alone -- tile loads, output stores in the same pattern, no transform, no phases
-  if (ce.out_off != 0xFFFFFFFFu) {
-    v2f *__restrict__ out = reinterpret_cast<v2f *>(a.out) + ce.out_off;
-    const uint32_t qs0 = s * a.V + u;
-#pragma unroll
-    for (int g = 0; g < 8; ++g)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const uint32_t qo = 16u * g + 8u * e + u, qs = qs0 + 16u * g + 8u * e;
-#ifdef XLI8_EXP_NOSTORE
-        if (qo < a.V && qs >= esh && qs - esh < ebnd.K && z[8 * e + g].x == 1.2345e-33f) out[qs - esh] = z[8 * e + g] * pe.x;
-#else
-        if (qo < a.V && qs >= esh && qs - esh < ebnd.K) out[qs - esh] = z[8 * e + g] * pe.x;
-#endif
-      }
-  }
-  (void)reg;
-  return;
-#endif
   // ---- roles 1, 2: Z_m1[t] = 16-point inverse transform over m2, times w^{m1 t}; role 3: into the exchange rows
   xl_fft16_inverse<v2f, XlpFftOps>(z);
   {
@@ -141,10 +90,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   xl_fft8_inverse<v2f, XlpFftOps>(y[0]);
   xl_fft8_inverse<v2f, XlpFftOps>(y[1]);
   // ---- the phases of the wave's 8 x 128 shared points
-  if (eok) {
-    const uint32_t left = ebnd.K - m0, span = XL_PH_STRIDE - ibeg;
-    unsigned char *const pw = reg + xli8_phase(c8, u * XL_PH_STRIDE + ibeg);
-    xl_phase_walk(pe, m0, left < span ? left : span, (v2f){ce.incr.x, ce.incr.y}, ebnd,
+  if (du.ok) {
+    unsigned char *const pw = reg + xli8_phase(c8, u * XL_PH_STRIDE + du.ibeg);
+    xl_phase_walk(pe, du.m0, xl_col_duty_count(du), (v2f){ce.incr.x, ce.incr.y}, du.bnd,
                   [&](uint32_t i, v2f phs) { *reinterpret_cast<v2f *>(pw + i * 8u) = phs; });
   }
   __builtin_amdgcn_wave_barrier();
@@ -159,9 +107,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         const uint32_t qo = 16u * g + 8u * e + u, qs = qs0 + 16u * g + 8u * e;  // shared point of this value: in the segment, in the call
-        if (qo < a.V && qs >= esh && qs - esh < ebnd.K) {
+        if (qo < a.V && qs >= du.shift && qs - du.shift < du.bnd.K) {
           const v2f val = y[e][xli8_slot8(g)] * (1.0f / (float)M);  // exact scaling by 2^-7
-          out[qs - esh] = xl_rotate<1>(val, *reinterpret_cast<const v2f *>(pr + g * XLI8_PROW + e * 64));
+          out[qs - du.shift] = xl_rotate<1>(val, *reinterpret_cast<const v2f *>(pr + g * XLI8_PROW + e * 64));
         }
       }
   }

@@ -44,11 +44,7 @@ XLM_FN size_t xlm_rh_slot(uint32_t cg, uint32_t M, uint32_t m, uint32_t w, uint3
 // sp >> 2) would waste go into the slot's low bits instead: 64 lanes, 64 banks.  The 16-byte operand reads do not care (a group
 // of four lanes still covers the same 64 bytes).
 XLM_FN uint32_t xlm_lds_slot(uint32_t lane_slot) {
-#ifdef XLM_NO_LDS_SWIZZLE  // (A/B builds only: tools/experiments/build_variant.sh)
-  return lane_slot;
-#else
   return lane_slot ^ (((lane_slot >> 5) & 1u) | (((lane_slot >> 4) & 1u) << 1));
-#endif
 }
 
 // Staging role of a lane of wave w in round q: k-block w + 4 q, branch 8 (w + 4 q) + (lane >> 3), segments 2 (lane & 7) and + 1 of

@@ -99,11 +99,7 @@ __global__ __launch_bounds__(256) void xlp_mix_f32_kernel(const XlpArgs a) {
       // drops it.  Unconditional on purpose: a load under `j < D` comes with a branch and a register copy behind it that waits for
       // EVERYTHING in flight -- the operands included)
       const uint32_t j = jr + 32u * (uint32_t)q, jc = j < a.Dpad ? j : a.Dpad - 1u;
-#ifdef XLMF_EXP_NOLOAD
-      g[q] = (v4f32){0.25f, -0.5f, 0.125f, 1.0f};
-#else
       g[q] = *reinterpret_cast<const v4f32 *>(xb + ((size_t)pass * a.Dpad + jc) * xrow);
-#endif
     }
   };
   auto stage = [&](const uint32_t buf) __attribute__((always_inline)) {
@@ -117,11 +113,10 @@ __global__ __launch_bounds__(256) void xlp_mix_f32_kernel(const XlpArgs a) {
   const uint32_t h = lane >> 5, c = lane & 31u;
   const uint32_t sgn = xlmf_a_negate(lane) << 31;
   const uint32_t af = xlmf_a_float(lane);
-  // ---- Y: this lane's column of segment s
-  const uint32_t CW = xlp_tile_columns(M), NSUB = XLP_COLS / CW;
+  // ---- Y (xl_y_layout.h): this lane's column of segment 0
   const uint32_t col = w * 32u + c;
-  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + ((((size_t)cg * a.nseg_cap) * NSUB + col / CW) * M + m) * CW + col % CW;
-  const size_t ystride = (size_t)NSUB * M * CW;  // v2f per segment
+  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + xly_row(a.nseg_cap, M, cg, 0u, col, m) + xly_col_in_tile(M, col);
+  const size_t ystride = xly_seg_stride(M);  // v2f per segment
   // Software pipeline (as xlp_mix_mfma_kernel): the rows of pass p + 1 go into the other buffer AFTER pass p's products and BEFORE
   // its stores, so that the wait for them finds no store younger than pass p - 1's.
   request(job.p0);
@@ -155,7 +150,6 @@ __global__ __launch_bounds__(256) void xlp_mix_f32_kernel(const XlpArgs a) {
     xlmf_store_pass(a, acc, Yc, ystride, pass, h);
     xlmf_lds_barrier();  // the other buffer is staged; everybody is done with this one
   };
-#ifndef XLMF_EXP_NO_PEEL
   // The FIRST pass runs its products as the B operands arrive (they were requested first and return in order: the compiler's waits
   // before product j let the later operands -- and the second pass's rows behind them -- stay in flight): a workgroup of a short run
   // (2-3 passes for small classes) no longer sits out the operands' whole latency before its first matrix instruction.
@@ -166,11 +160,6 @@ __global__ __launch_bounds__(256) void xlp_mix_f32_kernel(const XlpArgs a) {
 #pragma unroll
   for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(bq[j]));
   for (uint32_t pass = job.p0 + 1u; pass < job.p1; ++pass) products(pass, (pass - job.p0) & 1u);
-#else
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(bq[j]));
-  for (uint32_t pass = job.p0; pass < job.p1; ++pass) products(pass, (pass - job.p0) & 1u);
-#endif
 }
 
 // Any branch count (D > 112: huge decimations, few segments per call): the B operands do not fit a wave's registers for all its
@@ -187,10 +176,9 @@ __global__ __launch_bounds__(256) void xlp_mix_f32_stream_kernel(const XlpArgs a
   const uint32_t loff = xlmf_a_float(lane) * 4u;
   const char *__restrict__ xb = reinterpret_cast<const char *>(a.X) + (size_t)m * (XLP_XS * sizeof(float2));
   const size_t xrow = (size_t)M * (XLP_XS * sizeof(float2));
-  const uint32_t CW = xlp_tile_columns(M), NSUB = XLP_COLS / CW;
   const uint32_t col = w * 32u + c;
-  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + ((((size_t)cg * a.nseg_cap) * NSUB + col / CW) * M + m) * CW + col % CW;
-  const size_t ystride = (size_t)NSUB * M * CW;
+  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + xly_row(a.nseg_cap, M, cg, 0u, col, m) + xly_col_in_tile(M, col);
+  const size_t ystride = xly_seg_stride(M);
   struct Block {
     v4f32 b0, b1;
     float x[8];

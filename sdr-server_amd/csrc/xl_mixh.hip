@@ -20,7 +20,7 @@
 #include <hip/hip_ext.h>
 
 // ------------------------------------------------------------------------------------------- mix on the matrix cores
-// The same sums as xlp_mix_kernel, Y[c][s][m] = sum_b X[s][b][m] R[c][b][m], as one real matrix product per bin m:
+// The sums of the mix launch, Y[c][s][m] = sum_b X[s][b][m] R[c][b][m], as one real matrix product per bin m:
 //
 //   rows   i = (segment s, component re / im)        A[i][k]   k = 2 b + {0, 1}:   re row: ( X.re, X.im )   im row: ( X.im, -X.re )
 //   cols   j = client column c                       B[k][j]                       ( R.re, -R.im )
@@ -31,9 +31,9 @@
 //
 //   X R ~ (X1 R1) + (X1 R2 + X2 R1)        three matrix instructions per k-block; the dropped X2 R2 is 2^-22 relative.
 //
-// Measured against the oracle this is as good as the FP32 FMA chain of xlp_mix_kernel (CPU model of the arithmetic:
-// 8e-8 of max|y| against 1.9e-7 for the chain: the products are exact in FP32 and the small terms are summed on their own) --
-// and costs 12 half-precision MACs per complex MAC on units 16 x faster than the packed FP32 FMAs the other kernel saturates.
+// Measured against the oracle this is as good as a float32 FMA chain (the packed-FMA mix kernel of rounds 1-4; CPU model of the
+// arithmetic: 8e-8 of max|y| against 1.9e-7 for the chain: the products are exact in FP32 and the small terms are summed on their
+// own) -- and costs 12 half-precision MACs per complex MAC on units 16 x faster than the packed FP32 FMAs that kernel saturated.
 // The scales are powers of two: XLP_H_XSCALE for the spectra of the INTEGER input formats (bounded: |X| <= M sqrt 2; a cf32
 // stream has no a-priori bound: its segments are scaled by what the forward launch found, SEG below) and per column the one that
 // brings the bound of its branch spectra
@@ -161,12 +161,10 @@ void xlp_mix_mfma_kernel(const XlpArgs a) {
       }
     }
   };
-  // ---- Y image [cg][segment][sub][bin][CW columns] (the inverse workgroups' tiles): this lane's column of segment s
-  const uint32_t CW = xlp_tile_columns(M), NSUB = XLP_COLS / CW;
+  // ---- Y image (xl_y_layout.h: the inverse workgroups' tiles): this lane's column of segment 0
   const uint32_t col = w * 32u + c;
-  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) +
-                         ((((size_t)cg * a.nseg_cap) * NSUB + col / CW) * M + m) * CW + col % CW;
-  const size_t ystride = (size_t)NSUB * M * CW;  // v2f per segment
+  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + xly_row(a.nseg_cap, M, cg, 0u, col, m) + xly_col_in_tile(M, col);
+  const size_t ystride = xly_seg_stride(M);  // v2f per segment
   // Software pipeline: the rows of pass p + 1 are converted into the other buffer AFTER pass p's products and BEFORE its stores
   // -- the wait for those rows (vmcnt counts loads and stores alike, and the two complete out of order: the only safe wait is
   // "all") then finds nothing younger than the stores of pass p - 1, a whole pass old.  Waiting with pass p's stores just
@@ -178,13 +176,8 @@ void xlp_mix_mfma_kernel(const XlpArgs a) {
   v8h r1[NKB], r2[NKB];
 #pragma unroll
   for (int j = 0; j < NKB; ++j) {
-#ifdef XLP_MIX_EXP_NOOPERANDS
-    r1[j] = __builtin_bit_cast(v8h, (uint4){lane, tid, (uint32_t)j, m});
-    r2[j] = __builtin_bit_cast(v8h, (uint4){m, lane, tid, (uint32_t)j});
-#else
     r1[j] = __builtin_bit_cast(v8h, Rp[xlm_rh_slot(cg, M, m, w, 0u, NKB, (uint32_t)j, lane)]);
     r2[j] = __builtin_bit_cast(v8h, Rp[xlm_rh_slot(cg, M, m, w, 1u, NKB, (uint32_t)j, lane)]);
-#endif
   }
   stage(0u);
   if (p0 + 1u < p1) request(p0 + 1u);
@@ -200,18 +193,12 @@ void xlp_mix_mfma_kernel(const XlpArgs a) {
     for (int j = 0; j < NKB; ++j) {
       const v8h a1 = __builtin_bit_cast(v8h, xs[buf][0][j][xlm_lds_slot(lane)]);
       const v8h a2 = __builtin_bit_cast(v8h, xs[buf][1][j][xlm_lds_slot(lane)]);
-#ifdef XLP_MIX_EXP_NOMFMA  // (experiments, wrong results: what is the launch's time made of?  profiles/r05_mix_anatomy.txt)
-      hi[j] += a1[0] * r1[j][0], lo[j] += a2[1] * r2[j][1];
-#else
       lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, r1[j], lo, 0, 0, 0);
       hi = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, r1[j], hi, 0, 0, 0);
       lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, r2[j], lo, 0, 0, 0);
-#endif
     }
-#ifndef XLP_MIX_EXP_NOSTAGE
     if (pass + 1u < p1) stage(buf ^ 1u);
     if (pass + 2u < p1) request(pass + 2u);
-#endif
     // this lane's rows: registers g, g + 1 (g even) = (re, im) of the pass's segment xlm_result_row(g, h) / 2 = 2 h + (g >> 1 & 1) +
     // 4 (g >> 2): one 64-bit product per lane (its first segment), then wave-uniform steps; the bounds test is per lane only in the
     // call's last pass
@@ -229,13 +216,7 @@ void xlp_mix_mfma_kernel(const XlpArgs a) {
           y.x *= si, y.y *= si;
         }
         v2f *const dst = reinterpret_cast<v2f *>(base + cs * sb);
-#ifdef XLP_MIX_EXP_NOSTORE
-        if ((whole || s0 + 2u * h + cs < a.nseg) && y.x == 1.2345e-33f) __builtin_nontemporal_store(y, dst);
-#elif defined(XLP_Y_TEMPORAL)  // (tools/mall_calibration.sh: the same stores with the default cache policy)
-        if (whole || s0 + 2u * h + cs < a.nseg) *dst = y;
-#else
         if (whole || s0 + 2u * h + cs < a.nseg) __builtin_nontemporal_store(y, dst);
-#endif
       }
     }
     xlp_lds_barrier();  // the other buffer is staged; everybody is done with this one

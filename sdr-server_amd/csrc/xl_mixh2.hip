@@ -1,4 +1,4 @@
-// xl_mixh2.hip -- the two-half matrix-core mix (see xlp_mix_mfma_kernel in xl_polyphase.hip for the algebra, the operand layout and the
+// xl_mixh2.hip -- the two-half matrix-core mix (see xlp_mix_mfma_kernel in xl_mixh.hip for the algebra, the operand layout and the
 // scales) for WIDE classes: 9 .. XLP_NKB_MAX = 14 k-blocks of 8 branches (D = 65 .. 112; BASELINE config 5: D = 100).  Same sums
 //
 //   Y[c][s][m] = sum_b X[s][b][m] R[c][b][m]        (src/xlating.c:66-71, evaluated per spectrum bin of the D polyphase branches)
@@ -94,11 +94,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
   };
-  // ---- Y image [cg][segment][sub][bin][CW columns] (the inverse workgroups' tiles): this lane's column of segment s
-  const uint32_t CW = xlp_tile_columns(M), NSUB = XLP_COLS / CW;
+  // ---- Y image (xl_y_layout.h: the inverse workgroups' tiles): this lane's column of segment 0
   const uint32_t col = w * 32u + c;
-  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + ((((size_t)cg * a.nseg_cap) * NSUB + col / CW) * M + m) * CW + col % CW;
-  const size_t ystride = (size_t)NSUB * M * CW;  // v2f per segment
+  v2f *__restrict__ Yc = reinterpret_cast<v2f *>(a.Y) + xly_row(a.nseg_cap, M, cg, 0u, col, m) + xly_col_in_tile(M, col);
+  const size_t ystride = xly_seg_stride(M);  // v2f per segment
   request(p0);
   // ---- B operands of this wave: 2 NKB runs of 1 KB, requested behind the first pass's rows
   const uint4 *__restrict__ Rp = reinterpret_cast<const uint4 *>(a.Rh);
@@ -126,7 +125,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     stage(nxt);
     request(pass + 2u);
-#ifndef XLMH_EXP_NOSCHED
     // instruction order of the block above: A operands XLMH_PF k-blocks ahead; between the matrix instructions of a k-block and the
     // next one's, a share of the staging (masks: 0x008 matrix, 0x100 LDS read, 0x200 LDS write, 0x002 vector ALU, 0x020 memory read)
     __builtin_amdgcn_sched_group_barrier(0x100, 2 * XLMH_PF, 0);
@@ -134,12 +132,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int j = 0; j < NKB; ++j) {
       __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
       if (j + XLMH_PF < NKB) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-#ifndef XLMH_EXP_NOINTERLEAVE
       __builtin_amdgcn_sched_group_barrier(0x002, 14, 0);
       __builtin_amdgcn_sched_group_barrier(0x200, 3, 0);
-#endif
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);  // (the epilogue's LDS reads and stores are not part of the pattern above)
     // this lane's rows: registers g, g + 1 (g even) = (re, im) of the pass's segment 2 h + (g >> 1 & 1) + 4 (g >> 2)
     {

@@ -1,5 +1,6 @@
-// xl_poly_dev.h -- device helpers shared by the polyphase kernels (xl_polyphase.hip: forward / mix / inverse launches;
-// xl_fused.hip: the fused mix + inverse launch): complex products, the M-point Stockham transform staged in LDS, the
+// xl_poly_dev.h -- device helpers shared by the polyphase kernels (xl_polyphase.hip: forward / inverse launches; xl_mixh.hip,
+// xl_mixh2.hip, xl_mixf32.hip: mix launches; xl_inv8.hip, xl_inv32.hip: inverse launches): complex products, the M-point
+// Stockham transform staged in LDS, the work index of an inverse workgroup, the
 // packed-instruction arithmetic policy of the register transforms (xl_fft16.h), the two-half split of float32 values for
 // the matrix cores, and the branch spectra of a client column.  Include only from .hip files compiled -ffp-contract=off.
 #ifndef XL_POLY_DEV_H_
@@ -139,11 +140,7 @@ typedef float v16f32 __attribute__((ext_vector_type(16)));
 // v * scale as two halves; (lo, hi) of the returned pairs: first terms, second terms
 // Workgroup barrier for LDS hand-offs only: this wave's LDS operations are done (lgkmcnt), everybody arrives.  __syncthreads() also
 // fences global memory, which on this target is `s_waitcnt vmcnt(0)`: a wait for every load and store the wave has in flight.
-#ifdef XLP_EXP_SYNCTHREADS  // (A/B builds only, tools/experiments/build_variant.sh: the barrier of rounds 3-5)
-XL_DEV void xlp_lds_barrier() { __syncthreads(); }
-#else
 XL_DEV void xlp_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#endif
 
 // Two-half mix of a cf32 stream: the power-of-two scale of a segment's rows from the float bits of its largest spectrum component
 // (XlpArgs::segmax): 2^(14 - e), e = floor(log2 max) -- every scaled component < 2^15 --, and what undoes it.
@@ -230,13 +227,8 @@ XL_DEV void xlp_branch_spectrum(const float2 *__restrict__ rt, const uint32_t nl
 XL_DEV void xlp_mix_place(const uint32_t bid, const uint32_t M, const uint32_t runs, uint32_t &m, uint32_t &cg, uint32_t &run) {
   const uint32_t grp = bid / (8u * runs), rr = bid - grp * 8u * runs;
   run = rr >> 3;
-#ifdef XLP_MIX_BINS_STRIDED  // (experiment: round 3's placement -- XCD x takes the bins = x mod 8)
-  const uint32_t pair = grp * 8u + (rr & 7u);
-  m = pair & (M - 1u), cg = pair / M;
-#else
   const uint32_t per = M >> 3;
   m = (rr & 7u) * per + grp % per, cg = grp / per;
-#endif
 }
 
 // NCO role of a launch: the first a.nco_blocks workgroups carry XL_NCO_LANES clients each (first wave only) through
@@ -268,12 +260,27 @@ XL_DEV void xlp_nco_role(const XlpArgs &a) {
   }
 }
 
+// What workgroup blockIdx.x of an inverse launch is: one of the a.nco_blocks role workgroups in front (served here), one of the a.nco_skip
+// workgroups at a.nco_skip_at that exit at once (a slot kept empty on the role's CUs) -- false for both --, or work item xlp_work_index.
+XL_DEV bool xlp_work_role_or_skip(const XlpArgs &a) {
+  if (blockIdx.x < a.nco_blocks) {
+    xlp_nco_role(a);
+    return true;
+  }
+  return blockIdx.x >= a.nco_skip_at && blockIdx.x < a.nco_skip_at + a.nco_skip;
+}
+XL_DEV uint32_t xlp_work_index(const XlpArgs &a) { return blockIdx.x - a.nco_blocks - (blockIdx.x >= a.nco_skip_at ? a.nco_skip : 0u); }
+XL_DEV bool xlp_work_block(const XlpArgs &a, uint32_t &bid) {
+  if (xlp_work_role_or_skip(a)) return false;
+  bid = xlp_work_index(a);
+  return true;
+}
+
 // tuning: time span of the work (non-NCO) waves of a launch
 XL_DEV void xlp_trace_work(const XlpArgs &a, const unsigned long long t0) {
 #ifdef XL_TUNING  // (the engine only ever sets a.trace in a tuning build; outside one the bookkeeping is not carried along)
   if (a.trace && (threadIdx.x & 63u) == 0u) {  // per work wave: start, end, placement (own slot: no atomics)
-    const uint32_t bid = blockIdx.x - a.nco_blocks - (blockIdx.x >= a.nco_skip_at ? a.nco_skip : 0u);
-    const uint32_t slot = bid * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint32_t slot = xlp_work_index(a) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (slot < 6000u) {
       unsigned long long *t = a.trace + 4096 + 4 * (size_t)slot;
       t[0] = t0;

@@ -26,6 +26,7 @@
 #define XL_POLYPHASE_H_
 #include "xl_device.h"
 #include "xl_plan_rules.h"
+#include "xl_y_layout.h"
 
 #define XLP_M_MAX 256u  // transform length M (branch samples per segment): 256, 128 or 64, chosen per class (xl_batch.cpp: xl_poly_pick_m)
 #define XLP_SEG 16u    // segments per pass of the mix launches: with (re, im) the 32 rows of a matrix instruction (round 5; 14 before: the
@@ -50,9 +51,7 @@ static inline bool xlp_ximg_eligible(uint32_t fmt, uint32_t mix_kind, uint32_t n
   return fmt != XLF_CF32 && mix_kind == 1u && nkb >= 1u && nkb <= XLP_NKB_4W && (M == 128u || M == 256u);
 }
 
-// Columns of one tile of the mixed spectra Y = [cg][segment][sub][bin M][CW columns] (one inverse workgroup's tile, M x CW x 8 bytes =
-// 32 KB contiguous): 16 (M = 256), 32 (M = 128), 64 (M = 64)
-static inline __host__ __device__ uint32_t xlp_tile_columns(uint32_t M) { return M == 256u ? 16u : (M == 64u ? 64u : 32u); }
+static_assert(XLP_COLS == XLY_COLS, "a column group of the Y image (xl_y_layout.h) is a mix workgroup's columns");
 
 // One client column of a class: 16 bytes, one load.
 struct XlpCol {
@@ -104,7 +103,7 @@ struct XlpArgs {
                        // mix_kind 3: the same values as float32 (R.re, -R.im) in v_mfma_f32_32x32x2_f32's B-operand order
                        //   [cg][M][32-column quarter][k-block nkb][half 2][lane 64][4 branches] (xl_mixf_layout.h)
   const float *cscale; // mix_kind 1: per column, what the sums are multiplied by = 1 / (column scale * XLP_H_XSCALE) (segmax: 1 / column scale)
-  float2 *Y;           // mixed spectra    [cg][nseg_cap][sub][M][CW], CW = 32 (M = 128) / 16 (M = 256) columns: one inverse tile contiguous
+  float2 *Y;           // mixed spectra    [cg][nseg_cap][sub][bin M][CW columns], one inverse tile contiguous (xl_y_layout.h)
   const XlpCol *cols;  // per column
   const float2 *phtab;
   float2 *out;

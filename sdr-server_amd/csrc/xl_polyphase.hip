@@ -1,5 +1,5 @@
 // xl_polyphase.hip -- polyphase overlap-save evaluation of the frequency-xlating FIR (see xl_polyphase.h for the
-// algebra and why it is the same operator as /root/reference/src/xlating.c:52-72).  Hand-written for gfx950.
+// algebra and why it is the same operator as the reference's src/xlating.c:52-72).  Hand-written for gfx950.
 //
 // Three launches per call and class (stream order is the only synchronisation):
 //   xlp_forward_kernel  one workgroup per (pass of 16 segments, branch): raw samples -> cf32 (xlating.c:357-378, exact)
@@ -10,7 +10,7 @@
 //                       (segment, re / im), columns = clients, k = (branch, re / im)) with every float32 operand carried as two
 //                       halves, v_mfma_f32_32x32x16_f16, FP32 accumulation.  D <= 112; cf32 streams with a scale per segment.
 //   xlp_mix_f32_kernel  (xl_mixf32.hip) the same sums with float32 operands on v_mfma_f32_32x32x2_f32 -- the float32 FMA chain itself:
-//                       cf32 input, D > 64, and every class on request (option "mix_kernel" = 3).
+//                       D > 112, and every class on request (option "mix_kernel" = 3).
 //   xlp_inverse8_kernel (xl_inv8.hip) / xlp_inverse32_kernel (xl_inv32.hip) (128-point classes: small / big launches) /
 //   xlp_inverse_kernel  (256-point classes; 128-point ones on request): per (segment, 32 or 16 columns): Y tile -> M-point inverse DFT
 //                       per column -> scale, NCO rotate (xlating.c:70) with the tabulated float32 phase -> out[k], k < K.
@@ -160,15 +160,11 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
   // 128-byte line, D = 100 branches per period) it then pulls a fraction of the block's lines through its L2 instead of all of them.
   uint32_t pass, grp;
   {
-#ifdef XLP_EXP_FWD_PASS_MAJOR
-    pass = bid / ngrp, grp = bid - pass * ngrp;
-#else
     const uint32_t x = bid & 7u, kx = bid >> 3;
     uint32_t start = 0u;  // workgroups of the XCDs below x: XCD y holds the bids y, y + 8, .. < nwg
     for (uint32_t y = 0u; y < x; ++y) start += (nwg - y + 7u) >> 3;
     const uint32_t jj = start + kx;
     grp = jj / passes, pass = jj - grp * passes;
-#endif
   }
   const uint32_t b0 = grp * (uint32_t)NB;  // branches b0 .. b0 + NB - 1 (those >= D: computed from real samples, never stored)
   const uint32_t s = pass * XLP_SEG + h;
@@ -189,10 +185,6 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
     v2f v[NB];
     // all NB samples real and in ONE of the two buffers: one load.  Else (the window's edges: below the late joiners' zero line, across
     // history | block, past the block's end -- those outputs lie beyond K and are never stored) sample by sample.
-#ifdef XLP_EXP_FWD_NOLOAD  // (anatomy: wrong results)
-#pragma unroll
-    for (int n = 0; n < NB; ++n) v[n] = (v2f){(float)(idx + n), 1.0f};
-#else
     const bool whole = NB > 1 && live && idx >= a.zero_below && idx + (uint32_t)NB <= end && (idx + (uint32_t)NB <= a.n0 || idx >= a.n0);
     if (whole) {
       const bool lo = idx < a.n0;
@@ -207,7 +199,6 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
         v[n] = ok ? t : (v2f){0.0f, 0.0f};
       }
     }
-#endif
 #pragma unroll
     for (int n = 0; n < NB; ++n) u[n][r] = v[n];
   }
@@ -224,9 +215,7 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
     for (int n = 0; n < NBD; ++n) bufs[n] = lds[h][n], rs0[n] = 0u;
     v2f *const(&cb)[NBD] = bufs;
     const uint32_t(&crs)[NBD] = rs0;
-#ifndef XLP_EXP_FWD_NODFT  // (anatomy: wrong results)
     xlp_dft<-1, NBD, M>(*reinterpret_cast<v2f(*)[NBD][4]>(&u[c0]), cb, tw, l, crs);
-#endif
   }
   if (IMG) {
     // ---- operand form.  hp[term][n][r]: the halves of (re, im) of branch b0 + n at bin l + L r, packed; branches >= D: zeros
@@ -295,9 +284,6 @@ __global__ __launch_bounds__(XLP_SEG * M / 4) void xlp_forward_kernel(const XlpA
       const uint32_t m = i >> 3, part = i & 7u;  // row m, segments 2 part and 2 part + 1
       const v2f x0 = 2u * part < XLP_SEG ? lds[2u * part][n][m] : (v2f){0.0f, 0.0f};
       const v2f x1 = 2u * part + 1u < XLP_SEG ? lds[2u * part + 1u][n][m] : (v2f){0.0f, 0.0f};
-#ifdef XLP_EXP_FWD_NOSTORE  // (anatomy: wrong results)
-      if (x0.x == 1.2345e-30f)
-#endif
       X[i] = (v4f){x0.x, x0.y, x1.x, x1.y};
     }
   }
@@ -323,20 +309,16 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   constexpr bool SWZ = !__is_same(P, XlpPosPad);
   static_assert(!SWZ || M == 128, "the swizzled layout is written for rows of 128 elements");
   constexpr uint32_t L = M / 4;            // lanes per transform
-  constexpr uint32_t CW = 16u * (256 / M);  // columns per workgroup
+  constexpr uint32_t CW = xly_tile_columns(M);  // columns per workgroup: one tile of Y
   constexpr uint32_t WPC = CW / 4;          // columns per wave
   constexpr uint32_t NSUB = XLP_COLS / CW;  // workgroups per column group
   // [column][padded bin position].  Row length XLP_POS(M - 1) + 1 (319 / 159): 2 banks short of a multiple of 32, so
   // the lanes that fill different rows of one bin hit distinct bank pairs; and 16 x 319 x 8 B = 40832 B lets a CU hold
   // four workgroups (at 41.2 KB it held three: 768 slots for the 832 workgroups of a 1024-client block -> a second round)
   __shared__ v2f tile[CW][SWZ ? M : XLP_ROW(M) - 1];
-  if (blockIdx.x < a.nco_blocks) {
-    xlp_nco_role(a);
-    return;
-  }
-  if (blockIdx.x >= a.nco_skip_at && blockIdx.x < a.nco_skip_at + a.nco_skip) return;  // (as in xlp_mix_kernel; 4-wave workgroups: per CU)
+  if (xlp_work_role_or_skip(a)) return;  // (xlp_work_block, around the stamp)
   const unsigned long long t_begin = a.trace ? wall_clock64() : 0ull;
-  const uint32_t bid = blockIdx.x - a.nco_blocks - (blockIdx.x >= a.nco_skip_at ? a.nco_skip : 0u);
+  const uint32_t bid = xlp_work_index(a);
   const uint32_t sub = bid % NSUB;
   const uint32_t q = bid / NSUB;
   const uint32_t cg = q % a.ncg, s = q / a.ncg;
@@ -350,8 +332,7 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
     const uint32_t part = threadIdx.x % PARTS, mrow = threadIdx.x / PARTS;
     v4f v[8];
     {
-      const v4f *__restrict__ src = reinterpret_cast<const v4f *>(
-          a.Y + ((((size_t)cg * a.nseg_cap + s) * NSUB + sub) * M) * CW) + part;
+      const v4f *__restrict__ src = reinterpret_cast<const v4f *>(a.Y + xly_tile(a.nseg_cap, M, cg, s, sub)) + part;
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = src[(size_t)(mrow + MR * i) * PARTS];
     }
@@ -370,8 +351,6 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   // l + L r from there.  The one table entry a lane needs is requested here, before the transforms.
   constexpr uint32_t GQ = M / XL_PH_STRIDE;
   static_assert(WPC * GQ == 64u, "one expansion duty per lane");
-  const uint32_t N = a.pos.S * a.pos.G;
-  const uint32_t Ka = N / a.D, Nr = N - Ka * a.D;  // a column with j0 < Nr owns Ka + 1 outputs, else Ka
   const v2f *__restrict__ ph = reinterpret_cast<const v2f *>(a.phtab);
   v2f *__restrict__ out = reinterpret_cast<v2f *>(a.out);
   const uint32_t colbase = cg * XLP_COLS + sub * CW + WPC * w;
@@ -379,22 +358,14 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
     const XlpCol c = a.cols[colbase + 4u * h + n];
-    const uint32_t j0c = xl_merge_j0(a.j0_ref, c.delta, a.D);
     off[n] = c.out_off;
     ksh[n] = xl_merge_shift(a.j0_ref, c.delta, a.D);
-    kc[n] = Ka + (j0c < Nr ? 1u : 0u);
+    kc[n] = xl_merge_outputs(a.j0_ref, c.delta, a.D, a.pos);
   }
   const uint32_t en = j / GQ, gq = j % GQ;  // expansion duty: column en of the wave, shared points s V + gq*XL_PH_STRIDE ..
   const XlpCol ce = a.cols[colbase + en];
-  XlBnd ebnd;
-  ebnd.j0 = xl_merge_j0(a.j0_ref, ce.delta, a.D), ebnd.D = a.D, ebnd.S = a.pos.S, ebnd.G = a.pos.G, ebnd.flags = a.pos.pad;
-  ebnd.K = Ka + (ebnd.j0 < Nr ? 1u : 0u);
-  const uint32_t esh = xl_merge_shift(a.j0_ref, ce.delta, a.D);
-  const uint32_t q0 = s * a.V + gq * XL_PH_STRIDE;
-  const uint32_t ibeg = q0 < esh ? 1u : 0u;     // (shared point 0 of a column with shift 1 is nobody's output)
-  const uint32_t m0 = q0 + ibeg - esh;          // the column's output index of the first phase to expand
-  const bool eok = ce.out_off != 0xFFFFFFFFu && gq * XL_PH_STRIDE < a.V && m0 < ebnd.K;
-  const v2f pe = ph[eok ? (ce.out_off >> XL_PH_SHIFT) + (m0 >> XL_PH_SHIFT) : 0u];
+  const XlColDuty du = xl_col_duty(a.j0_ref, ce.delta, a.D, a.pos, a.V, s, gq, ce.out_off == 0xFFFFFFFFu);
+  const v2f pe = ph[du.ok ? (ce.out_off >> XL_PH_SHIFT) + du.tab : 0u];
   __syncthreads();
   const unsigned long long t_loaded = a.trace ? wall_clock64() : 0ull;
   v2f u[4][4];
@@ -409,12 +380,11 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   __builtin_amdgcn_wave_barrier();
   xlp_dft<+1, 4, M, P>(u, rows, tw, l, rs);
   __builtin_amdgcn_wave_barrier();
-  if (eok) {
+  if (du.ok) {
     v2f *__restrict__ row = tile[WPC * w + en];
     const uint32_t ers = XLP_SWZ_ROW(WPC * w + en);
-    const uint32_t left = ebnd.K - m0, span = XL_PH_STRIDE - ibeg;
-    const uint32_t p0 = gq * XL_PH_STRIDE + ibeg;
-    xl_phase_walk(pe, m0, left < span ? left : span, (v2f){ce.incr.x, ce.incr.y}, ebnd,
+    const uint32_t p0 = gq * XL_PH_STRIDE + du.ibeg;
+    xl_phase_walk(pe, du.m0, xl_col_duty_count(du), (v2f){ce.incr.x, ce.incr.y}, du.bnd,
                   [&](uint32_t i, v2f phs) { row[P::pos(p0 + i, ers)] = phs; });
   }
   __builtin_amdgcn_wave_barrier();
@@ -531,7 +501,7 @@ hipError_t xlp_launch_inverse(const XlpArgs &a0, hipStream_t s, hipEvent_t done)
   // 128-point classes: eight lanes per column, transforms of 16 and 8 points in registers (xl_inv8.hip), the 32 x 4 cut (xl_inv32.hip),
   // or staged in LDS on dense XOR-swizzled rows -- xlp_inverse_pick() says which; 256-point classes: staged in LDS on padded rows.
   // Workgroup = one tile of 32 (16) columns.
-  const uint32_t tiles = a0.nseg * a0.ncg * (XLP_COLS / xlp_tile_columns(a0.M));
+  const uint32_t tiles = a0.nseg * a0.ncg * (XLP_COLS / xly_tile_columns(a0.M));
   const uint32_t kind = xlp_inverse_pick(a0.M, a0.inv_reg, tiles);
   const uint32_t work = kind == 6u ? xlp_inverse32_work(tiles) : tiles;
   const XlpArgs a = xlp_checked_skip(a0, work);

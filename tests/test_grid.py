@@ -35,6 +35,13 @@ uint32_t g_bnd_next(uint32_t j0, uint32_t D, uint32_t S, uint32_t G, uint32_t K,
 uint32_t g_merge_j0(uint32_t j0_ref, uint32_t delta, uint32_t D) { return xl_merge_j0(j0_ref, delta, D); }
 uint32_t g_merge_shift(uint32_t j0_ref, uint32_t delta, uint32_t D) { return xl_merge_shift(j0_ref, delta, D); }
 uint32_t g_merge_points(uint32_t D, uint32_t S, uint32_t G) { XlPos p = {0, S, G, 0}; return xl_merge_points(D, p); }
+void g_col_duty(uint32_t j0_ref, uint32_t delta, uint32_t D, uint32_t S, uint32_t G, uint32_t V, uint32_t s, uint32_t g, int vacant,
+                uint32_t *out) {
+  XlPos p = {0, S, G, 0};
+  XlColDuty d = xl_col_duty(j0_ref, delta, D, p, V, s, g, vacant);
+  out[0] = d.bnd.K; out[1] = d.shift; out[2] = d.ibeg; out[3] = d.m0; out[4] = xl_col_duty_count(d); out[5] = d.tab;
+  out[6] = d.bnd.j0; out[7] = d.ok;
+}
 """
 
 
@@ -51,6 +58,7 @@ def grid(tmp_path_factory):
         getattr(L, n).restype = C.c_uint32
         getattr(L, n).argtypes = [C.c_uint32] * {"g_mstart": 4, "g_bnd_next": 6, "g_merge_j0": 3, "g_merge_shift": 3, "g_merge_points": 3}[n]
     L.g_dyn.argtypes = [C.c_uint32] * 7 + [C.POINTER(C.c_uint32)]
+    L.g_col_duty.argtypes = [C.c_uint32] * 8 + [C.c_int, C.POINTER(C.c_uint32)]
     return L
 
 
@@ -131,6 +139,55 @@ def test_merged_grid_identity(grid):
         q = k + shift
         b = np.dot(rp, x[HCAP - (T - 1) + j0_ref - D + q * D:][:T + delta])
         assert abs(a - b) < 1e-9
+
+
+def test_column_duty_expands_every_output_where_the_epilogue_reads_it(grid):
+    """xl_col_duty (the inverse launches' phase expansion): output k of a member column is the shared point q = k + shift, which lies
+    in segment q // V, group (q % V) // 16 of it -- that duty expands k, at the place the epilogue reads it from: m0 <= k < m0 + count
+    and k - m0 == (q % V) % 16 - ibeg (the point's place in its group, less the group's first point where that is nobody's output).
+    Its table entry is the one below m0, its K and j0 are the column's own (xl_grid_dyn), and a vacant column expands nothing.  (A
+    segment's last group may run past V, into phases the next segment's first group expands too: the epilogue's `point < V` test cuts
+    it, so an output may be expanded twice, never not at all.)"""
+    rng = np.random.default_rng(23)
+    out = (C.c_uint32 * 8)()
+    dyn = (C.c_uint32 * 4)()
+    for it in range(150):
+        D = int(rng.integers(2, 120))
+        G = int(rng.choice([1, 2, 3, 8]))
+        S = int(rng.integers(D, 2500))
+        V = int(rng.choice([int(rng.integers(1, 64)), int(rng.integers(64, 257)), 116, 126, 128]))
+        j0_ref = int(rng.integers(0, D))
+        delta = int(rng.integers(0, D)) if it % 5 else (D - j0_ref) % D  # (every fifth: the member whose j0 wraps to 0)
+        j0 = grid.g_merge_j0(j0_ref, delta, D)
+        shift = grid.g_merge_shift(j0_ref, delta, D)
+        grid.g_dyn(D, 1, (D - j0) % D, 0, 0, S, G, dyn)  # the member's own grid: consumed = -j0 mod D
+        K = dyn[1]
+        assert dyn[3] == j0
+        nseg = -(-grid.g_merge_points(D, S, G) // V)
+        groups = -(-V // 16)
+        for s in range(nseg):
+            for g in range(groups + 1):  # (one group beyond V: the lanes that have none)
+                grid.g_col_duty(j0_ref, delta, D, S, G, V, s, g, 0, out)
+                Kd, sh, ibeg, m0, count, tab, j0d, ok = (int(v) for v in out)
+                assert (Kd, sh, j0d) == (K, shift, j0)
+                assert ibeg == (1 if (s == 0 and g == 0 and shift == 1) else 0)
+                assert ok == (1 if count else 0) and count <= 16 - ibeg
+                if g >= groups:
+                    assert count == 0
+                if count:
+                    assert tab == m0 // 16 and m0 + count <= K
+                    assert m0 == s * V + 16 * g + ibeg - shift
+                else:
+                    assert tab == 0
+                grid.g_col_duty(j0_ref, delta, D, S, G, V, s, g, 1, out)
+                assert out[4] == 0 and out[7] == 0 and out[5] == 0  # vacant: count 0 everywhere
+        for k in range(K):
+            q = k + shift
+            s, g = q // V, (q % V) // 16
+            grid.g_col_duty(j0_ref, delta, D, S, G, V, s, g, 0, out)
+            ibeg, m0, count = int(out[2]), int(out[3]), int(out[4])
+            assert m0 <= k < m0 + count, (D, S, G, V, j0_ref, delta, k)
+            assert k - m0 == (q % V) % 16 - ibeg
 
 
 # ------------------------------------------------------------------------------------------------------------------
