@@ -3,10 +3,11 @@
 //
 // State across feeds: P, the number of samples consumed (row r starts at r * sr; its transform k covers r * sr + k W .. + W); the raw
 // samples of the transform that straddles two feeds (at most W - 1, in d_carry, stream-ordered device copies); the per-row maxima in
-// a ring of `cap` row slots (d_max, float bits, zero between rows).  A span of a feed is cut into: the straddling transform (completed
-// from the carry), the transforms that lie wholly inside the span (one launch over the span in place), and the start of the next
-// straddling one (into the carry).  Skipped samples are never transformed.  Every row whose F-th transform is in gets one finishing
-// launch (dB, shift, pixel into d_db / d_px of its slot) and a copy into the pinned host ring; take_rows waits for the latest feed.
+// a ring of `cap` row slots (d_max, float bits, zero between rows).  A span of a feed is cut by xl_spectrum_cut.h's xl_spec_cut, as the
+// bank cuts every stream of its feeds, into: the straddling transform (completed from the carry), the transforms that lie wholly
+// inside the span (one launch over the span in place), and the start of the next straddling one (into the carry).  Skipped samples
+// are never transformed.  Every row whose F-th transform is in gets one finishing launch (dB, shift, pixel into d_db / d_px of its
+// slot) and a copy into the pinned host ring; take_rows waits for the latest feed.
 // Any split gives bit-identical rows: every transform sees the same samples and the same code, and max is exact.
 #include "../../include/xlating_spectrum.h"
 
@@ -24,18 +25,13 @@
 #include "xl_device.h"
 #include "xl_spectrum.h"
 #include "xl_spectrum_core.h"
+#include "xl_spectrum_cut.h"
 
-#define XL_SPEC_SPAN_MAX ((int64_t)1 << 30)  // samples per span: keeps every in-launch offset within 32 bits
-
-struct xlating_spectrum {
-  uint32_t sr = 0, W = 0, F = 0, N = 0, ssz = 0;
-  int fmt = 0;
-  bool blue = false;
-  int device = 0;
+struct xlating_spectrum : XlSpecSetup {
+  uint32_t sr = 0, F = 0;
   hipStream_t stream = nullptr;  // host feeds
   hipEvent_t last = nullptr;     // behind the latest feed's work
   bool fed = false, broken = false;
-  float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bspec = nullptr;
   uint8_t *d_carry = nullptr;
   uint32_t cap = 0;
   uint32_t *d_max = nullptr;
@@ -69,7 +65,7 @@ static void xl_fft_double(std::vector<std::complex<double>> &a) {  // in-place r
       }
 }
 
-int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_chirp, float2 **d_bspec) {
+static int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_chirp, float2 **d_bspec) {
   std::vector<float2> tw(N);
   for (uint32_t m = 0; m < N; ++m) {
     const double ang = -2.0 * M_PI * (double)m / (double)N;
@@ -96,6 +92,40 @@ int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_
   XL_SPEC_TRY(hipMalloc(d_bspec, sizeof(float2) * N));
   XL_SPEC_TRY(hipMemcpy(*d_bspec, bs.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
   return 0;
+}
+
+int xl_spec_setup_init(XlSpecSetup *u, int width, int format, const char *who) {
+  if (width <= 0 || width > XLATING_SPECTRUM_MAX_WIDTH ||
+      (format != XLATING_SPECTRUM_CU8 && format != XLATING_SPECTRUM_CS16 && format != XLATING_SPECTRUM_CF32))
+    return -EINVAL;
+  u->device = xl_hip_select_device(-1);
+  if (u->device < 0) {
+    XL_LOG_ERR("%s: no usable HIP device (%s); there is no CPU path", who, xlating_hip_device_info());
+    return -ENODEV;
+  }
+  u->W = (uint32_t)width, u->fmt = format, u->ssz = xl_bytes_per_sample(format);
+  u->blue = (u->W & (u->W - 1u)) != 0;
+  u->N = u->W;
+  if (u->blue) {
+    u->N = 1;
+    while (u->N < 2u * u->W - 1u) u->N <<= 1;
+  }
+  const hipError_t e = hipSetDevice(u->device);
+  if (e != hipSuccess) {
+    xl_last_hip_error = e;
+    XL_LOG_ERR("%s: %s", who, hipGetErrorString(e));
+    return xl_errno_of_last_hip_error();
+  }
+  const int rc = xl_spec_tables(u->W, u->N, u->blue, &u->d_tw, &u->d_chirp, &u->d_bspec);
+  if (rc != 0) xl_spec_setup_free(u);
+  return rc;
+}
+
+void xl_spec_setup_free(XlSpecSetup *u) {
+  if (u->d_tw) (void)hipFree(u->d_tw);
+  if (u->d_chirp) (void)hipFree(u->d_chirp);
+  if (u->d_bspec) (void)hipFree(u->d_bspec);
+  u->d_tw = u->d_chirp = u->d_bspec = nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------- row ring
@@ -164,35 +194,24 @@ static int xl_spec_launch_t(xlating_spectrum *s, const void *in, int64_t base, i
   return 0;
 }
 
-// n (<= XL_SPEC_SPAN_MAX) samples at device address `in`: stream samples P .. P + n - 1
+// n (0 < n <= XL_SPEC_SPAN_MAX) samples at device address `in`: stream samples P .. P + n - 1
 static int xl_spec_span(xlating_spectrum *s, const uint8_t *in, int64_t n, hipStream_t st) {
-  const int64_t sr = s->sr, W = s->W, F = s->F, FW = F * W, ssz = s->ssz;
-  const int64_t P0 = s->P, P1 = P0 + n;
-  int rc = xl_spec_reserve(s, P1, st);
+  const int64_t W = s->W, ssz = s->ssz;
+  int rc = xl_spec_reserve(s, s->P + n, st);
   if (rc != 0) return rc;
-  const int64_t row0 = P0 / sr, pos0 = P0 % sr;
-  // the transform that straddles P0: its first samples are in the carry
-  if (pos0 < FW && pos0 % W != 0) {
-    const int64_t k = pos0 / W, t0 = row0 * sr + k * W, t1 = t0 + W;
-    const int64_t m = std::min(t1, P1) - P0;
-    XL_SPEC_TRY(hipMemcpyAsync(s->d_carry + (P0 - t0) * ssz, in, (size_t)(m * ssz), hipMemcpyDeviceToDevice, st));
-    if (P0 + m == t1 && (rc = xl_spec_launch_t(s, s->d_carry, t0, row0 * F + k, 1, st)) != 0) return rc;
-  }
+  const XlSpecCut c = xl_spec_cut(s->sr, W, s->P, n);
+  // the transform that straddles P: its first samples are in the carry
+  if (c.carry_app > 0)
+    XL_SPEC_TRY(hipMemcpyAsync(s->d_carry + c.carry_have * ssz, in, (size_t)(c.carry_app * ssz), hipMemcpyDeviceToDevice, st));
+  if (c.carry_done && (rc = xl_spec_launch_t(s, s->d_carry, c.carry_t0, c.carry_g, 1, st)) != 0) return rc;
   // the transforms wholly inside the span, in place
-  const int64_t kc = (pos0 + W - 1) / W;
-  const int64_t g_first = kc >= F ? (row0 + 1) * F : row0 * F + kc;
-  const int64_t row1 = P1 / sr, pos1 = P1 % sr;
-  const int64_t g_end = row1 * F + std::min(F, pos1 / W);
-  if (g_end > g_first && (rc = xl_spec_launch_t(s, in, P0, g_first, g_end - g_first, st)) != 0) return rc;
-  // the transform that straddles P1 and starts inside the span: its start into the carry
-  if (pos1 < FW && pos1 % W != 0) {
-    const int64_t t0 = row1 * sr + (pos1 / W) * W;
-    if (t0 >= P0)
-      XL_SPEC_TRY(hipMemcpyAsync(s->d_carry, in + (t0 - P0) * ssz, (size_t)((P1 - t0) * ssz), hipMemcpyDeviceToDevice, st));
-  }
-  s->P = P1;
+  if (c.T > 0 && (rc = xl_spec_launch_t(s, in, s->P, c.g_first, c.T, st)) != 0) return rc;
+  // the transform that straddles P + n and starts inside the span: its start into the carry
+  if (c.save_n > 0)
+    XL_SPEC_TRY(hipMemcpyAsync(s->d_carry, in + c.save_off * ssz, (size_t)(c.save_n * ssz), hipMemcpyDeviceToDevice, st));
+  s->P += n;
   // rows whose F-th transform is in: finish, and copy to the host ring
-  const int64_t done = P1 >= FW ? (P1 - FW) / sr + 1 : 0;
+  const int64_t done = c.rows_done;
   for (int64_t r = s->rows_finished; r < done;) {
     const int64_t slot = r % s->cap;
     const int64_t nr = std::min<int64_t>({done - r, (int64_t)s->cap - slot, 65535});
@@ -225,33 +244,25 @@ static int xl_spec_end(xlating_spectrum *s, hipStream_t st, int rc) {
 
 // ---------------------------------------------------------------------------------------------------------- C API
 extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int format, xlating_spectrum **out) {
-  if (out == nullptr || width <= 0 || width > XLATING_SPECTRUM_MAX_WIDTH || sampling_rate == 0 || (uint32_t)width > sampling_rate ||
-      (format != XLATING_SPECTRUM_CU8 && format != XLATING_SPECTRUM_CS16 && format != XLATING_SPECTRUM_CF32))
-    return -EINVAL;
+  if (out == nullptr || sampling_rate == 0 || (int64_t)width > (int64_t)sampling_rate) return -EINVAL;
+  XlSpecSetup u;
+  int rc = xl_spec_setup_init(&u, width, format, "xlating_spectrum_create");
+  if (rc == -EINVAL) return rc;  // (as the refusals above: *out is left alone)
   *out = nullptr;
-  const int dev = xl_hip_select_device(-1);
-  if (dev < 0) {
-    XL_LOG_ERR("xlating_spectrum_create: no usable HIP device (%s); there is no CPU path", xlating_hip_device_info());
-    return -ENODEV;
-  }
+  if (rc != 0) return rc;
   xlating_spectrum *s = new (std::nothrow) xlating_spectrum();
-  if (s == nullptr) return -ENOMEM;
-  s->sr = sampling_rate, s->W = (uint32_t)width, s->F = sampling_rate / (uint32_t)width, s->fmt = format, s->device = dev;
-  s->ssz = xl_bytes_per_sample(format);  // (bytes per complex sample)
-  s->blue = (s->W & (s->W - 1u)) != 0;
-  s->N = 1;
-  if (s->blue)
-    while (s->N < 2u * s->W - 1u) s->N <<= 1;
-  else
-    s->N = s->W;
+  if (s == nullptr) {
+    xl_spec_setup_free(&u);
+    return -ENOMEM;
+  }
+  static_cast<XlSpecSetup &>(*s) = u;
+  s->sr = sampling_rate, s->F = sampling_rate / s->W;
   s->chunk = ((size_t)16 << 20) / s->ssz;
   if (const char *e = xl_exp_getenv("XL_EXP_SPEC_CHUNK")) {  // test knob: host staging size in samples
     const long v = strtol(e, nullptr, 10);
     if (v > 0) s->chunk = (size_t)v;
   }
-  int rc = 0;
-  hipError_t e = hipSetDevice(dev);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->last, hipEventDisableTiming);
   for (int i = 0; i < 2 && e == hipSuccess; ++i) {
     e = hipEventCreateWithFlags(&s->stage_ev[i], hipEventDisableTiming);
@@ -264,7 +275,6 @@ extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int fo
     XL_LOG_ERR("xlating_spectrum_create: %s", hipGetErrorString(e));
     rc = xl_errno_of_last_hip_error();
   }
-  if (rc == 0) rc = xl_spec_tables(s->W, s->N, s->blue, &s->d_tw, &s->d_chirp, &s->d_bspec);
   // room for the rows one staging buffer can complete, and two more
   if (rc == 0) rc = xl_spec_rows_alloc(s, (uint32_t)std::min<size_t>(s->chunk / s->sr + 3, 1u << 16));
   if (rc != 0) {
@@ -322,7 +332,7 @@ extern "C" int xlating_spectrum_feed_device(xlating_spectrum *s, const void *dev
   if (rc != 0) return rc;
   const uint8_t *src = static_cast<const uint8_t *>(dev_samples);
   for (size_t i = 0; i < n && rc == 0;) {
-    const size_t m = std::min<size_t>((size_t)XL_SPEC_SPAN_MAX, n - i);
+    const size_t m = std::min(XL_SPEC_SPAN_MAX, n - i);
     rc = xl_spec_span(s, src + i * s->ssz, (int64_t)m, st);
     i += m;
   }
@@ -359,9 +369,7 @@ extern "C" void xlating_spectrum_destroy(xlating_spectrum *s) {
     if (s->stage_ev[i]) (void)hipEventDestroy(s->stage_ev[i]);
   }
   if (s->d_carry) (void)hipFree(s->d_carry);
-  if (s->d_tw) (void)hipFree(s->d_tw);
-  if (s->d_chirp) (void)hipFree(s->d_chirp);
-  if (s->d_bspec) (void)hipFree(s->d_bspec);
+  xl_spec_setup_free(s);
   if (s->last) (void)hipEventDestroy(s->last);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;

@@ -1,4 +1,5 @@
-// xl_spectrum.h -- the spectrogram's launches (xl_spectrum.hip) as the streaming core (xl_spectrum.cpp) calls them.
+// xl_spectrum.h -- the spectrogram's launches (xl_spectrum.hip) as the streaming core (xl_spectrum.cpp) calls them, and what the single
+// object and the bank (xl_spectrum_bank.cpp) both set up for a width and a format.
 // Internal to libxlating_spectrum.so; the public interface is include/xlating_spectrum.h.
 #ifndef XL_SPECTRUM_INTERNAL_H_
 #define XL_SPECTRUM_INTERNAL_H_
@@ -8,6 +9,9 @@
 
 #define XL_SPEC_MAX_W 8192
 #define XL_SPEC_MAX_L 16384  // Bluestein length for W = 8191: the power of two >= 2 W - 1
+// samples of one stream that one cut (xl_spectrum_cut.h) may take -- a span of the single object's feed, a stream's count in a feed of the
+// bank: keeps every in-launch offset within 32 bits
+#define XL_SPEC_SPAN_MAX ((size_t)1 << 30)
 
 // One launch: transforms g0 .. g0 + T - 1 of the stream (transform g = row g / F, k = g % F; its samples start at stream index
 // (g / F) * sr + (g % F) * W).  `in` holds stream samples base .. : every transform of the launch lies inside it, so that the relative
@@ -37,9 +41,22 @@ int xl_spec_launch(const XlSpecArgs &a, uint32_t N, bool bluestein, int fmt, hip
 // db[slot * W ..] and W bytes to px[slot * W ..], and zeroes the slot's maxima for the row that reuses it.
 int xl_spec_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t cap, int64_t r0, uint32_t nrows, hipStream_t st);
 
-// The tables of a width (host, double, rounded to float): N-point twiddles, and for Bluestein the chirp and the chirp filter's spectrum.
-// Device allocations the caller frees.  0 or a negative errno.
-int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_chirp, float2 **d_bspec);
+// What a width and a format determine, the same for the single object and the bank: the transform length N (W for a power of two, else
+// the Bluestein L) and the tables on `device` (host, double, rounded to float): N-point twiddles, and for Bluestein the chirp and the chirp
+// filter's spectrum.
+struct XlSpecSetup {
+  uint32_t W = 0, N = 0, ssz = 0;  // ssz: bytes per complex sample
+  int fmt = 0;
+  bool blue = false;
+  int device = 0;
+  float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bspec = nullptr;
+};
+
+// In this order: -EINVAL for a width outside 1 .. XLATING_SPECTRUM_MAX_WIDTH or an unknown format, before the device is touched; the
+// device, -ENODEV with a "<3>" line that names `who` (the calling function) when there is none; N; the tables (-ENOMEM, -EIO).  The
+// device is left current.  A failed init leaves nothing to free.
+int xl_spec_setup_init(XlSpecSetup *u, int width, int format, const char *who);
+void xl_spec_setup_free(XlSpecSetup *u);
 
 // (needs xl_common.h at the place of use)
 #define XL_SPEC_TRY(expr)                                                                                         \

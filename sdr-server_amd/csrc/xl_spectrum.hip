@@ -39,39 +39,7 @@ __global__ void __launch_bounds__(xl_spec_nt(N)) xl_spec_kernel(const XlSpecArgs
       slot[b] = ~0u;
     }
   }
-  __syncthreads();
-  // load
-  for (uint32_t q = tid; q < B * N; q += NT) {
-    const uint32_t b = q / N, n = q % N;
-    v2f v = (v2f){0.0f, 0.0f};
-    if (slot[b] != ~0u && n < a.W) v = xl_spec_point<FMT, BLUE>(a.in, off[b], n, a.chirp);
-    buf[q] = v;
-  }
-  __syncthreads();
-  xl_fft_lds<N, B, NT>(buf, a.tw, tid);
-  if constexpr (BLUE) {
-    for (uint32_t q = tid; q < B * N; q += NT) buf[q] = xl_spec_blue_mid(buf[q], a.bspec[q % N]);
-    __syncthreads();
-    xl_fft_lds<N, B, NT>(buf, a.tw, tid);
-  }
-  // power and row maximum
-  for (uint32_t j = tid; j < a.W; j += NT) {
-    const v2f cj = BLUE ? (v2f){a.chirp[j].x, a.chirp[j].y} : (v2f){1.0f, 0.0f};
-    uint32_t cur = ~0u, m = 0u;
-    for (uint32_t b = 0; b < B; ++b) {
-      const uint32_t sl = slot[b];
-      if (sl == ~0u) break;
-      const float pw = xl_spec_power<BLUE>(buf[b * N + j], cj, a.norm);
-      if (sl != cur) {
-        if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
-        cur = sl;
-        m = 0u;
-      }
-      const uint32_t bits = __float_as_uint(pw);
-      m = bits > m ? bits : m;
-    }
-    if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
-  }
+  xl_spec_pack<N, FMT, BLUE>(buf, off, slot, a, [&](uint32_t) { return a.in; });
 }
 
 // spectrogram.c:150-158 (10 log10f, halves swapped with half = W / 2, an odd W's last bin in place) and png_util.c:53-63 (the pixel)
@@ -80,65 +48,17 @@ __global__ void __launch_bounds__(256) xl_spec_finish_kernel(uint32_t *rowmax, f
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= W) return;
   const size_t s = (size_t)((r0 + (int64_t)blockIdx.y) % cap) * W;
-  const uint32_t src = xl_spec_shift_src(j, W);
-  const float v = __uint_as_float(rowmax[s + src]);
-  rowmax[s + src] = 0u;  // (a permutation: every bin is read and cleared by exactly one thread)
-  const float d = xl_spec_db(v);
-  db[s + j] = d;
-  px[s + j] = xl_spec_pixel(d);
-}
-
-template <uint32_t N, bool BLUE>
-int xl_spec_launch_n(const XlSpecArgs &a, int fmt, hipStream_t st) {
-  const uint32_t B = xl_spec_b(N);
-  const dim3 grid((unsigned)((a.T + B - 1u) / B)), block(xl_spec_nt(N));
-  if (fmt == XLF_CU8)
-    hipLaunchKernelGGL((xl_spec_kernel<N, XLF_CU8, BLUE>), grid, block, 0, st, a);
-  else if (fmt == XLF_CS16)
-    hipLaunchKernelGGL((xl_spec_kernel<N, XLF_CS16, BLUE>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((xl_spec_kernel<N, XLF_CF32, BLUE>), grid, block, 0, st, a);
-  return (int)hipGetLastError();
+  xl_spec_finish_bin(rowmax, db, px, W, j, s, s);
 }
 
 }  // namespace
 
 int xl_spec_launch(const XlSpecArgs &a, uint32_t N, bool bluestein, int fmt, hipStream_t st) {
   if (a.T == 0) return 0;
-  if (bluestein) {
-    switch (N) {
-      case 8: return xl_spec_launch_n<8, true>(a, fmt, st);
-      case 16: return xl_spec_launch_n<16, true>(a, fmt, st);
-      case 32: return xl_spec_launch_n<32, true>(a, fmt, st);
-      case 64: return xl_spec_launch_n<64, true>(a, fmt, st);
-      case 128: return xl_spec_launch_n<128, true>(a, fmt, st);
-      case 256: return xl_spec_launch_n<256, true>(a, fmt, st);
-      case 512: return xl_spec_launch_n<512, true>(a, fmt, st);
-      case 1024: return xl_spec_launch_n<1024, true>(a, fmt, st);
-      case 2048: return xl_spec_launch_n<2048, true>(a, fmt, st);
-      case 4096: return xl_spec_launch_n<4096, true>(a, fmt, st);
-      case 8192: return xl_spec_launch_n<8192, true>(a, fmt, st);
-      case 16384: return xl_spec_launch_n<16384, true>(a, fmt, st);
-    }
-    return (int)hipErrorInvalidValue;
-  }
-  switch (N) {
-    case 1: return xl_spec_launch_n<1, false>(a, fmt, st);
-    case 2: return xl_spec_launch_n<2, false>(a, fmt, st);
-    case 4: return xl_spec_launch_n<4, false>(a, fmt, st);
-    case 8: return xl_spec_launch_n<8, false>(a, fmt, st);
-    case 16: return xl_spec_launch_n<16, false>(a, fmt, st);
-    case 32: return xl_spec_launch_n<32, false>(a, fmt, st);
-    case 64: return xl_spec_launch_n<64, false>(a, fmt, st);
-    case 128: return xl_spec_launch_n<128, false>(a, fmt, st);
-    case 256: return xl_spec_launch_n<256, false>(a, fmt, st);
-    case 512: return xl_spec_launch_n<512, false>(a, fmt, st);
-    case 1024: return xl_spec_launch_n<1024, false>(a, fmt, st);
-    case 2048: return xl_spec_launch_n<2048, false>(a, fmt, st);
-    case 4096: return xl_spec_launch_n<4096, false>(a, fmt, st);
-    case 8192: return xl_spec_launch_n<8192, false>(a, fmt, st);
-  }
-  return (int)hipErrorInvalidValue;
+  return xl_spec_dispatch(N, bluestein, fmt, [&](auto n, auto f, auto blue) {
+    constexpr uint32_t B = xl_spec_b(n);
+    hipLaunchKernelGGL((xl_spec_kernel<n, f, blue>), dim3((unsigned)((a.T + B - 1u) / B)), dim3(xl_spec_nt(n)), 0, st, a);
+  });
 }
 
 int xl_spec_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t cap, int64_t r0, uint32_t nrows, hipStream_t st) {

@@ -30,7 +30,6 @@
 #include "xl_spectrum_bank.h"
 #include "xl_spectrum_cut.h"
 
-#define XL_BANK_COUNT_MAX ((size_t)1 << 30)  // samples per stream and feed: keeps every in-launch offset within 32 bits
 #define XL_BANK_TABLES 4
 #define XL_BANK_MAX_STREAMS 65536
 
@@ -66,15 +65,11 @@ struct XlBankTable {
 
 }  // namespace
 
-struct xlating_spectrum_bank {
-  uint32_t W = 0, N = 0, ssz = 0, slots = 0;
-  int fmt = 0;
-  bool blue = false;
-  int device = 0;
+struct xlating_spectrum_bank : XlSpecSetup {
+  uint32_t slots = 0;
   hipStream_t own = nullptr;  // growth and clearing of the per-stream state
   hipEvent_t last = nullptr;  // behind the latest feed's work
   bool fed = false, broken = false;
-  float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bspec = nullptr;
   uint32_t cap_streams = 0;
   uint8_t *d_carry = nullptr;  // [cap_streams][W] samples
   uint32_t *d_max = nullptr;   // [cap_streams * slots][W]
@@ -332,7 +327,7 @@ static int xl_bank_feed(xlating_spectrum_bank *b, size_t n, const int *ids, cons
   b->feed_no++;
   uint64_t total_t = 0;
   for (size_t i = 0; i < n; ++i) {
-    if (!xl_bank_live(b, ids[i]) || counts[i] > XL_BANK_COUNT_MAX || (counts[i] > 0 && dev_samples[i] == nullptr)) return -EINVAL;
+    if (!xl_bank_live(b, ids[i]) || counts[i] > XL_SPEC_SPAN_MAX || (counts[i] > 0 && dev_samples[i] == nullptr)) return -EINVAL;
     XlBankStream &s = b->streams[(size_t)ids[i]];
     if (s.mark == b->feed_no) return -EINVAL;  // named twice
     s.mark = b->feed_no;
@@ -361,41 +356,30 @@ static int xl_bank_feed(xlating_spectrum_bank *b, size_t n, const int *ids, cons
 
 // ---------------------------------------------------------------------------------------------------------- C API
 extern "C" int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out) {
-  if (out == nullptr || width <= 0 || width > XLATING_SPECTRUM_MAX_WIDTH ||
-      (format != XLATING_SPECTRUM_CU8 && format != XLATING_SPECTRUM_CS16 && format != XLATING_SPECTRUM_CF32))
-    return -EINVAL;
+  if (out == nullptr) return -EINVAL;
+  XlSpecSetup u;
+  int rc = xl_spec_setup_init(&u, width, format, "xlating_spectrum_bank_create");
+  if (rc == -EINVAL) return rc;  // (as the refusal above: *out is left alone)
   *out = nullptr;
-  const int dev = xl_hip_select_device(-1);
-  if (dev < 0) {
-    XL_LOG_ERR("xlating_spectrum_bank_create: no usable HIP device (%s); there is no CPU path", xlating_hip_device_info());
-    return -ENODEV;
-  }
+  if (rc != 0) return rc;
   xlating_spectrum_bank *b = new (std::nothrow) xlating_spectrum_bank();
-  if (b == nullptr) return -ENOMEM;
-  b->W = (uint32_t)width, b->fmt = format, b->device = dev, b->ssz = xl_bytes_per_sample(format);
-  b->blue = (b->W & (b->W - 1u)) != 0;
-  b->N = 1;
-  if (b->blue)
-    while (b->N < 2u * b->W - 1u) b->N <<= 1;
-  else
-    b->N = b->W;
+  if (b == nullptr) {
+    xl_spec_setup_free(&u);
+    return -ENOMEM;
+  }
+  static_cast<XlSpecSetup &>(*b) = u;
   b->slots = std::min(16u, std::max(2u, 16384u / b->W));  // 64 KiB of maxima per stream at most
   if (const char *e = xl_exp_getenv("XL_EXP_SPEC_BANK_SLOTS")) {  // test knob: row slots per stream (rounds per feed)
     const long v = strtol(e, nullptr, 10);
     if (v > 0 && v <= 1024) b->slots = (uint32_t)v;
   }
-  hipError_t e = hipSetDevice(dev);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->last, hipEventDisableTiming);
   for (int i = 0; i < XL_BANK_TABLES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->tab[i].ev, hipEventDisableTiming);
-  int rc = 0;
   if (e != hipSuccess) {
     xl_last_hip_error = e;
     XL_LOG_ERR("xlating_spectrum_bank_create: %s", hipGetErrorString(e));
     rc = xl_errno_of_last_hip_error();
-  }
-  if (rc == 0) rc = xl_spec_tables(b->W, b->N, b->blue, &b->d_tw, &b->d_chirp, &b->d_bspec);
-  if (rc != 0) {
     xlating_spectrum_bank_destroy(b);
     return rc;
   }
@@ -522,9 +506,7 @@ extern "C" void xlating_spectrum_bank_destroy(xlating_spectrum_bank *b) {
   if (b->d_px) (void)hipFree(b->d_px);
   if (b->d_carry) (void)hipFree(b->d_carry);
   if (b->d_max) (void)hipFree(b->d_max);
-  if (b->d_tw) (void)hipFree(b->d_tw);
-  if (b->d_chirp) (void)hipFree(b->d_chirp);
-  if (b->d_bspec) (void)hipFree(b->d_bspec);
+  xl_spec_setup_free(b);
   if (b->last) (void)hipEventDestroy(b->last);
   if (b->own) (void)hipStreamDestroy(b->own);
   delete b;

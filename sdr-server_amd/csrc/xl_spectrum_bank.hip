@@ -2,12 +2,12 @@
 // streams in one ragged launch, the carries of all streams in one launch before and one after it, and the finishing pass over the
 // list of rows a feed completed.
 //
-// The arithmetic of a transform is xl_spectrum_dev.h's, instantiated here exactly as xl_spectrum.hip instantiates it: a bank row is
-// bit for bit the single object's row.  What differs is where a packed transform comes from: a workgroup still packs B = xl_spec_b(N)
-// transforms, but transform t of the launch belongs to the run (XlBankRun: one stream's transforms in one source buffer) whose
-// running sum tsum covers t, found by a binary search per packed transform; its source pointer, sample offset and row slot are kept
-// in LDS.  The row maximum is flushed by an unsigned atomicMax on the float's bits whenever the row slot changes along the pack (a
-// slot belongs to one stream and, within a launch, to one row: stream or row changes are slot changes).
+// What a workgroup does with its pack of transforms is xl_spectrum_dev.h's xl_spec_pack, the one body xl_spectrum.hip calls too: a
+// bank row is bit for bit the single object's row.  What differs is the prologue, where a packed transform comes from: a workgroup
+// still packs B = xl_spec_b(N) transforms, but transform t of the launch belongs to the run (XlBankRun: one stream's transforms in
+// one source buffer) whose running sum tsum covers t, found by a binary search per packed transform; its source pointer, sample
+// offset and row slot are kept in LDS.  The shared body flushes the row maximum whenever the row slot changes along the pack; here
+// a slot belongs to one stream and, within a launch, to one row: stream or row changes are slot changes.
 // SCALAR FP32 ONLY, no matrix instructions (Makefile: SPEC_FLAGS), as xl_spectrum.hip: these launches run behind and beside the
 // engine's matrix-core launches.
 #include "xl_spectrum_bank.h"
@@ -45,39 +45,7 @@ __global__ void __launch_bounds__(xl_spec_nt(N)) xl_bank_kernel(const XlBankArgs
       slot[b] = ~0u;
     }
   }
-  __syncthreads();
-  // load
-  for (uint32_t q = tid; q < B * N; q += NT) {
-    const uint32_t b = q / N, n = q % N;
-    v2f v = (v2f){0.0f, 0.0f};
-    if (slot[b] != ~0u && n < a.W) v = xl_spec_point<FMT, BLUE>(src[b], off[b], n, a.chirp);
-    buf[q] = v;
-  }
-  __syncthreads();
-  xl_fft_lds<N, B, NT>(buf, a.tw, tid);
-  if constexpr (BLUE) {
-    for (uint32_t q = tid; q < B * N; q += NT) buf[q] = xl_spec_blue_mid(buf[q], a.bspec[q % N]);
-    __syncthreads();
-    xl_fft_lds<N, B, NT>(buf, a.tw, tid);
-  }
-  // power and row maximum
-  for (uint32_t j = tid; j < a.W; j += NT) {
-    const v2f cj = BLUE ? (v2f){a.chirp[j].x, a.chirp[j].y} : (v2f){1.0f, 0.0f};
-    uint32_t cur = ~0u, m = 0u;
-    for (uint32_t b = 0; b < B; ++b) {
-      const uint32_t sl = slot[b];
-      if (sl == ~0u) break;
-      const float pw = xl_spec_power<BLUE>(buf[b * N + j], cj, a.norm);
-      if (sl != cur) {
-        if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
-        cur = sl;
-        m = 0u;
-      }
-      const uint32_t bits = __float_as_uint(pw);
-      m = bits > m ? bits : m;
-    }
-    if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
-  }
+  xl_spec_pack<N, FMT, BLUE>(buf, off, slot, a, [&](uint32_t b) { return src[b]; });
 }
 
 // one workgroup per stream of the feed; T: an unsigned type of one complex sample's size
@@ -100,66 +68,17 @@ __global__ void __launch_bounds__(256) xl_bank_finish_kernel(const uint32_t *__r
                                                              const uint32_t W) {
   const uint32_t j = blockIdx.y * 256u + threadIdx.x;
   if (j >= W) return;
-  const size_t s = (size_t)list[blockIdx.x] * W, o = (size_t)blockIdx.x * W;
-  const uint32_t from = xl_spec_shift_src(j, W);
-  const float v = __uint_as_float(rowmax[s + from]);
-  rowmax[s + from] = 0u;  // (a permutation: every bin is read and cleared by exactly one thread)
-  const float d = xl_spec_db(v);
-  db[o + j] = d;
-  px[o + j] = xl_spec_pixel(d);
-}
-
-template <uint32_t N, bool BLUE>
-int xl_bank_launch_n(const XlBankArgs &a, int fmt, hipStream_t st) {
-  const uint32_t B = xl_spec_b(N);
-  const dim3 grid((unsigned)(((uint64_t)a.T + B - 1u) / B)), block(xl_spec_nt(N));
-  if (fmt == XLF_CU8)
-    hipLaunchKernelGGL((xl_bank_kernel<N, XLF_CU8, BLUE>), grid, block, 0, st, a);
-  else if (fmt == XLF_CS16)
-    hipLaunchKernelGGL((xl_bank_kernel<N, XLF_CS16, BLUE>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((xl_bank_kernel<N, XLF_CF32, BLUE>), grid, block, 0, st, a);
-  return (int)hipGetLastError();
+  xl_spec_finish_bin(rowmax, db, px, W, j, (size_t)list[blockIdx.x] * W, (size_t)blockIdx.x * W);
 }
 
 }  // namespace
 
 int xl_bank_launch(const XlBankArgs &a, uint32_t N, bool bluestein, int fmt, hipStream_t st) {
   if (a.T == 0 || a.nruns == 0) return 0;
-  if (bluestein) {
-    switch (N) {
-      case 8: return xl_bank_launch_n<8, true>(a, fmt, st);
-      case 16: return xl_bank_launch_n<16, true>(a, fmt, st);
-      case 32: return xl_bank_launch_n<32, true>(a, fmt, st);
-      case 64: return xl_bank_launch_n<64, true>(a, fmt, st);
-      case 128: return xl_bank_launch_n<128, true>(a, fmt, st);
-      case 256: return xl_bank_launch_n<256, true>(a, fmt, st);
-      case 512: return xl_bank_launch_n<512, true>(a, fmt, st);
-      case 1024: return xl_bank_launch_n<1024, true>(a, fmt, st);
-      case 2048: return xl_bank_launch_n<2048, true>(a, fmt, st);
-      case 4096: return xl_bank_launch_n<4096, true>(a, fmt, st);
-      case 8192: return xl_bank_launch_n<8192, true>(a, fmt, st);
-      case 16384: return xl_bank_launch_n<16384, true>(a, fmt, st);
-    }
-    return (int)hipErrorInvalidValue;
-  }
-  switch (N) {
-    case 1: return xl_bank_launch_n<1, false>(a, fmt, st);
-    case 2: return xl_bank_launch_n<2, false>(a, fmt, st);
-    case 4: return xl_bank_launch_n<4, false>(a, fmt, st);
-    case 8: return xl_bank_launch_n<8, false>(a, fmt, st);
-    case 16: return xl_bank_launch_n<16, false>(a, fmt, st);
-    case 32: return xl_bank_launch_n<32, false>(a, fmt, st);
-    case 64: return xl_bank_launch_n<64, false>(a, fmt, st);
-    case 128: return xl_bank_launch_n<128, false>(a, fmt, st);
-    case 256: return xl_bank_launch_n<256, false>(a, fmt, st);
-    case 512: return xl_bank_launch_n<512, false>(a, fmt, st);
-    case 1024: return xl_bank_launch_n<1024, false>(a, fmt, st);
-    case 2048: return xl_bank_launch_n<2048, false>(a, fmt, st);
-    case 4096: return xl_bank_launch_n<4096, false>(a, fmt, st);
-    case 8192: return xl_bank_launch_n<8192, false>(a, fmt, st);
-  }
-  return (int)hipErrorInvalidValue;
+  return xl_spec_dispatch(N, bluestein, fmt, [&](auto n, auto f, auto blue) {
+    constexpr uint32_t B = xl_spec_b(n);
+    hipLaunchKernelGGL((xl_bank_kernel<n, f, blue>), dim3((unsigned)(((uint64_t)a.T + B - 1u) / B)), dim3(xl_spec_nt(n)), 0, st, a);
+  });
 }
 
 int xl_bank_carry(const XlBankCarry *ops, uint32_t n, void *carry, uint32_t W, uint32_t ssz, bool save, hipStream_t st) {

@@ -1,6 +1,6 @@
 /* xl_spectrum_cut.h -- how a feed cuts a stream's next n samples into transforms: pure integer state, plain C, no HIP (compiled by
- * gcc in tests/test_spectrum_bank_cpu.py, with the sanitizers under tools/sanitize.sh).  The spectrum bank (xl_spectrum_bank.cpp) cuts
- * every stream of a feed with it.
+ * gcc in tests/test_spectrum_bank_cpu.py, with the sanitizers under tools/sanitize.sh).  The single object (xl_spectrum.cpp) cuts every
+ * span of a feed with it, the spectrum bank (xl_spectrum_bank.cpp) every stream of a feed.
  *
  * A stream of sampling_rate sr and width W has rows of F = sr / W transforms: transform g = row g / F, k = g % F covers stream samples
  * (g / F) * sr + (g % F) * W .. + W; the sr % W samples after a row's F-th transform are skipped.  Samples P0 .. P0 + n - 1 hold:

@@ -1,10 +1,14 @@
-// xl_spectrum_dev.h -- the arithmetic of one spectrogram transform, shared by the single stream's kernel (xl_spectrum.hip) and the
-// bank's ragged kernel (xl_spectrum_bank.hip): packing constants, the Stockham transform in LDS, the load (sample converter and
-// Bluestein pre-multiplication), the Bluestein middle step, the power expression and the finishing dB / pixel.  Both files instantiate
-// these and nothing else for a transform's values, with the same compiler flags (Makefile: SPEC_FLAGS, -ffp-contract=off): a row of the
-// bank is bit for bit the row of the single object.  See xl_spectrum.hip's header for the method.
+// xl_spectrum_dev.h -- everything a workgroup of spectrogram transforms does once it knows where its transforms come from, shared by
+// the single stream's kernel (xl_spectrum.hip) and the bank's ragged kernel (xl_spectrum_bank.hip): packing constants, the Stockham
+// transform in LDS, xl_spec_pack (load with sample converter and Bluestein pre-multiplication, transform, Bluestein middle step and
+// second transform, power, row maximum and its flush), xl_spec_finish_bin (dB, half swap, pixel), and the host-side list of the
+// transform lengths that have kernels (xl_spec_dispatch).  A kernel of either file is its LDS, its own prologue (which samples, which
+// row slot) and one call; both files are compiled with the same flags (Makefile: SPEC_FLAGS, -ffp-contract=off): a row of the bank is bit
+// for bit the row of the single object.  See xl_spectrum.hip's header for the method.
 #ifndef XL_SPECTRUM_DEV_H_
 #define XL_SPECTRUM_DEV_H_
+
+#include <type_traits>
 
 #include "xl_dev_inline.h"
 
@@ -103,6 +107,49 @@ XL_DEV float xl_spec_power(v2f X, const v2f cj, const float norm) {
   return re * re + im * im + 1e-20f;
 }
 
+// A workgroup's pack of B = xl_spec_b(N) transforms, after the kernel's prologue has written for each: off[b], its first sample as an
+// element index into src(b), and slot[b], the row slot its maxima go to (~0u from the first b past the launch's transforms).  Load,
+// transform, power; then per bin one thread walks the pack in order with a running maximum, flushed by an unsigned atomicMax on the
+// float's bits whenever the slot changes and at the end.  A slot change is a row or stream change: along a pack the transforms of one
+// row of one stream are consecutive.  a: XlSpecArgs or XlBankArgs (W, rowmax, tw, chirp, bspec, norm).
+template <uint32_t N, int FMT, bool BLUE, class Args, class Src>
+XL_DEV void xl_spec_pack(v2f *buf, const uint32_t *off, const uint32_t *slot, const Args &a, const Src src) {
+  constexpr uint32_t B = xl_spec_b(N);
+  constexpr uint32_t NT = xl_spec_nt(N);
+  const uint32_t tid = threadIdx.x;
+  __syncthreads();  // (the prologue's off[] / slot[])
+  for (uint32_t q = tid; q < B * N; q += NT) {
+    const uint32_t b = q / N, n = q % N;
+    v2f v = (v2f){0.0f, 0.0f};
+    if (slot[b] != ~0u && n < a.W) v = xl_spec_point<FMT, BLUE>(src(b), off[b], n, a.chirp);
+    buf[q] = v;
+  }
+  __syncthreads();
+  xl_fft_lds<N, B, NT>(buf, a.tw, tid);
+  if constexpr (BLUE) {
+    for (uint32_t q = tid; q < B * N; q += NT) buf[q] = xl_spec_blue_mid(buf[q], a.bspec[q % N]);
+    __syncthreads();
+    xl_fft_lds<N, B, NT>(buf, a.tw, tid);
+  }
+  for (uint32_t j = tid; j < a.W; j += NT) {
+    const v2f cj = BLUE ? (v2f){a.chirp[j].x, a.chirp[j].y} : (v2f){1.0f, 0.0f};
+    uint32_t cur = ~0u, m = 0u;
+    for (uint32_t b = 0; b < B; ++b) {
+      const uint32_t sl = slot[b];
+      if (sl == ~0u) break;
+      const float pw = xl_spec_power<BLUE>(buf[b * N + j], cj, a.norm);
+      if (sl != cur) {
+        if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
+        cur = sl;
+        m = 0u;
+      }
+      const uint32_t bits = __float_as_uint(pw);
+      m = bits > m ? bits : m;
+    }
+    if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
+  }
+}
+
 // spectrogram.c:150-158: the bin that lands in column j after the halves of half = W / 2 are swapped (an odd W's last bin in place)
 XL_DEV uint32_t xl_spec_shift_src(const uint32_t j, const uint32_t W) {
   const uint32_t half = W / 2u;
@@ -115,6 +162,72 @@ XL_DEV uint8_t xl_spec_pixel(const float d) {
   const float f = d + 255.0f;
   const int pixel = f >= 255.0f ? 255 : (f > 0.0f ? (int)f : 0);
   return (uint8_t)pixel;
+}
+
+// Column j (< W) of the finished row: the maximum of the bin that the half swap brings there, from the row slot at rowmax[s ..], as dB
+// to db[o + j] and as a pixel to px[o + j]; the maximum is cleared for the row that reuses the slot (the swap is a permutation: every bin
+// is read and cleared by exactly one thread)
+XL_DEV void xl_spec_finish_bin(uint32_t *rowmax, float *db, uint8_t *px, const uint32_t W, const uint32_t j, const size_t s,
+                               const size_t o) {
+  const uint32_t from = xl_spec_shift_src(j, W);
+  const float v = __uint_as_float(rowmax[s + from]);
+  rowmax[s + from] = 0u;
+  const float d = xl_spec_db(v);
+  db[o + j] = d;
+  px[o + j] = xl_spec_pixel(d);
+}
+
+// The transform lengths that have kernels: powers of two 1 .. 8192 as they are, 8 .. 16384 as Bluestein lengths; the three sample formats.
+// launch(n, fmt, blue) gets them as std::integral_constants and enqueues its kernel<n, fmt, blue>.  0 or a hipError_t.
+template <uint32_t N, bool BLUE, class Launch>
+int xl_spec_dispatch_fmt(const int fmt, Launch &launch) {
+  const std::integral_constant<uint32_t, N> n;
+  const std::integral_constant<bool, BLUE> blue;
+  if (fmt == XLF_CU8)
+    launch(n, std::integral_constant<int, XLF_CU8>(), blue);
+  else if (fmt == XLF_CS16)
+    launch(n, std::integral_constant<int, XLF_CS16>(), blue);
+  else
+    launch(n, std::integral_constant<int, XLF_CF32>(), blue);
+  return (int)hipGetLastError();
+}
+
+template <class Launch>
+int xl_spec_dispatch(const uint32_t N, const bool bluestein, const int fmt, Launch launch) {
+  if (bluestein) {
+    switch (N) {
+      case 8: return xl_spec_dispatch_fmt<8, true>(fmt, launch);
+      case 16: return xl_spec_dispatch_fmt<16, true>(fmt, launch);
+      case 32: return xl_spec_dispatch_fmt<32, true>(fmt, launch);
+      case 64: return xl_spec_dispatch_fmt<64, true>(fmt, launch);
+      case 128: return xl_spec_dispatch_fmt<128, true>(fmt, launch);
+      case 256: return xl_spec_dispatch_fmt<256, true>(fmt, launch);
+      case 512: return xl_spec_dispatch_fmt<512, true>(fmt, launch);
+      case 1024: return xl_spec_dispatch_fmt<1024, true>(fmt, launch);
+      case 2048: return xl_spec_dispatch_fmt<2048, true>(fmt, launch);
+      case 4096: return xl_spec_dispatch_fmt<4096, true>(fmt, launch);
+      case 8192: return xl_spec_dispatch_fmt<8192, true>(fmt, launch);
+      case 16384: return xl_spec_dispatch_fmt<16384, true>(fmt, launch);
+    }
+    return (int)hipErrorInvalidValue;
+  }
+  switch (N) {
+    case 1: return xl_spec_dispatch_fmt<1, false>(fmt, launch);
+    case 2: return xl_spec_dispatch_fmt<2, false>(fmt, launch);
+    case 4: return xl_spec_dispatch_fmt<4, false>(fmt, launch);
+    case 8: return xl_spec_dispatch_fmt<8, false>(fmt, launch);
+    case 16: return xl_spec_dispatch_fmt<16, false>(fmt, launch);
+    case 32: return xl_spec_dispatch_fmt<32, false>(fmt, launch);
+    case 64: return xl_spec_dispatch_fmt<64, false>(fmt, launch);
+    case 128: return xl_spec_dispatch_fmt<128, false>(fmt, launch);
+    case 256: return xl_spec_dispatch_fmt<256, false>(fmt, launch);
+    case 512: return xl_spec_dispatch_fmt<512, false>(fmt, launch);
+    case 1024: return xl_spec_dispatch_fmt<1024, false>(fmt, launch);
+    case 2048: return xl_spec_dispatch_fmt<2048, false>(fmt, launch);
+    case 4096: return xl_spec_dispatch_fmt<4096, false>(fmt, launch);
+    case 8192: return xl_spec_dispatch_fmt<8192, false>(fmt, launch);
+  }
+  return (int)hipErrorInvalidValue;
 }
 
 }  // namespace

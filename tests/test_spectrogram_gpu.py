@@ -12,6 +12,7 @@ import sdr_server_amd as xl
 import siggen
 import spectrogram_ref as R
 from conftest import GOLDEN, ROOT
+from spectrogram_ref import signal
 
 pytestmark = pytest.mark.gpu
 
@@ -59,52 +60,14 @@ def test_cli_golden(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------ parity
-def signal(fmt, n, W, seed):
-    """a few seeded tones (one on a bin, one between bins) plus noise, scaled into the format's range; interleaved scalars"""
-    rng = np.random.default_rng(seed)
-    t = np.arange(n)
-    f1 = (rng.integers(0, max(W, 1)) / max(W, 1)) - 0.5
-    f2 = rng.uniform(-0.5, 0.5)
-    z = 0.5 * np.exp(2j * np.pi * f1 * t) + 0.2 * np.exp(2j * np.pi * f2 * t + 1.0)
-    z = z + 0.05 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
-    v = np.stack([z.real, z.imag], axis=1).reshape(-1)
-    if fmt == "cu8":
-        return np.clip(np.round(127.5 + 127 * v / 0.8), 0, 255).astype(np.uint8)
-    if fmt == "cs16":
-        return np.clip(np.round(32767 * v / 0.8), -32768, 32767).astype(np.int16)
-    return v.astype(np.float32)
-
-
-def shifted(a):
-    """the bin permutation of spectrogram.c:150-158 applied to any per-bin array"""
-    W = a.shape[1]
-    half = W // 2
-    out = a.copy()
-    out[:, :half] = a[:, half:2 * half]
-    out[:, half:2 * half] = a[:, :half]
-    return out
-
-
 _PIXELS = {"total": 0, "equal": 0}
 
 
 def check_parity(db, px, raw, fmt, sr, W):
-    want_db, want_px, amp = R.spectrogram(raw, fmt, sr, W)
-    assert db.shape == want_db.shape and px.shape == want_px.shape, (db.shape, want_db.shape)
-    # (a) amplitudes within 1e-5 of the row's peak
-    got_amp = np.sqrt(10.0 ** (db.astype(np.float64) / 10.0))
-    want_amp = shifted(amp)
-    err = np.abs(got_amp - want_amp).max(axis=1)
-    peak = want_amp.max(axis=1)
-    assert np.all(err <= 1e-5 * peak), (fmt, sr, W, (err / peak).max())
-    # (b) the pixels are what the returned dB floats give
-    assert np.array_equal(px, R.pixels(db)), (fmt, sr, W)
-    # (c) within 1 of the float64 pixels, and (aggregated in test_pixel_agreement) 99.9 % equal
-    d = np.abs(px.astype(np.int32) - want_px.astype(np.int32))
-    assert d.max() <= 1, (fmt, sr, W)
-    assert (d != 0).sum() <= max(2, px.size // 1000), (fmt, sr, W, (d != 0).sum())
-    _PIXELS["total"] += px.size
-    _PIXELS["equal"] += int((d == 0).sum())
+    """R.check_parity's criteria; its pixel counts go into the aggregate of test_pixel_agreement"""
+    total, equal = R.check_parity(db, px, raw, fmt, sr, W)
+    _PIXELS["total"] += total
+    _PIXELS["equal"] += equal
 
 
 def run_spectrum(raw, fmt, sr, W):

@@ -125,15 +125,24 @@ def test_bank_knob_goes_through_the_gate():
 
 
 def test_bank_and_single_kernels_share_the_transform_arithmetic():
-    """the bit-identity of bank rows and single-object rows rests on one definition of the transform's arithmetic"""
+    """the bit-identity of bank rows and single-object rows rests on one definition of everything a workgroup does after its kernel's
+    prologue: the pack body (load, transforms, power, row maximum and its flush) and the finishing of a bin are defined in
+    xl_spectrum_dev.h only, both kernel files call them, and neither transforms or flushes a maximum on its own"""
     dev = open(os.path.join(CSRC, "xl_spectrum_dev.h")).read()
-    for name in ("xl_fft_lds", "xl_spec_point", "xl_spec_blue_mid", "xl_spec_power", "xl_spec_db", "xl_spec_pixel", "xl_spec_shift_src"):
-        assert re.search(r"XL_DEV \w+ %s\(" % name, dev), name
-        for f in ("xl_spectrum.hip", "xl_spectrum_bank.hip"):
-            src = open(os.path.join(CSRC, f)).read()
-            assert '#include "xl_spectrum_dev.h"' in src
-            assert name in src, (f, name)
-            assert not re.search(r"XL_DEV \w+ %s\(" % name, src), (f, name)
+    for name in ("xl_fft_lds", "xl_spec_point", "xl_spec_blue_mid", "xl_spec_power", "xl_spec_db", "xl_spec_pixel", "xl_spec_shift_src",
+                 "xl_spec_pack", "xl_spec_finish_bin"):
+        assert len(re.findall(r"^XL_DEV \w+ %s\(" % name, dev, re.M)) == 1, name
+    assert "atomicMax" in dev
+    for f in ("xl_spectrum.hip", "xl_spectrum_bank.hip"):
+        src = open(os.path.join(CSRC, f)).read()
+        code = re.sub(r"//[^\n]*", "", src)  # (the headers' prose names what the shared body does)
+        assert '#include "xl_spectrum_dev.h"' in src
+        assert not re.search(r"XL_DEV \w+ xl_", src), f
+        assert len(re.findall(r"\bxl_spec_pack<N, FMT, BLUE>\(", code)) == 1, f
+        assert len(re.findall(r"\bxl_spec_finish_bin\(", code)) == 1, f
+        assert len(re.findall(r"\bxl_spec_dispatch\(", code)) == 1, f
+        for own in ("atomicMax", "xl_fft_lds", "xl_spec_point", "xl_spec_power", "xl_spec_db", "xl_spec_pixel", "case "):
+            assert own not in code, (f, own)
 
 
 # ------------------------------------------------------------------------------------------------------------ the cutting of a feed
