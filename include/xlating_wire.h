@@ -65,6 +65,27 @@ int xlating_wire_parse_response(const uint8_t *buf, size_t len, uint8_t *status,
 int xlating_wire_admit(const xlating_wire_request *req, uint32_t band_sampling_rate, uint32_t current_band_freq,
                        uint32_t lpf_cutoff_rate, xlating_wire_admission *adm, uint32_t *failure_details);
 
+/* Admission of ANY rate.  Every check of xlating_wire_admit in the same order with the same answers, except the divisibility one
+ * (tcp_server.c:100-104): a rate fo that divides the band rate fs is admitted exactly as xlating_wire_admit admits it, with
+ * L = M = 1 (no second stage); any other is served by the engine at an integer decimation D, which leaves the client at fs / D in
+ * [fo, 2 fo), and a stream of the resampler bank (xlating_resample.h) that takes it to fo by L / M.  Of D = fs / fo / 2 + 1 ..
+ * fs / fo (integer divisions), with g = gcd(fo D, fs), L = fo D / g, M = fs / g, those are eligible whose
+ * L <= XLATING_RESAMPLE_MAX_L (4096) and fo M <= UINT32_MAX; the one of the smallest L is taken, of equal L the largest D; without
+ * an eligible D the answer is INVALID_REQUEST as before.  adm->decimation = D; lpf_cutoff and lpf_transition are fo / 2 and
+ * fo / lpf_cutoff_rate as before (the engine's filter, at fs); virtual_rate = fo M = L fs / D is the rate of the second stage's
+ * upsampled grid. */
+typedef struct {
+  uint32_t L, M, virtual_rate; /* L == M == 1: no second stage */
+} xlating_wire_resample;
+int xlating_wire_admit_any_rate(const xlating_wire_request *req, uint32_t band_sampling_rate, uint32_t current_band_freq,
+                                uint32_t lpf_cutoff_rate, xlating_wire_admission *adm, xlating_wire_resample *rs,
+                                uint32_t *failure_details);
+/* The second stage's prototype, by the project's own designer (lpf.h) at the virtual rate:
+ * create_low_pass_filter((float)L, virtual_rate, fo / 2, fo / lpf_cutoff_rate).  *taps is malloc'ed (the caller frees it).
+ * 0 or -EINVAL. */
+int xlating_wire_resample_taps(const xlating_wire_request *req, const xlating_wire_resample *rs, uint32_t lpf_cutoff_rate,
+                               float **taps, size_t *len);
+
 /* dsp_worker_start for the batched path: designs the client's low-pass (lpf.h) and adds it to `engine`.
  * Returns the engine's client id (>= 0), or a negative errno (the server answers INTERNAL_ERROR). */
 int xlating_wire_add_client(struct xlating_batch_t *engine, const xlating_wire_admission *adm, uint32_t band_sampling_rate);

@@ -30,6 +30,12 @@ class WireAdmission(C.Structure):
     """include/xlating_wire.h xlating_wire_admission"""
     _fields_ = [("decimation", C.c_uint32), ("center_offset", C.c_int32), ("lpf_cutoff", C.c_uint32), ("lpf_transition", C.c_uint32)]
 
+
+class WireResample(C.Structure):
+    """include/xlating_wire.h xlating_wire_resample"""
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("virtual_rate", C.c_uint32)]
+
+
 _c_float_p = C.POINTER(C.c_float)
 _c_i16_p = C.POINTER(C.c_int16)
 
@@ -53,7 +59,8 @@ EXPORTED_SYMBOLS = (
        "xlating_sinks_submit", "xlating_sinks_failed", "xlating_sinks_flush", "xlating_sinks_detach", "xlating_sinks_stats",
        "xlating_sinks_destroy"]
     + ["xlating_wire_parse_header", "xlating_wire_parse_request", "xlating_wire_build_request", "xlating_wire_build_response",
-       "xlating_wire_build_header", "xlating_wire_parse_response", "xlating_wire_admit", "xlating_wire_add_client"]
+       "xlating_wire_build_header", "xlating_wire_parse_response", "xlating_wire_admit", "xlating_wire_add_client",
+       "xlating_wire_admit_any_rate", "xlating_wire_resample_taps"]
 )
 
 MULTI_SYMBOLS = ["xlating_multi_unique_id", "xlating_multi_create_rank", "xlating_multi_create_local", "xlating_multi_world",
@@ -226,6 +233,12 @@ def lib():
     L.xlating_wire_admit.argtypes = [C.POINTER(WireRequest), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(WireAdmission),
                                      C.POINTER(C.c_uint32)]
     L.xlating_wire_admit.restype = C.c_int
+    L.xlating_wire_admit_any_rate.argtypes = [C.POINTER(WireRequest), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(WireAdmission),
+                                              C.POINTER(WireResample), C.POINTER(C.c_uint32)]
+    L.xlating_wire_admit_any_rate.restype = C.c_int
+    L.xlating_wire_resample_taps.argtypes = [C.POINTER(WireRequest), C.POINTER(WireResample), C.c_uint32, C.POINTER(_c_float_p),
+                                             C.POINTER(C.c_size_t)]
+    L.xlating_wire_resample_taps.restype = C.c_int
     L.xlating_wire_add_client.argtypes = [C.c_void_p, C.POINTER(WireAdmission), C.c_uint32]
     L.xlating_wire_add_client.restype = C.c_int
     L.xlating_batch_timing_stride.argtypes = [C.c_void_p, C.c_uint]
@@ -708,6 +721,26 @@ def wire_add_client(engine, adm, band_sampling_rate):
     return lib().xlating_wire_add_client(engine.h, C.byref(adm), band_sampling_rate)
 
 
+def wire_admit_any_rate(req, band_sampling_rate, current_band_freq=0, lpf_cutoff_rate=5):
+    """-> (code, WireAdmission, WireResample, failure_details); L == M == 1: the rate divides the band rate, no second stage"""
+    adm, rs, why = WireAdmission(), WireResample(), C.c_uint32(0)
+    code = lib().xlating_wire_admit_any_rate(C.byref(req), band_sampling_rate, current_band_freq, lpf_cutoff_rate, C.byref(adm),
+                                             C.byref(rs), C.byref(why))
+    return code, adm, rs, why.value
+
+
+def wire_resample_taps(req, rs, lpf_cutoff_rate=5):
+    """-> (code, float32 taps | None): the second stage's prototype of an admitted request"""
+    p = _c_float_p()
+    n = C.c_size_t(0)
+    code = lib().xlating_wire_resample_taps(C.byref(req), C.byref(rs), lpf_cutoff_rate, C.byref(p), C.byref(n))
+    if code != 0:
+        return code, None
+    taps = np.ctypeslib.as_array(p, shape=(n.value,)).copy()
+    _libc.free(p)
+    return 0, taps
+
+
 # ------------------------------------------------------------------------------------------------- spectrogram (libxlating_spectrum.so)
 SPECTRUM_SYMBOLS = ["xlating_spectrum_create", "xlating_spectrum_feed_host", "xlating_spectrum_feed_device", "xlating_spectrum_take_rows",
                     "xlating_spectrum_destroy", "spectrogram_main", "spectrogram_sighandler",
@@ -918,3 +951,139 @@ def spectrogram_main(input_file, output_file, width=1024, sampling_rate=48000, d
     enc = lambda v: None if v is None else str(v).encode()  # noqa: E731
     req = SpectrogramRequest(sampling_rate, width, enc(data_format), enc(input_file), enc(output_file), enc(fftw_flags))
     return spectrum_lib().spectrogram_main(C.byref(req))
+
+
+# ------------------------------------------------------------------------------------------------- resampler bank (libxlating_resample.so)
+RESAMPLE_SYMBOLS = ["xlating_resample_bank_create", "xlating_resample_bank_add", "xlating_resample_bank_remove",
+                    "xlating_resample_bank_feed_device", "xlating_resample_bank_output_device", "xlating_resample_bank_fetch",
+                    "xlating_resample_bank_output_host", "xlating_resample_bank_produced", "xlating_resample_bank_last_feed_ops",
+                    "xlating_resample_bank_stats", "xlating_resample_bank_destroy"]
+_rlib = None
+
+
+def resample_library_path():
+    return os.path.join(os.path.dirname(library_path()), "libxlating_resample.so")
+
+
+def resample_lib():
+    """include/xlating_resample.h: the rational resampler bank behind the engine."""
+    global _rlib
+    if _rlib is not None:
+        return _rlib
+    lib()  # (torch's HIP runtime first, see lib())
+    path = resample_library_path()
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    R = C.CDLL(path)
+    R.xlating_resample_bank_create.argtypes = [C.POINTER(C.c_void_p)]
+    R.xlating_resample_bank_create.restype = C.c_int
+    R.xlating_resample_bank_add.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+    R.xlating_resample_bank_add.restype = C.c_int
+    R.xlating_resample_bank_remove.argtypes = [C.c_void_p, C.c_int]
+    R.xlating_resample_bank_remove.restype = C.c_int
+    R.xlating_resample_bank_feed_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    R.xlating_resample_bank_feed_device.restype = C.c_int
+    R.xlating_resample_bank_output_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    R.xlating_resample_bank_output_device.restype = C.c_int
+    R.xlating_resample_bank_fetch.argtypes = [C.c_void_p]
+    R.xlating_resample_bank_fetch.restype = C.c_int
+    R.xlating_resample_bank_output_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(_c_float_p), C.POINTER(C.c_size_t)]
+    R.xlating_resample_bank_output_host.restype = C.c_int
+    R.xlating_resample_bank_produced.argtypes = [C.c_void_p, C.c_int]
+    R.xlating_resample_bank_produced.restype = C.c_uint64
+    R.xlating_resample_bank_last_feed_ops.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    R.xlating_resample_bank_last_feed_ops.restype = C.c_int
+    R.xlating_resample_bank_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]
+    R.xlating_resample_bank_stats.restype = C.c_int
+    R.xlating_resample_bank_destroy.argtypes = [C.c_void_p]
+    R.xlating_resample_bank_destroy.restype = None
+    _rlib = R
+    return R
+
+
+class ResamplerBank:
+    """One `xlating_resample_bank *` (include/xlating_resample.h): many complex float32 streams, each resampled by its own L / M
+    with its own prototype, advanced together by one feed of device buffers; the latest feed's outputs are read per stream."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        code = resample_lib().xlating_resample_bank_create(C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_resample_bank_create", code)
+        self.h = h
+
+    def add(self, L, M, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        sid = resample_lib().xlating_resample_bank_add(self.h, L, M, t.ctypes.data, t.size)
+        if sid < 0:
+            raise XlatingError("xlating_resample_bank_add", sid)
+        return sid
+
+    def remove(self, stream_id):
+        code = resample_lib().xlating_resample_bank_remove(self.h, stream_id)
+        if code != 0:
+            raise XlatingError("xlating_resample_bank_remove", code)
+
+    def feed(self, ids, ptrs, counts, stream=0):
+        """stream ids[i] consumes counts[i] complex float32 samples from device address ptrs[i], in place, ordered on `stream`."""
+        a = np.ascontiguousarray(ids, dtype=np.intc)
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        assert a.size == p.size == c.size
+        code = resample_lib().xlating_resample_bank_feed_device(self.h, a.size, a.ctypes.data, p.ctypes.data, c.ctypes.data, stream)
+        if code != 0:
+            raise XlatingError("xlating_resample_bank_feed_device", code)
+
+    def feed_engine(self, engine, streams, stream=0):
+        """streams: {client id of `engine`: stream id}.  Feeds every listed client's output of the engine's latest call in one call;
+        ordering and lifetime as SpectrumBank.feed_engine."""
+        self.feed(*SpectrumBank.gather_engine(engine, streams), stream)
+
+    def fetch(self):
+        code = resample_lib().xlating_resample_bank_fetch(self.h)
+        if code != 0:
+            raise XlatingError("xlating_resample_bank_fetch", code)
+
+    def output(self, stream_id):
+        """-> complex64 [n]: the stream's outputs of the latest feed as of the latest fetch (a copy)"""
+        p, n = _c_float_p(), C.c_size_t(0)
+        code = resample_lib().xlating_resample_bank_output_host(self.h, stream_id, C.byref(p), C.byref(n))
+        if code != 0:
+            raise XlatingError("xlating_resample_bank_output_host", code)
+        if n.value == 0:
+            return np.zeros(0, np.complex64)
+        return np.ctypeslib.as_array(p, shape=(2 * n.value,)).copy().view(np.complex64)
+
+    def output_device(self, stream_id):
+        """-> (device pointer | None, complex samples) of the stream's outputs of the latest feed; valid until the next feed"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        code = resample_lib().xlating_resample_bank_output_device(self.h, stream_id, C.byref(p), C.byref(n))
+        if code != 0:
+            raise XlatingError("xlating_resample_bank_output_device", code)
+        return p.value, n.value
+
+    def produced(self, stream_id):
+        return resample_lib().xlating_resample_bank_produced(self.h, stream_id)
+
+    def last_feed_ops(self):
+        """-> (kernel launches, memory copies) the latest feed issued"""
+        a, b = C.c_uint(0), C.c_uint(0)
+        resample_lib().xlating_resample_bank_last_feed_ops(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def stats(self):
+        """-> (live streams, device tap tables, their bytes)"""
+        a, b, c = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
+        resample_lib().xlating_resample_bank_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            resample_lib().xlating_resample_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -7,6 +7,7 @@
 
 #include "../../include/lpf.h"
 #include "../../include/xlating_batch.h"
+#include "../../include/xlating_resample.h"
 #include "../../include/xlating_wire.h"
 
 static uint32_t xl_be32(const uint8_t *p) {
@@ -71,14 +72,58 @@ int xlating_wire_parse_response(const uint8_t *buf, size_t len, uint8_t *status,
   return 0;
 }
 
-int xlating_wire_admit(const xlating_wire_request *req, uint32_t band_sampling_rate, uint32_t current_band_freq,
-                       uint32_t lpf_cutoff_rate, xlating_wire_admission *adm, uint32_t *failure_details) {
-  uint32_t why = XL_WIRE_DETAILS_INVALID_REQUEST;
+static uint64_t xl_wire_gcd(uint64_t a, uint64_t g) {
+  while (g != 0) {
+    const uint64_t r = a % g;
+    a = g, g = r;
+  }
+  return a;
+}
+
+/* The integer decimation and the rational second stage of a rate that does not divide the band rate (xlating_wire.h): among
+ * D = fs / fo / 2 + 1 .. fs / fo, with L / M = fo D / fs in lowest terms, the smallest L that the resampler bank takes and whose
+ * virtual rate fo M fits 32 bits; of equal L the largest D.  0 when there is none (fo > fs among them).
+ * The rate comes from the network, so the search does not walk all D (fs / fo / 2 of them): fo D / fs > 1 / 2 makes M < 2 L, so an
+ * eligible D has an M below 2 * MAX_L that divides fs, and with g = fs / M it is a multiple k of g / gcd(g, fo) with
+ * L = k fo / gcd(g, fo) <= MAX_L.  Those D are the candidates; each is then judged by the rule as stated. */
+static uint32_t xl_wire_any_rate(uint32_t fs, uint32_t fo, xlating_wire_resample *rs) {
+  const uint32_t dmax = fs / fo, dmin = dmax / 2 + 1;
+  uint32_t best = 0, m;
+  for (m = 1; m < 2 * XLATING_RESAMPLE_MAX_L && m <= fs; ++m) {
+    uint64_t step, f, k, k1;
+    if (fs % m != 0) continue;
+    step = (fs / m) / xl_wire_gcd(fs / m, fo);
+    f = fo / xl_wire_gcd(fs / m, fo);
+    k1 = dmax / step;
+    if (k1 > XLATING_RESAMPLE_MAX_L / f) k1 = XLATING_RESAMPLE_MAX_L / f;
+    for (k = (dmin + step - 1) / step; k <= k1; ++k) {
+      const uint32_t d = (uint32_t)(k * step);
+      const uint64_t g = xl_wire_gcd((uint64_t)fo * d, fs);
+      const uint64_t L = (uint64_t)fo * d / g, M = fs / g;
+      if (L > XLATING_RESAMPLE_MAX_L || (uint64_t)fo * M > UINT32_MAX) continue;
+      if (best == 0 || L < rs->L || (L == rs->L && d > best))
+        best = d, rs->L = (uint32_t)L, rs->M = (uint32_t)M, rs->virtual_rate = (uint32_t)(fo * M);
+    }
+  }
+  return best;
+}
+
+/* rs == NULL: the reference's rule, the rate must divide the band rate; else a rate that does not is given a second stage */
+static int xl_wire_admit_rule(const xlating_wire_request *req, uint32_t band_sampling_rate, uint32_t current_band_freq,
+                              uint32_t lpf_cutoff_rate, xlating_wire_admission *adm, xlating_wire_resample *rs,
+                              uint32_t *failure_details) {
+  uint32_t why = XL_WIRE_DETAILS_INVALID_REQUEST, decimation = 0;
   int ok = 0;
   if (req == NULL || adm == NULL || band_sampling_rate == 0 || lpf_cutoff_rate == 0) return -EINVAL;
   do {
     /* tcp_server.c:100-104: the rate must divide the band rate */
-    if (req->sampling_rate > 0 && band_sampling_rate % req->sampling_rate != 0) break;
+    if (req->sampling_rate > 0 && band_sampling_rate % req->sampling_rate != 0) {
+      if (rs == NULL) break;
+      decimation = xl_wire_any_rate(band_sampling_rate, req->sampling_rate, rs);
+      if (decimation == 0) break;
+    } else if (rs != NULL) {
+      rs->L = rs->M = 1, rs->virtual_rate = req->sampling_rate;
+    }
     /* :111-127 */
     if (req->center_freq == 0 || req->sampling_rate == 0 || req->band_freq == 0) break;
     if (req->destination != XL_WIRE_DESTINATION_FILE && req->destination != XL_WIRE_DESTINATION_SOCKET) break;
@@ -101,11 +146,32 @@ int xlating_wire_admit(const xlating_wire_request *req, uint32_t band_sampling_r
     if (failure_details) *failure_details = why;
     return -EINVAL;
   }
-  adm->decimation = band_sampling_rate / req->sampling_rate;
+  adm->decimation = decimation != 0 ? decimation : band_sampling_rate / req->sampling_rate;
   adm->center_offset = (int32_t)((int64_t)req->center_freq - (int64_t)req->band_freq); /* dsp_worker.c:104 */
   adm->lpf_cutoff = req->sampling_rate / 2;                                             /* dsp_worker.c:98 */
   adm->lpf_transition = req->sampling_rate / lpf_cutoff_rate;
   if (failure_details) *failure_details = 0;
+  return 0;
+}
+
+int xlating_wire_admit(const xlating_wire_request *req, uint32_t band_sampling_rate, uint32_t current_band_freq,
+                       uint32_t lpf_cutoff_rate, xlating_wire_admission *adm, uint32_t *failure_details) {
+  return xl_wire_admit_rule(req, band_sampling_rate, current_band_freq, lpf_cutoff_rate, adm, NULL, failure_details);
+}
+
+int xlating_wire_admit_any_rate(const xlating_wire_request *req, uint32_t band_sampling_rate, uint32_t current_band_freq,
+                                uint32_t lpf_cutoff_rate, xlating_wire_admission *adm, xlating_wire_resample *rs,
+                                uint32_t *failure_details) {
+  if (rs == NULL) return -EINVAL;
+  return xl_wire_admit_rule(req, band_sampling_rate, current_band_freq, lpf_cutoff_rate, adm, rs, failure_details);
+}
+
+int xlating_wire_resample_taps(const xlating_wire_request *req, const xlating_wire_resample *rs, uint32_t lpf_cutoff_rate,
+                               float **taps, size_t *len) {
+  if (req == NULL || rs == NULL || taps == NULL || len == NULL || lpf_cutoff_rate == 0 || rs->L == 0) return -EINVAL;
+  if (create_low_pass_filter((float)rs->L, rs->virtual_rate, req->sampling_rate / 2, req->sampling_rate / lpf_cutoff_rate, taps,
+                             len) != 0)
+    return -EINVAL;
   return 0;
 }
 

@@ -11,7 +11,10 @@ src/sdr/*_device.c, src/tcp_server.c:257-271).
 Every --client CENTER_HZ:RATE_HZ goes through the 15-byte wire request, the admission rules and
 xlating_wire_add_client, and ends up as <out>/<id>.cf32[.gz].  With --waterfall-width W every admitted client also gets a stream of a
 spectrum bank (include/xlating_spectrum.h) at its own rate, fed from the engine's device rows after every block, and <out>/<id>.png:
-the 8-bit gray waterfall sdr_spectrogram makes from that client's .cf32 (-w W -s RATE -d cf32)."""
+the 8-bit gray waterfall sdr_spectrogram makes from that client's .cf32 (-w W -s RATE -d cf32).
+With --any-rate a client whose RATE_HZ does not divide the band rate is admitted too (xlating_wire_admit_any_rate): the engine takes it
+to band_rate / D, one resampler bank (include/xlating_resample.h) from there to RATE_HZ by L / M, and its .cf32 and waterfall are at
+RATE_HZ like everybody's."""
 import argparse
 import os
 import struct
@@ -41,28 +44,47 @@ def write_gray_png(path, pixels):
 
 
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
-           gzip=False, writer_threads=2, waterfall_width=None):
+           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False):
     """clients: [(center_hz, rate_hz)].  Returns {client_id: (center_hz, rate_hz)} of the admitted ones, the list of
     (center, rate, failure_details) of the rejected ones and the run's counters.  waterfall_width: also write <out>/<id>.png per
-    admitted client whose output holds at least one row (rate samples)."""
+    admitted client whose output holds at least one row (rate samples).  any_rate: admit rates that do not divide the band rate through
+    a resampler bank behind the engine."""
     os.makedirs(out_dir, exist_ok=True)
     bank = xl.SpectrumBank(waterfall_width, "cf32") if waterfall_width else None
     streams, rows, samples = {}, {}, {}  # client id -> bank stream, its rows so far, its output samples so far
     eng = xl.BatchEngine(band_rate, fmt, buffer_size)
     sinks = xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
     admitted, rejected = {}, []
+    rbank, rsinks, rstreams = None, None, {}  # the second stage: client id -> resampler stream; those clients' sinks are written, not submitted
     for center, rate in clients:
         code, req = xl.wire_parse_request(xl.wire_build_request(center, rate, band_freq, 0)[2:])
         assert code == 0
-        code, adm, why = xl.wire_admit(req, band_rate, band_freq if admitted else 0, lpf_cutoff_rate)
+        rs = None
+        if any_rate:
+            code, adm, rs, why = xl.wire_admit_any_rate(req, band_rate, band_freq if admitted else 0, lpf_cutoff_rate)
+        else:
+            code, adm, why = xl.wire_admit(req, band_rate, band_freq if admitted else 0, lpf_cutoff_rate)
         if code != 0:
             rejected.append((center, rate, why))
             continue
+        rtaps = None
+        if rs is not None and (rs.L, rs.M) != (1, 1):
+            code, rtaps = xl.wire_resample_taps(req, rs, lpf_cutoff_rate)
+            if code != 0:
+                rejected.append((center, rate, 3))  # INTERNAL_ERROR
+                continue
         cid = xl.wire_add_client(eng, adm, band_rate)
         if cid < 0:
             rejected.append((center, rate, 3))  # INTERNAL_ERROR
             continue
-        assert sinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
+        if rtaps is not None:
+            if rbank is None:
+                rbank = xl.ResamplerBank()
+                rsinks = xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
+            rstreams[cid] = rbank.add(rs.L, rs.M, rtaps)
+            assert rsinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
+        else:
+            assert sinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
         admitted[cid] = (center, rate)
         if bank is not None and rate >= waterfall_width:
             streams[cid], rows[cid], samples[cid] = bank.add(rate), [], 0
@@ -79,20 +101,34 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
         eng.process_host(blk, variant)
         eng.fetch()
         sinks.submit(eng)
-        if streams:  # (fetch has waited for the block; the device rows hold until the next process call)
-            bank.feed_engine(eng, streams)
+        if rstreams:  # (fetch has waited for the block; the device rows hold until the next process call)
+            rbank.feed_engine(eng, rstreams)
+            rbank.fetch()
+            for cid, rid in rstreams.items():
+                rsinks.write(cid, rbank.output(rid))
+        if streams:
+            direct = {cid: sid for cid, sid in streams.items() if cid not in rstreams}
+            if direct:
+                bank.feed_engine(eng, direct)
+            second = [(streams[cid], *rbank.output_device(rid)) for cid, rid in rstreams.items() if cid in streams]
+            if second:  # (the resampler's device rows hold until its next feed)
+                bank.feed([sid for sid, _, _ in second], [p or 0 for _, p, _ in second], [n for _, _, n in second])
             for cid, sid in streams.items():
-                samples[cid] += eng.output_len(cid)
+                samples[cid] += rbank.output_device(rstreams[cid])[1] if cid in rstreams else eng.output_len(cid)
                 if bank.rows_pending(sid):
                     rows[cid].append(bank.take_rows(sid)[1])
-        for cid in sinks.failed():
-            sinks.detach(cid)
+        for cid in sinks.failed() + (rsinks.failed() if rsinks is not None else []):
+            (rsinks if cid in rstreams else sinks).detach(cid)
             eng.remove_client(cid)
             admitted.pop(cid, None)
             if cid in streams:
                 bank.remove(streams.pop(cid))
+            if cid in rstreams:
+                rbank.remove(rstreams.pop(cid))
         nblocks += 1
     sinks.flush()
+    if rsinks is not None:
+        rsinks.flush()
     for cid, sid in streams.items():
         rows[cid].append(bank.take_rows(sid)[1])
         px = np.concatenate(rows[cid])[:samples[cid] // admitted[cid][1]]  # (a last row whose skipped tail never came is no row)
@@ -101,9 +137,13 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
     if bank is not None:
         bank.close()
     for cid in list(admitted):
-        sinks.detach(cid)
+        (rsinks if cid in rstreams else sinks).detach(cid)
     written, dropped = sinks.stats()
     sinks.close()
+    if rbank is not None:
+        written, dropped = (a + b for a, b in zip((written, dropped), rsinks.stats()))
+        rsinks.close()
+        rbank.close()
     eng.close()
     return admitted, rejected, {"blocks": nblocks, "bytes_written": written, "blocks_dropped": dropped}
 
@@ -121,10 +161,12 @@ def main():
     ap.add_argument("--variant", default="optimized", choices=["native", "optimized"])
     ap.add_argument("--gzip", action="store_true")
     ap.add_argument("--waterfall-width", type=int, default=None, help="also write <id>.png: each client's waterfall, this many bins wide")
+    ap.add_argument("--any-rate", action="store_true",
+                    help="admit rates that do not divide the band rate: integer decimation in the engine, then a resampler bank")
     a = ap.parse_args()
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate,
-                          a.variant, a.gzip, waterfall_width=a.waterfall_width)
+                          a.variant, a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate)
     for cid, (c, r) in adm.items():
         print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.cf32{'.gz' if a.gzip else ''}")
     for c, r, why in rej:
