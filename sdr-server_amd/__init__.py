@@ -1005,34 +1005,40 @@ class ResamplerBank:
     """One `xlating_resample_bank *` (include/xlating_resample.h): many complex float32 streams, each resampled by its own L / M
     with its own prototype, advanced together by one feed of device buffers; the latest feed's outputs are read per stream."""
 
+    _prefix = "xlating_resample_bank_"  # (ResamplerBankQ15: the other header's functions, the same signatures)
+    _lib = staticmethod(resample_lib)
+
+    def _call(self, name, *args):
+        return getattr(self._lib(), self._prefix + name)(self.h, *args)
+
     def __init__(self):
         h = C.c_void_p()
-        code = resample_lib().xlating_resample_bank_create(C.byref(h))
+        code = getattr(self._lib(), self._prefix + "create")(C.byref(h))
         if code != 0:
-            raise XlatingError("xlating_resample_bank_create", code)
+            raise XlatingError(self._prefix + "create", code)
         self.h = h
 
     def add(self, L, M, taps):
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        sid = resample_lib().xlating_resample_bank_add(self.h, L, M, t.ctypes.data, t.size)
+        sid = self._call("add", L, M, t.ctypes.data, t.size)
         if sid < 0:
-            raise XlatingError("xlating_resample_bank_add", sid)
+            raise XlatingError(self._prefix + "add", sid)
         return sid
 
     def remove(self, stream_id):
-        code = resample_lib().xlating_resample_bank_remove(self.h, stream_id)
+        code = self._call("remove", stream_id)
         if code != 0:
-            raise XlatingError("xlating_resample_bank_remove", code)
+            raise XlatingError(self._prefix + "remove", code)
 
     def feed(self, ids, ptrs, counts, stream=0):
-        """stream ids[i] consumes counts[i] complex float32 samples from device address ptrs[i], in place, ordered on `stream`."""
+        """stream ids[i] consumes counts[i] complex samples from device address ptrs[i], in place, ordered on `stream`."""
         a = np.ascontiguousarray(ids, dtype=np.intc)
         p = np.ascontiguousarray(ptrs, dtype=np.uint64)
         c = np.ascontiguousarray(counts, dtype=np.uint64)
         assert a.size == p.size == c.size
-        code = resample_lib().xlating_resample_bank_feed_device(self.h, a.size, a.ctypes.data, p.ctypes.data, c.ctypes.data, stream)
+        code = self._call("feed_device", a.size, a.ctypes.data, p.ctypes.data, c.ctypes.data, stream)
         if code != 0:
-            raise XlatingError("xlating_resample_bank_feed_device", code)
+            raise XlatingError(self._prefix + "feed_device", code)
 
     def feed_engine(self, engine, streams, stream=0):
         """streams: {client id of `engine`: stream id}.  Feeds every listed client's output of the engine's latest call in one call;
@@ -1040,16 +1046,16 @@ class ResamplerBank:
         self.feed(*SpectrumBank.gather_engine(engine, streams), stream)
 
     def fetch(self):
-        code = resample_lib().xlating_resample_bank_fetch(self.h)
+        code = self._call("fetch")
         if code != 0:
-            raise XlatingError("xlating_resample_bank_fetch", code)
+            raise XlatingError(self._prefix + "fetch", code)
 
     def output(self, stream_id):
         """-> complex64 [n]: the stream's outputs of the latest feed as of the latest fetch (a copy)"""
         p, n = _c_float_p(), C.c_size_t(0)
-        code = resample_lib().xlating_resample_bank_output_host(self.h, stream_id, C.byref(p), C.byref(n))
+        code = self._call("output_host", stream_id, C.byref(p), C.byref(n))
         if code != 0:
-            raise XlatingError("xlating_resample_bank_output_host", code)
+            raise XlatingError(self._prefix + "output_host", code)
         if n.value == 0:
             return np.zeros(0, np.complex64)
         return np.ctypeslib.as_array(p, shape=(2 * n.value,)).copy().view(np.complex64)
@@ -1057,29 +1063,29 @@ class ResamplerBank:
     def output_device(self, stream_id):
         """-> (device pointer | None, complex samples) of the stream's outputs of the latest feed; valid until the next feed"""
         p, n = C.c_void_p(), C.c_size_t(0)
-        code = resample_lib().xlating_resample_bank_output_device(self.h, stream_id, C.byref(p), C.byref(n))
+        code = self._call("output_device", stream_id, C.byref(p), C.byref(n))
         if code != 0:
-            raise XlatingError("xlating_resample_bank_output_device", code)
+            raise XlatingError(self._prefix + "output_device", code)
         return p.value, n.value
 
     def produced(self, stream_id):
-        return resample_lib().xlating_resample_bank_produced(self.h, stream_id)
+        return self._call("produced", stream_id)
 
     def last_feed_ops(self):
         """-> (kernel launches, memory copies) the latest feed issued"""
         a, b = C.c_uint(0), C.c_uint(0)
-        resample_lib().xlating_resample_bank_last_feed_ops(self.h, C.byref(a), C.byref(b))
+        self._call("last_feed_ops", C.byref(a), C.byref(b))
         return a.value, b.value
 
     def stats(self):
         """-> (live streams, device tap tables, their bytes)"""
         a, b, c = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
-        resample_lib().xlating_resample_bank_stats(self.h, C.byref(a), C.byref(b), C.byref(c))
+        self._call("stats", C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
 
     def close(self):
         if getattr(self, "h", None):
-            resample_lib().xlating_resample_bank_destroy(self.h)
+            self._call("destroy")
             self.h = None
 
     def __del__(self):
@@ -1087,3 +1093,54 @@ class ResamplerBank:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------------------------------------- Q15 resampler bank (the same library)
+RESAMPLE_Q15_SYMBOLS = ["xlating_resample_q15_quantize"] + [s.replace("xlating_resample_bank_", "xlating_resample_q15_bank_")
+                                                            for s in RESAMPLE_SYMBOLS]
+_rqlib = None
+
+
+def resample_q15_lib():
+    """include/xlating_resample_q15.h: the resampler bank of the cs16 output family (libxlating_resample.so, bound once)."""
+    global _rqlib
+    if _rqlib is not None:
+        return _rqlib
+    R = resample_lib()
+    R.xlating_resample_q15_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    R.xlating_resample_q15_quantize.restype = C.c_int
+    for name in RESAMPLE_SYMBOLS:  # the float bank's signatures, one for one; output_host gives int16
+        f, q = getattr(R, name), getattr(R, name.replace("xlating_resample_bank_", "xlating_resample_q15_bank_"))
+        q.argtypes, q.restype = list(f.argtypes), f.restype
+    R.xlating_resample_q15_bank_output_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(_c_i16_p), C.POINTER(C.c_size_t)]
+    _rqlib = R
+    return R
+
+
+def resample_q15_quantize(taps):
+    """xlating_resample_q15_quantize: float32 taps -> int16 array, c = trunc(h * 32768); XlatingError(-ERANGE) for a tap that is
+    not finite or does not fit, XlatingError(-EINVAL) for no taps"""
+    t = np.ascontiguousarray(taps, dtype=np.float32)
+    out = np.zeros(t.size, np.int16)
+    code = resample_q15_lib().xlating_resample_q15_quantize(t.ctypes.data if t.size else None, t.size, out.ctypes.data if t.size else None)
+    if code != 0:
+        raise XlatingError("xlating_resample_q15_quantize", code)
+    return out
+
+
+class ResamplerBankQ15(ResamplerBank):
+    """One `xlating_resample_q15_bank *` (include/xlating_resample_q15.h): many streams of int16 (re, im) pairs -- the engine's rows
+    after a "q15" call -- each resampled by its own L / M in exact Q15 arithmetic.  ResamplerBank's methods; counts are complex samples
+    of 4 bytes, output() is int16 [n, 2]."""
+    _prefix = "xlating_resample_q15_bank_"
+    _lib = staticmethod(resample_q15_lib)
+
+    def output(self, stream_id):
+        """-> int16 [n, 2]: the stream's outputs of the latest feed as of the latest fetch (a copy)"""
+        p, n = _c_i16_p(), C.c_size_t(0)
+        code = self._call("output_host", stream_id, C.byref(p), C.byref(n))
+        if code != 0:
+            raise XlatingError(self._prefix + "output_host", code)
+        if n.value == 0:
+            return np.zeros((0, 2), np.int16)
+        return np.ctypeslib.as_array(p, shape=(n.value, 2)).copy()

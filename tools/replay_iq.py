@@ -6,7 +6,7 @@ the device (its device plugins deliver blocks of `buffer_size` bytes: cu8 rtl-sd
 src/sdr/*_device.c, src/tcp_server.c:257-271).
 
   python tools/replay_iq.py capture.cu8 --format cu8 --band-rate 2016000 --band-freq 460100000 --out /tmp/out \\
-         --client 460112000:48000 --client 460050000:96000 [--gzip] [--variant optimized]
+         --client 460112000:48000 --client 460050000:96000 [--gzip] [--variant optimized | native | q15]
 
 Every --client CENTER_HZ:RATE_HZ goes through the 15-byte wire request, the admission rules and
 xlating_wire_add_client, and ends up as <out>/<id>.cf32[.gz].  With --waterfall-width W every admitted client also gets a stream of a
@@ -14,7 +14,11 @@ spectrum bank (include/xlating_spectrum.h) at its own rate, fed from the engine'
 the 8-bit gray waterfall sdr_spectrogram makes from that client's .cf32 (-w W -s RATE -d cf32).
 With --any-rate a client whose RATE_HZ does not divide the band rate is admitted too (xlating_wire_admit_any_rate): the engine takes it
 to band_rate / D, one resampler bank (include/xlating_resample.h) from there to RATE_HZ by L / M, and its .cf32 and waterfall are at
-RATE_HZ like everybody's."""
+RATE_HZ like everybody's.
+With --variant q15 the engine runs the reference's cs16 output family (XL_MODE_Q15: exact Q15 arithmetic, int16 pairs), the second
+stage of --any-rate is the Q15 resampler bank (include/xlating_resample_q15.h), the waterfall is that of cs16 samples, and every
+client's samples are written by this tool itself as <out>/<id>.cs16 (raw int16 pairs): the sinks library writes the cf32 family's
+files, so --gzip, which is its work, is refused together with q15."""
 import argparse
 import os
 import struct
@@ -48,12 +52,16 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
     """clients: [(center_hz, rate_hz)].  Returns {client_id: (center_hz, rate_hz)} of the admitted ones, the list of
     (center, rate, failure_details) of the rejected ones and the run's counters.  waterfall_width: also write <out>/<id>.png per
     admitted client whose output holds at least one row (rate samples).  any_rate: admit rates that do not divide the band rate through
-    a resampler bank behind the engine."""
+    a resampler bank behind the engine.  variant "q15": the cs16 family throughout, <out>/<id>.cs16 written here, no gzip."""
+    q15 = variant == "q15"
+    if q15 and gzip:
+        raise ValueError("gzip is the sinks library's, which writes the cf32 family: not with variant q15")
     os.makedirs(out_dir, exist_ok=True)
-    bank = xl.SpectrumBank(waterfall_width, "cf32") if waterfall_width else None
+    bank = xl.SpectrumBank(waterfall_width, "cs16" if q15 else "cf32") if waterfall_width else None
     streams, rows, samples = {}, {}, {}  # client id -> bank stream, its rows so far, its output samples so far
     eng = xl.BatchEngine(band_rate, fmt, buffer_size)
-    sinks = xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
+    sinks = None if q15 else xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
+    files, written = {}, 0  # q15: client id -> its open <id>.cs16, the bytes written to them
     admitted, rejected = {}, []
     rbank, rsinks, rstreams = None, None, {}  # the second stage: client id -> resampler stream; those clients' sinks are written, not submitted
     for center, rate in clients:
@@ -78,13 +86,18 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             rejected.append((center, rate, 3))  # INTERNAL_ERROR
             continue
         if rtaps is not None:
-            if rbank is None:
+            if rbank is None and q15:
+                rbank = xl.ResamplerBankQ15()
+            elif rbank is None:
                 rbank = xl.ResamplerBank()
                 rsinks = xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
             rstreams[cid] = rbank.add(rs.L, rs.M, rtaps)
-            assert rsinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
-        else:
+            if not q15:
+                assert rsinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
+        elif not q15:
             assert sinks.attach_file(cid, out_dir, use_gzip=gzip) == 0
+        if q15:
+            files[cid] = open(os.path.join(out_dir, f"{cid}.cs16"), "wb")
         admitted[cid] = (center, rate)
         if bank is not None and rate >= waterfall_width:
             streams[cid], rows[cid], samples[cid] = bank.add(rate), [], 0
@@ -100,12 +113,20 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             break
         eng.process_host(blk, variant)
         eng.fetch()
-        sinks.submit(eng)
+        if q15:
+            for cid, f in files.items():
+                if cid not in rstreams:
+                    written += f.write(eng.output_cs16(cid).tobytes())
+        else:
+            sinks.submit(eng)
         if rstreams:  # (fetch has waited for the block; the device rows hold until the next process call)
             rbank.feed_engine(eng, rstreams)
             rbank.fetch()
             for cid, rid in rstreams.items():
-                rsinks.write(cid, rbank.output(rid))
+                if q15:
+                    written += files[cid].write(rbank.output(rid).tobytes())
+                else:
+                    rsinks.write(cid, rbank.output(rid))
         if streams:
             direct = {cid: sid for cid, sid in streams.items() if cid not in rstreams}
             if direct:
@@ -117,7 +138,7 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
                 samples[cid] += rbank.output_device(rstreams[cid])[1] if cid in rstreams else eng.output_len(cid)
                 if bank.rows_pending(sid):
                     rows[cid].append(bank.take_rows(sid)[1])
-        for cid in sinks.failed() + (rsinks.failed() if rsinks is not None else []):
+        for cid in [] if q15 else sinks.failed() + (rsinks.failed() if rsinks is not None else []):
             (rsinks if cid in rstreams else sinks).detach(cid)
             eng.remove_client(cid)
             admitted.pop(cid, None)
@@ -126,7 +147,8 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             if cid in rstreams:
                 rbank.remove(rstreams.pop(cid))
         nblocks += 1
-    sinks.flush()
+    if sinks is not None:
+        sinks.flush()
     if rsinks is not None:
         rsinks.flush()
     for cid, sid in streams.items():
@@ -136,19 +158,24 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             write_gray_png(os.path.join(out_dir, f"{cid}.png"), px)
     if bank is not None:
         bank.close()
-    for cid in list(admitted):
-        (rsinks if cid in rstreams else sinks).detach(cid)
-    written, dropped = sinks.stats()
-    sinks.close()
-    if rbank is not None:
+    for f in files.values():
+        f.close()
+    dropped = 0
+    if sinks is not None:
+        for cid in list(admitted):
+            (rsinks if cid in rstreams else sinks).detach(cid)
+        written, dropped = sinks.stats()
+        sinks.close()
+    if rsinks is not None:
         written, dropped = (a + b for a, b in zip((written, dropped), rsinks.stats()))
         rsinks.close()
+    if rbank is not None:
         rbank.close()
     eng.close()
     return admitted, rejected, {"blocks": nblocks, "bytes_written": written, "blocks_dropped": dropped}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("iq_file")
     ap.add_argument("--format", default="cu8", choices=list(DTYPES))
@@ -158,17 +185,25 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--buffer-size", type=int, default=262144)
     ap.add_argument("--lpf-cutoff-rate", type=int, default=5)
-    ap.add_argument("--variant", default="optimized", choices=["native", "optimized"])
-    ap.add_argument("--gzip", action="store_true")
+    ap.add_argument("--variant", default="optimized", choices=["native", "optimized", "q15"],
+                    help="q15: the cs16 output family; every client's samples are written as <id>.cs16 (raw int16 pairs)")
+    ap.add_argument("--gzip", action="store_true", help="gzip the .cf32 files (the sinks library's work: refused with --variant q15)")
     ap.add_argument("--waterfall-width", type=int, default=None, help="also write <id>.png: each client's waterfall, this many bins wide")
     ap.add_argument("--any-rate", action="store_true",
                     help="admit rates that do not divide the band rate: integer decimation in the engine, then a resampler bank")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.gzip and a.variant == "q15":
+        ap.error("--gzip is refused with --variant q15: the .cs16 files are written raw by this tool, not by the sinks library")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate,
                           a.variant, a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate)
     for cid, (c, r) in adm.items():
-        print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.cf32{'.gz' if a.gzip else ''}")
+        print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{'cs16' if a.variant == 'q15' else 'cf32'}{'.gz' if a.gzip else ''}")
     for c, r, why in rej:
         print(f"rejected: center {c} Hz rate {r} Hz (details {why})")
     print(st)
