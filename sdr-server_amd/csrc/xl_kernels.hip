@@ -87,6 +87,46 @@ XL_DEV uint32_t xl_lds_poll(const uint32_t addr) {
   return v;
 }
 
+// The chain wave's view of the drainers: all three counters with ONE wait (three polls in a row are three LDS round trips).
+XL_DEV uint32_t xl_lds_poll3_min(const uint32_t a0, const uint32_t a1, const uint32_t a2) {
+  uint32_t v0, v1, v2;
+  asm volatile("ds_read_b32 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b32 %2, %5\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(v0), "=&v"(v1), "=&v"(v2)
+               : "v"(a0), "v"(a1), "v"(a2)
+               : "memory");
+  v0 = v0 < v1 ? v0 : v1;
+  return v0 < v2 ? v0 : v2;
+}
+// All entry pairs below mn (the least of the drainers' next pairs) have left the ring: the entries below 2 mn + XLC_RING may
+// be written (a drainer that is through with the call posts 0xFFFFFFFF).
+XL_DEV uint32_t xl_chain_lim(const uint32_t mn) { return mn >= 0x7FFFFFE0u ? 0xFFFFFFFFu : 2u * mn + XLC_RING; }
+// Wait until the entries below `upto` may be written.  Bounded: a drainer that never shows up must not hang the device (cannot
+// happen while the four waves of the workgroup are resident, which a launch guarantees) -- ~0.1 s, then the table is wrong,
+// the launch ends.
+XL_DEV uint32_t xl_chain_wait_drained(const uint32_t upto, const uint32_t a0, const uint32_t a1, const uint32_t a2) {
+  uint32_t lim = 0u;
+  for (uint32_t spin = 0; spin < (1u << 22); ++spin) {
+    lim = xl_chain_lim((uint32_t)__builtin_amdgcn_readfirstlane((int)xl_lds_poll3_min(a0, a1, a2)));
+    if (upto <= lim) break;
+    __builtin_amdgcn_s_sleep(1);
+  }
+  return lim;
+}
+// The least event index of the wave (0xFFFFFFFF = this lane has none).  Clients that joined together share their block ends:
+// when every lane that has an event has the same one, there is nothing to reduce.
+XL_DEV uint32_t xl_chain_event(uint32_t ev) {
+  const unsigned long long act = __ballot(ev != 0xFFFFFFFFu);
+  if (act == 0ull) return 0xFFFFFFFFu;
+  const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)ev, (int)__ffsll((long long)act) - 1);
+  if (__ballot(ev != 0xFFFFFFFFu && ev != first) == 0ull) return first;
+#pragma unroll
+  for (int sh = 1; sh < 64; sh <<= 1) {
+    const uint32_t other = (uint32_t)__shfl_xor((int)ev, sh);
+    ev = other < ev ? other : ev;
+  }
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)ev);
+}
+
 // One table entry of the chain wave = 16 recurrence steps, hand-scheduled.  A lone wave issues in order, and each step
 // is mul, mul, (wait ~6 cycles), add, (wait ~6 cycles): an independent instruction placed in a wait costs nothing,
 // anywhere else it costs its 4-5 issue cycles (the compiler's version of the entry bookkeeping took the step from 17.5
@@ -138,12 +178,37 @@ XL_DEV uint32_t xl_lds_poll(const uint32_t addr) {
   XLC_E8("0", "512", "1024", "1536", "2048", "2560", "3072", "3584")   \
   XLC_E7("4096", "4608", "5120", "5632", "6144", "6656", "7168")       \
   XLC_MUL "ds_write_b64 %[addr], %[p] offset:7680\n\t" XLC_ADD XLC_BLOCK_END("16", "0x2000")
-#define XLC_B32                                                         \
-  XLC_E8("0", "512", "1024", "1536", "2048", "2560", "3072", "3584")   \
-  XLC_E8("4096", "4608", "5120", "5632", "6144", "6656", "7168", "7680") \
-  XLC_E8("8192", "8704", "9216", "9728", "10240", "10752", "11264", "11776") \
-  XLC_E7("12288", "12800", "13312", "13824", "14336", "14848", "15360") \
-  XLC_MUL "ds_write_b64 %[addr], %[p] offset:15872\n\t" XLC_ADD XLC_BLOCK_END("32", "0x4000")
+// The 32-entry block is the body of a loop that stays inside one asm block: the code between two asm blocks -- choosing the
+// next block, its ring address, the drain check -- is a few dozen scalar instructions and taken branches, and a lone wave pays
+// each in full (measured, profiles/chain_nonstep_time.txt: ~1400 cycles per 32 entries against ~7100 for the block itself).
+// The drain check costs no round trip: the three drainers' counters are read in the shadows of entry 30's steps (a stale
+// value is only ever too small), and the last entry's idle steps take their minimum and weigh it against [need], the pair
+// index below which everything must have left the ring before the NEXT block may be written.  [todo] counts the blocks still
+// wanted; the loop goes on while there is one and the drainers have kept up, otherwise the code after the block sorts it out
+// ([sm] = the minimum it saw).  The 4-byte instructions come in pairs, in the two shadows of one step, so that the 8-byte ones
+// after them stay on 8-byte boundaries.  (Shadows are not free for everything: 32 entries that each carry their own ring
+// address, count and exit test -- one asm block for any region, no alignment -- ran at 17.0 cycles per step against 13.9.)
+#define XLC_STEP2(I1, I2) XLC_MUL I1 "\n\t" XLC_ADD I2 "\n\t"
+#define XLC_B32_LOOP                                                                                         \
+  XLC_E8("0", "512", "1024", "1536", "2048", "2560", "3072", "3584")                                       \
+  XLC_E8("4096", "4608", "5120", "5632", "6144", "6656", "7168", "7680")                                   \
+  XLC_E8("8192", "8704", "9216", "9728", "10240", "10752", "11264", "11776")                               \
+  XLC_E("12288") XLC_E("12800") XLC_E("13312") XLC_E("13824") XLC_E("14336") XLC_E("14848")               \
+  XLC_QENTRY("15360")                                                                                      \
+  XLC_MUL "ds_read_b32 %[mn], %[an0]\n\t" XLC_ADD                                                           \
+  XLC_MUL "ds_read_b32 %[n1], %[an1]\n\t" XLC_ADD                                                           \
+  XLC_MUL "ds_read_b32 %[n2], %[an2]\n\t" XLC_ADD XLC_STEPS10                                               \
+  XLC_MUL "ds_write_b64 %[addr], %[p] offset:15872\n\t" XLC_ADD                                             \
+  XLC_MUL "v_add_u32 %[cnt], 32, %[cnt]\n\t" XLC_ADD "s_sub_u32 %[todo], %[todo], 1\n\t"                    \
+  XLC_MUL "ds_write_b32 %[paddr], %[cnt]\n\t" XLC_ADD                                                       \
+  XLC_MUL "v_add_u32 %[off], 0x4000, %[off]\n\t" XLC_ADD                                                    \
+  XLC_MUL "v_and_b32 %[off], 0x7fff, %[off]\n\t" XLC_ADD                                                    \
+  XLC_STEP2("v_add_u32 %[addr], %[off], %[base]", "s_add_u32 %[need], %[need], 16")                         \
+  XLC_STEP2("s_waitcnt lgkmcnt(0)", "v_min_u32 %[mn], %[mn], %[n1]")                                        \
+  XLC_STEP2("v_min_u32 %[mn], %[mn], %[n2]", "s_nop 0")                                                     \
+  XLC_STEP2("v_readfirstlane_b32 %[sm], %[mn]", "s_nop 0")                                                  \
+  XLC_STEP2("s_cmp_ge_u32 %[sm], %[need]", "s_cselect_b32 %[st], %[todo], 0")                               \
+  XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP
 static_assert(XL_PH_STRIDE == 16u && XLC_RING * 64u * 8u == 0x8000u, "XLC_ENTRY is written for 16 steps per entry and a 32 KB ring");
 
 // One launch tabulates `calls.n` consecutive calls of the same shape (pos, then xl_grid_next of it, ...): table and final
@@ -184,7 +249,7 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
     __syncthreads();
     if (w == 0 && E > 0u) atomicMax(&s_emax, E);
     __syncthreads();
-    const uint32_t Emax = s_emax;
+    const uint32_t Emax = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_emax);
     const uint32_t a_prod = xl_lds_off(&s_prod), a_ring0 = xl_lds_off(&ring[0][0]), a_ring = xl_lds_off(&ring[0][lane]);
     v2f *__restrict__ o = reinterpret_cast<v2f *>(tab) + (k.out_off >> XL_PH_SHIFT);  // out_off = 0 mod 2 * XL_PH_STRIDE: 16-byte pairs
     if (w == 0) {
@@ -193,40 +258,35 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
       uint32_t nb = xl_bnd_next(bnd, 0u);  // the phase is renormalised after output nb - 1 (xlating.c:73)
       const uint32_t a_n0 = xl_lds_off(&s_next[0]), a_n1 = xl_lds_off(&s_next[1]), a_n2 = xl_lds_off(&s_next[2]);
       const unsigned long long c0 = stats ? clock64() : 0ull, w0 = stats ? wall_clock64() : 0ull;  // (tuning: shader cycles / 100 MHz ticks)
-      uint32_t e = 0;  // (wave-uniform: the lanes step in lockstep)
+      // (tuning: where a call's cycles go besides the 32-entry blocks -- the straight-line regions, their drain waits, the blocks)
+      unsigned long long t_region = 0ull, t_drain = 0ull, t_b32 = 0ull;
+      uint32_t n_drain = 0u, n_b32 = 0u, n_event = 0u, n_runs = 0u;
+      uint32_t e = 0;            // (wave-uniform: the lanes step in lockstep)
+      uint32_t lim = XLC_RING;   // entries below lim may enter the ring: the slots of the entries below lim - XLC_RING have been drained
+      // the next output index at which ANY lane has something other than a plain step to do: its block ends (renormalise)
+      // or its call ends -- worked out once per event.  Up to there the loop below is branch-free per lane.
+      uint32_t evs = xl_chain_event(0u < K ? (nb < K ? nb : K) : 0xFFFFFFFFu);
       while (e < Emax) {
-        // the next output index at which ANY lane has something other than a plain step to do: its block ends (renormalise)
-        // or its call ends.  Up to there the loop below is branch-free per lane: an entry into the ring, 16 steps.
-        uint32_t ev = (e << XL_PH_SHIFT) < K ? (nb < K ? nb : K) : 0xFFFFFFFFu;
-#pragma unroll
-        for (int sh = 1; sh < 64; sh <<= 1) {
-          const uint32_t other = (uint32_t)__shfl_xor((int)ev, sh);
-          ev = other < ev ? other : ev;
-        }
-        const uint32_t evs = __builtin_amdgcn_readfirstlane(ev);
         // entries e .. e_stop - 1: their steps hold no block end for anybody ((e + 1) * 16 < evs)
         uint32_t e_stop = evs == 0u ? 0u : (evs - 1u) >> XL_PH_SHIFT;
         e_stop = e_stop < Emax ? e_stop : Emax;
         if (pos.pad & XL_POS_FMA_STEP) e_stop = e;  // (the hand-scheduled blocks are the plain step: a call with the FMA-contracted
                                                     // step of an -mfma reference build takes the per-step path throughout)
+        const unsigned long long r0 = stats ? clock64() : 0ull;
         if ((e << XL_PH_SHIFT) < K) {  // (a lane whose call has ended sits the region out; the others' mask is constant in it)
           uint32_t ee = e;
           while (ee < e_stop) {
-            if ((ee & (XLC_RING / 2u - 1u)) == 0u && ee >= XLC_RING) {
-              // the next XLC_RING / 2 entries go to the slots of entries e - RING .. e - RING / 2 - 1: all pairs below
-              // (e - RING / 2) / 2 must have left the ring (checked once per half ring: an LDS round trip is ~50 ns).
-              // Bounded: a drainer that never shows up must not hang the device (cannot happen while the four waves of
-              // the workgroup are resident, which a launch guarantees) -- ~0.1 s, then the table is wrong, the launch ends.
-              const uint32_t q = (ee - XLC_RING / 2u) >> 1;
-              for (uint32_t spin = 0; spin < (1u << 22); ++spin) {
-                if (xl_lds_poll(a_n0) >= q && xl_lds_poll(a_n1) >= q && xl_lds_poll(a_n2) >= q) break;
-                __builtin_amdgcn_s_sleep(1);
-              }
+            // the longest block that ends by e_stop and does not run over the end of the ring (its slots are addressed with
+            // immediate offsets): no climb through the shorter ones after an event
+            const uint32_t left = e_stop - ee, slot = ee & (XLC_RING - 1u), room = XLC_RING - slot;
+            const uint32_t fit = left < room ? left : room;
+            const uint32_t nn = fit >= 32u ? 32u : fit >= 16u ? 16u : fit >= 8u ? 8u : fit >= 4u ? 4u : 1u;
+            if (ee + nn > lim) {
+              const unsigned long long d0 = stats ? clock64() : 0ull;
+              lim = xl_chain_wait_drained(ee + nn, a_n0, a_n1, a_n2);
+              if (stats) t_drain += clock64() - d0, ++n_drain;
             }
-            // entries ee .. chunk_end - 1 (up to the next drain check), two per trip
-            const uint32_t next_check = (ee | (XLC_RING / 2u - 1u)) + 1u;
-            const uint32_t chunk_end = e_stop < next_check ? e_stop : next_check;
-            uint32_t off = ((ee & (XLC_RING - 1u)) << 9) + lane * (uint32_t)sizeof(v2f);  // ring offset of entry ee, this lane
+            uint32_t off = (slot << 9) + lane * (uint32_t)sizeof(v2f);  // ring offset of entry ee, this lane
             uint32_t addr = a_ring0 + off, cnt = ee;
             v2f t1, t2;
 #define XLC_RUN(BLOCK)                                                                                            \
@@ -234,37 +294,45 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
                : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2) \
                : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod)                                        \
                : "memory")
-            for (; ee < chunk_end && (ee & 3u) != 0u; ++ee) XLC_RUN(XLC_ENTRY);  // up to a multiple of four
-            if ((ee & 7u) == 4u && ee + 4u <= chunk_end) {                       // up to a multiple of eight
-              XLC_RUN(XLC_QUAD);
-              ee += 4u;
-            }
-            if ((ee & 15u) == 8u && ee + 8u <= chunk_end) {  // up to a multiple of sixteen
-              XLC_RUN(XLC_OCT);
-              ee += 8u;
-            }
-            if ((ee & 31u) == 16u && ee + 16u <= chunk_end) {
+            if (nn == 32u) {
+              // 32-entry blocks back to back inside one asm block while the drainers keep up (a block that starts at a multiple
+              // of 32 ends where the next one may start); the drainers' counters are read during each block and weighed at its end
+              const uint32_t want = (slot & 31u) == 0u ? left >> 5 : 1u;
+              // need: the block adds 16 before it compares, so it starts one block short -- below zero (wraps, on purpose) while
+              // ee < 32.  For a lone block (want == 1) the comparison decides nothing: todo is 0 by then.
+              uint32_t todo = want, need = (ee >> 1) - 16u, mn, n1, n2, sm, st;
+              const unsigned long long b0 = stats ? clock64() : 0ull;
+              asm volatile(XLC_ALIGN "1:\n\t" XLC_B32_LOOP "s_cmp_lg_u32 %[st], 0\n\ts_cbranch_scc1 1b\n\t"
+                           : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2),
+                             [mn] "=&v"(mn), [n1] "=&v"(n1), [n2] "=&v"(n2), [todo] "+s"(todo), [need] "+s"(need), [sm] "=&s"(sm),
+                             [st] "=&s"(st)
+                           : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod), [an0] "v"(a_n0), [an1] "v"(a_n1), [an2] "v"(a_n2)
+                           : "memory", "scc");
+              const uint32_t ran = (want - todo) << 5;
+              if (stats) t_b32 += clock64() - b0, n_b32 += ran, ++n_runs;
+              lim = xl_chain_lim(sm);
+              ee += ran;
+            } else if (nn == 16u) {
               XLC_RUN(XLC_HEX);
               ee += 16u;
+            } else if (nn == 8u) {
+              XLC_RUN(XLC_OCT);
+              ee += 8u;
+            } else if (nn == 4u) {
+              XLC_RUN(XLC_QUAD);
+              ee += 4u;
+            } else {
+              XLC_RUN(XLC_ENTRY);
+              ee += 1u;
             }
-            for (; ee + 32u <= chunk_end; ee += 32u) XLC_RUN(XLC_B32);
-            for (; ee + 16u <= chunk_end; ee += 16u) XLC_RUN(XLC_HEX);
-            for (; ee + 8u <= chunk_end; ee += 8u) XLC_RUN(XLC_OCT);
-            for (; ee + 4u <= chunk_end; ee += 4u) XLC_RUN(XLC_QUAD);
-            for (; ee < chunk_end; ++ee) XLC_RUN(XLC_ENTRY);
 #undef XLC_RUN
           }
         }
         if (e_stop > e) e = e_stop;
+        if (stats) t_region += clock64() - r0, ++n_event;
         // ---- the entry that holds the event (or the tail of the call): per-step checks, every lane for itself
         if (e < Emax) {
-          if ((e & (XLC_RING / 2u - 1u)) == 0u && e >= XLC_RING) {
-            const uint32_t q = (e - XLC_RING / 2u) >> 1;
-            for (uint32_t spin = 0; spin < (1u << 22); ++spin) {
-              if (xl_lds_poll(a_n0) >= q && xl_lds_poll(a_n1) >= q && xl_lds_poll(a_n2) >= q) break;
-              __builtin_amdgcn_s_sleep(1);
-            }
-          }
+          if (e + 1u > lim) lim = xl_chain_wait_drained(e + 1u, a_n0, a_n1, a_n2);
           const uint32_t m0 = e << XL_PH_SHIFT;
           if (m0 < K) xl_lds_post64(a_ring + (e & (XLC_RING - 1u)) * 64u * (uint32_t)sizeof(v2f), p);
           xl_lds_post(a_prod, e + 1u);
@@ -276,6 +344,7 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
             }
           }
           ++e;
+          evs = xl_chain_event((e << XL_PH_SHIFT) < K ? (nb < K ? nb : K) : 0xFFFFFFFFu);
         }
       }
       if (have) state_out[k.slot] = make_float2(p.x, p.y);  // (K == 0: untouched, xlating.c:58)
@@ -288,6 +357,13 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
         if (lane == 0u && blockIdx.x < 1024u) {  // timeline of the launch: entry, per call start / end of the stepping, exit
           stats[8192u + 8u * blockIdx.x + 1u + 2u * call] = w0 - t_entry;
           stats[8192u + 8u * blockIdx.x + 2u + 2u * call] = w1 - t_entry;
+        }
+        if (lane == 0u && blockIdx.x < 128u) {  // the call's split, shader cycles: all, regions, drain waits, 32-entry blocks; counts (regions | stamped block runs << 32); a stamp's own cost
+          unsigned long long *const sp = stats + 4096u + 32u * blockIdx.x + 8u * call;
+          const unsigned long long k0 = clock64(), k1 = clock64(), k2 = clock64(), k3 = clock64(), k4 = clock64();
+          (void)k1, (void)k2, (void)k3;
+          sp[0] = k0 - c0, sp[1] = t_region, sp[2] = t_drain, sp[3] = t_b32;
+          sp[4] = n_drain, sp[5] = n_b32, sp[6] = n_event | ((unsigned long long)n_runs << 32), sp[7] = (k4 - k0) / 4ull;
         }
       }
       continue;

@@ -20,6 +20,37 @@ import sdr_server_amd as xl  # noqa: E402
 BLOCK = 262144
 
 
+def chain_split(big, nwg, ghz, tl):
+    """Where the chain wave's time goes inside one call besides plain steps (XL_EXP_CHAIN_STATS + XL_EXP_CHAIN_TIMELINE): the stamps of
+    xl_nco_chain_kernel at stats[4096 + 32 wg + 8 call ..], mean over the workgroups, in us at the chain's own clock.  A stamp costs
+    what five back-to-back reads of the counter measured; that is taken off every stamped span."""
+    ncalls = int(os.environ.get("XL_EXP_CHAIN_CALLS", "4"))
+    out = ""
+    for call in range(ncalls):
+        rows = [[big[4096 + 32 * wg + 8 * call + i] for i in range(8)] for wg in range(nwg)]
+        for r in rows:  # (regions | stamped runs of 32-entry blocks << 32)
+            r[6], runs = r[6] & 0xFFFFFFFF, r[6] >> 32
+            r.append(runs)
+        T, R, Dr, B, nd, nb, nev, s, nblk = (sum(r[i] for r in rows) / nwg for i in range(9))
+        if T <= 0 or nb <= 0:
+            continue
+        us = lambda cyc: cyc / (ghz * 1e3)
+        nblk = nblk or nb / 32.0  # (no run count recorded: one stamped run per block)
+        rate = (B - s * nblk) / (nb * 16)  # cycles per step inside the 32-entry blocks
+        entries = big[2] / ncalls
+        steps = entries * 16 * rate
+        drain = Dr - s * nd
+        stamps = s * (2 * nd + 2 * nblk + 2 * nev)
+        ends = T - steps - drain - stamps  # event entries, reductions, ramps through the shorter blocks, loop control
+        # the timeline holds entry, start / end of calls 0 .. 2, exit (8 slots): the joins 0 -> 1 and 1 -> 2 can be read from it
+        join = (tl[2 * call + 3] - tl[2 * call + 2]) / 100.0 if call + 1 < min(ncalls, 3) else None
+        out += ("\n    call %d: %.1f us = steps %.1f (%.0f entries at %.2f cycles/step) + drain checks %.2f (%d) + block ends and ramps %.2f (%d regions)"
+                " + stamps %.2f (%.0f cycles each)%s" % (
+                    call, us(T), us(steps), entries, rate, us(drain), nd, us(ends), nev, us(stamps), s,
+                    "" if join is None else "; join to the next call %.1f us" % join))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", default="128,256,1024,4096")
@@ -116,6 +147,7 @@ def sweep(args, D, data, sarg):
                             if os.environ.get("XL_EXP_CHAIN_TIMELINE") and xl.lib().xlating_batch_debug_chain_stats(eng.h, big, 4096) == 0:
                                 tl = [big[8192 + i] for i in range(8)]
                                 extra += "  launch timeline wg0 (us from entry): " + " ".join("%.1f" % (v / 100.0) for v in tl[1:])
+                                extra += chain_split(big, min(nwg, 128), sum(cyc) / max(sum(tick), 1) / 10.0, tl)
                             extra += "  chain: %.1f cycles/step, %.2f ns/step, clock %.2f GHz, start spread %.1f us" % (
                                 sum(cyc) / nwg / (ent * 16), sum(tick) / nwg * 10.0 / (ent * 16), sum(cyc) / max(sum(tick), 1) / 10.0, (max(st) - min(st)) / 100.0)
                     eng.close()
