@@ -25,6 +25,7 @@
 //   grid      = (groups) x (output tiles), group-major, cut into 8 equal contiguous chunks, one per XCD: the
 //               output tiles of a group re-read the same taps, which then stay in that XCD's L2.
 #include "xl_dev_inline.h"
+#include "xl_chain_plan.h"
 
 #include <hip/hip_ext.h>
 
@@ -139,45 +140,30 @@ XL_DEV uint32_t xl_chain_event(uint32_t ev) {
 #define XLC_MUL "v_pk_mul_f32 %[t1], %[p], %[inc] op_sel_hi:[1,0]\n\tv_pk_mul_f32 %[t2], %[p], %[inc] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
 #define XLC_ADD "v_pk_add_f32 %[p], %[t1], %[t2] op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]\n\t"
 #define XLC_STEP XLC_MUL XLC_ADD
-#define XLC_ENTRY                                                       \
-  XLC_MUL "ds_write_b64 %[addr], %[p]\n\t" XLC_ADD                      \
-  XLC_MUL "v_add_u32 %[cnt], 1, %[cnt]\n\t" XLC_ADD                     \
-  XLC_MUL "ds_write_b32 %[paddr], %[cnt]\n\t" XLC_ADD                   \
-  XLC_MUL "v_add_u32 %[off], 0x200, %[off]\n\t" XLC_ADD                 \
-  XLC_MUL "v_and_b32 %[off], 0x7fff, %[off]\n\t" XLC_ADD                \
-  XLC_MUL "v_add_u32 %[addr], %[off], %[base]\n\t" XLC_ADD              \
-  XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP
-// Four consecutive entries whose ring slots do not wrap (entry index = 0 mod 4): the slots are addressed with immediate
-// offsets, the ring address is advanced once per four entries, and the loop around it closes once per 64 steps.
+// One entry that may sit in ANY ring slot, as the body of a counted loop that stays inside one asm block (the head and the
+// tail of a region, xl_chain_plan.h): it carries its own ring address ((offset + 512) mod 32 KB + base), posts its count and
+// holds its exit test, all in the shadows of its first steps; [todo] counts the entries still wanted (>= 1 on entry).  The
+// 4-byte instructions come in pairs, in the two shadows of one step, so that the 8-byte ones after them stay on 8-byte boundaries.
+#define XLC_STEP2(I1, I2) XLC_MUL I1 "\n\t" XLC_ADD I2 "\n\t"
 #define XLC_STEPS10 XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP
+#define XLC_ANY_LOOP                                                                       \
+  "1:\n\t" XLC_MUL "ds_write_b64 %[addr], %[p]\n\t" XLC_ADD                               \
+  XLC_STEP2("v_add_u32 %[cnt], 1, %[cnt]", "s_sub_u32 %[todo], %[todo], 1")               \
+  XLC_MUL "ds_write_b32 %[paddr], %[cnt]\n\t" XLC_ADD                                     \
+  XLC_MUL "v_add_u32 %[off], 0x200, %[off]\n\t" XLC_ADD                                   \
+  XLC_MUL "v_and_b32 %[off], 0x7fff, %[off]\n\t" XLC_ADD                                  \
+  XLC_STEP2("v_add_u32 %[addr], %[off], %[base]", "s_cmp_lg_u32 %[todo], 0")              \
+  XLC_STEPS10 "s_cbranch_scc1 1b\n\t"
+// [todo] plain steps and nothing else (the entry that holds a block end: the steps before and after the renormalisation)
+#define XLC_STEP_LOOP "1:\n\t" XLC_STEP2("s_sub_u32 %[todo], %[todo], 1", "s_cmp_lg_u32 %[todo], 0") "s_cbranch_scc1 1b\n\t"
+// A whole entry without bookkeeping, the ring slot at an immediate offset: 16 steps (the entry's phase goes into the ring in
+// the shadow of the first).  Entry count and ring address are advanced once per block of entries: the drainers take the entries
+// in pairs and are a few entries behind anyway; fewer instructions in the chain wave is what counts -- each one outside a wait
+// costs ~3.6 cycles.
 #define XLC_QENTRY(OFFS) XLC_MUL "ds_write_b64 %[addr], %[p] offset:" OFFS "\n\t" XLC_ADD XLC_STEP XLC_STEP
-// (the entry count is posted once per block of entries: the drainers take the entries in pairs and are a few entries
-// behind anyway; fewer instructions in the chain wave is what counts -- each one outside a wait costs ~3.6 cycles)
-#define XLC_BLOCK_END(N, ADV)                                           \
-  XLC_MUL "v_add_u32 %[cnt], " N ", %[cnt]\n\t" XLC_ADD                 \
-  XLC_MUL "ds_write_b32 %[paddr], %[cnt]\n\t" XLC_ADD                   \
-  XLC_MUL "v_add_u32 %[off], " ADV ", %[off]\n\t" XLC_ADD               \
-  XLC_MUL "v_and_b32 %[off], 0x7fff, %[off]\n\t" XLC_ADD                \
-  XLC_MUL "v_add_u32 %[addr], %[off], %[base]\n\t" XLC_ADD XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP
-#define XLC_QUAD                                                        \
-  XLC_QENTRY("0") XLC_STEP XLC_STEP XLC_STEP XLC_STEPS10                \
-  XLC_QENTRY("512") XLC_STEP XLC_STEP XLC_STEP XLC_STEPS10              \
-  XLC_QENTRY("1024") XLC_STEP XLC_STEP XLC_STEP XLC_STEPS10             \
-  XLC_MUL "ds_write_b64 %[addr], %[p] offset:1536\n\t" XLC_ADD XLC_BLOCK_END("4", "0x800")
-// a whole entry without bookkeeping: 16 steps, the ring slot at an immediate offset
 #define XLC_E(OFFS) XLC_QENTRY(OFFS) XLC_STEP XLC_STEP XLC_STEP XLC_STEPS10
-// eight / sixteen / thirty-two entries (entry index = 0 mod 8 / 16 / 32): straight-line code, 13 instructions of
-// bookkeeping per block.  Longer blocks are faster -- measured cycles per step: single entries 19.7, blocks of four 19.2,
-// of eight 16.7: fewer extra instructions and fewer taken branches (a lone wave pays each refetch in full).
 #define XLC_E7(B0, B1, B2, B3, B4, B5, B6) XLC_E(B0) XLC_E(B1) XLC_E(B2) XLC_E(B3) XLC_E(B4) XLC_E(B5) XLC_E(B6)
 #define XLC_E8(B0, B1, B2, B3, B4, B5, B6, B7) XLC_E7(B0, B1, B2, B3, B4, B5, B6) XLC_E(B7)
-#define XLC_OCT                                                         \
-  XLC_E7("0", "512", "1024", "1536", "2048", "2560", "3072")           \
-  XLC_MUL "ds_write_b64 %[addr], %[p] offset:3584\n\t" XLC_ADD XLC_BLOCK_END("8", "0x1000")
-#define XLC_HEX                                                         \
-  XLC_E8("0", "512", "1024", "1536", "2048", "2560", "3072", "3584")   \
-  XLC_E7("4096", "4608", "5120", "5632", "6144", "6656", "7168")       \
-  XLC_MUL "ds_write_b64 %[addr], %[p] offset:7680\n\t" XLC_ADD XLC_BLOCK_END("16", "0x2000")
 // The 32-entry block is the body of a loop that stays inside one asm block: the code between two asm blocks -- choosing the
 // next block, its ring address, the drain check -- is a few dozen scalar instructions and taken branches, and a lone wave pays
 // each in full (measured, profiles/chain_nonstep_time.txt: ~1400 cycles per 32 entries against ~7100 for the block itself).
@@ -188,7 +174,6 @@ XL_DEV uint32_t xl_chain_event(uint32_t ev) {
 // ([sm] = the minimum it saw).  The 4-byte instructions come in pairs, in the two shadows of one step, so that the 8-byte ones
 // after them stay on 8-byte boundaries.  (Shadows are not free for everything: 32 entries that each carry their own ring
 // address, count and exit test -- one asm block for any region, no alignment -- ran at 17.0 cycles per step against 13.9.)
-#define XLC_STEP2(I1, I2) XLC_MUL I1 "\n\t" XLC_ADD I2 "\n\t"
 #define XLC_B32_LOOP                                                                                         \
   XLC_E8("0", "512", "1024", "1536", "2048", "2560", "3072", "3584")                                       \
   XLC_E8("4096", "4608", "5120", "5632", "6144", "6656", "7168", "7680")                                   \
@@ -209,7 +194,7 @@ XL_DEV uint32_t xl_chain_event(uint32_t ev) {
   XLC_STEP2("v_readfirstlane_b32 %[sm], %[mn]", "s_nop 0")                                                  \
   XLC_STEP2("s_cmp_ge_u32 %[sm], %[need]", "s_cselect_b32 %[st], %[todo], 0")                               \
   XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP XLC_STEP
-static_assert(XL_PH_STRIDE == 16u && XLC_RING * 64u * 8u == 0x8000u, "XLC_ENTRY is written for 16 steps per entry and a 32 KB ring");
+static_assert(XL_PH_STRIDE == 16u && XLC_RING * 64u * 8u == 0x8000u, "the chain wave's asm blocks are written for 16 steps per entry and a 32 KB ring");
 
 // One launch tabulates `calls.n` consecutive calls of the same shape (pos, then xl_grid_next of it, ...): table and final
 // phases per call -- the launch's fixed costs (~11 us of prologue / epilogue, ~6 us between two dependent launches) are paid
@@ -274,59 +259,58 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
                                                     // step of an -mfma reference build takes the per-step path throughout)
         const unsigned long long r0 = stats ? clock64() : 0ull;
         if ((e << XL_PH_SHIFT) < K) {  // (a lane whose call has ended sits the region out; the others' mask is constant in it)
+          // head of single entries up to the next 32-entry boundary of the ring, 32-entry blocks, tail of single entries
+          // (xl_chain_plan.h): three asm blocks per region at the most, nothing climbs and nothing is chosen in between
+          const XlChainPlan pl = xl_chain_plan(e, e_stop, XLC_RING, 32u);
           uint32_t ee = e;
-          while (ee < e_stop) {
-            // the longest block that ends by e_stop and does not run over the end of the ring (its slots are addressed with
-            // immediate offsets): no climb through the shorter ones after an event
-            const uint32_t left = e_stop - ee, slot = ee & (XLC_RING - 1u), room = XLC_RING - slot;
-            const uint32_t fit = left < room ? left : room;
-            const uint32_t nn = fit >= 32u ? 32u : fit >= 16u ? 16u : fit >= 8u ? 8u : fit >= 4u ? 4u : 1u;
-            if (ee + nn > lim) {
+          v2f t1, t2;
+          // a run of N any-slot entries from ee on (N < 32 and the ring holds 64: one drain check covers the run, the loop needs no poll)
+#define XLC_ANY_RUN(N)                                                                                                       \
+  if ((N) != 0u) {                                                                                                           \
+    uint32_t todo = (N);                                                                                                     \
+    if (ee + todo > lim) {                                                                                                   \
+      const unsigned long long d0 = stats ? clock64() : 0ull;                                                                \
+      lim = xl_chain_wait_drained(ee + todo, a_n0, a_n1, a_n2);                                                              \
+      if (stats) t_drain += clock64() - d0, ++n_drain;                                                                       \
+    }                                                                                                                        \
+    uint32_t off = ((ee & (XLC_RING - 1u)) << 9) + lane * (uint32_t)sizeof(v2f); /* ring offset of entry ee, this lane */    \
+    uint32_t addr = a_ring0 + off, cnt = ee;                                                                                 \
+    ee += todo;                                                                                                              \
+    asm volatile(XLC_ALIGN XLC_ANY_LOOP                                                                                      \
+                 : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2),         \
+                   [todo] "+s"(todo)                                                                                         \
+                 : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod)                                                  \
+                 : "memory", "scc");                                                                                         \
+  }
+          XLC_ANY_RUN(pl.head);
+          // 32-entry blocks back to back inside one asm block while the drainers keep up (a block that starts at a multiple
+          // of 32 ends where the next one may start); the drainers' counters are read during each block and weighed at its end
+          for (uint32_t want = pl.blocks; want != 0u;) {
+            if (ee + 32u > lim) {
               const unsigned long long d0 = stats ? clock64() : 0ull;
-              lim = xl_chain_wait_drained(ee + nn, a_n0, a_n1, a_n2);
+              lim = xl_chain_wait_drained(ee + 32u, a_n0, a_n1, a_n2);
               if (stats) t_drain += clock64() - d0, ++n_drain;
             }
-            uint32_t off = (slot << 9) + lane * (uint32_t)sizeof(v2f);  // ring offset of entry ee, this lane
+            uint32_t off = ((ee & (XLC_RING - 1u)) << 9) + lane * (uint32_t)sizeof(v2f);
             uint32_t addr = a_ring0 + off, cnt = ee;
-            v2f t1, t2;
-#define XLC_RUN(BLOCK)                                                                                            \
-  asm volatile(XLC_ALIGN BLOCK                                                                                   \
-               : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2) \
-               : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod)                                        \
-               : "memory")
-            if (nn == 32u) {
-              // 32-entry blocks back to back inside one asm block while the drainers keep up (a block that starts at a multiple
-              // of 32 ends where the next one may start); the drainers' counters are read during each block and weighed at its end
-              const uint32_t want = (slot & 31u) == 0u ? left >> 5 : 1u;
-              // need: the block adds 16 before it compares, so it starts one block short -- below zero (wraps, on purpose) while
-              // ee < 32.  For a lone block (want == 1) the comparison decides nothing: todo is 0 by then.
-              uint32_t todo = want, need = (ee >> 1) - 16u, mn, n1, n2, sm, st;
-              const unsigned long long b0 = stats ? clock64() : 0ull;
-              asm volatile(XLC_ALIGN "1:\n\t" XLC_B32_LOOP "s_cmp_lg_u32 %[st], 0\n\ts_cbranch_scc1 1b\n\t"
-                           : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2),
-                             [mn] "=&v"(mn), [n1] "=&v"(n1), [n2] "=&v"(n2), [todo] "+s"(todo), [need] "+s"(need), [sm] "=&s"(sm),
-                             [st] "=&s"(st)
-                           : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod), [an0] "v"(a_n0), [an1] "v"(a_n1), [an2] "v"(a_n2)
-                           : "memory", "scc");
-              const uint32_t ran = (want - todo) << 5;
-              if (stats) t_b32 += clock64() - b0, n_b32 += ran, ++n_runs;
-              lim = xl_chain_lim(sm);
-              ee += ran;
-            } else if (nn == 16u) {
-              XLC_RUN(XLC_HEX);
-              ee += 16u;
-            } else if (nn == 8u) {
-              XLC_RUN(XLC_OCT);
-              ee += 8u;
-            } else if (nn == 4u) {
-              XLC_RUN(XLC_QUAD);
-              ee += 4u;
-            } else {
-              XLC_RUN(XLC_ENTRY);
-              ee += 1u;
-            }
-#undef XLC_RUN
+            // need: the block adds 16 before it compares, so it starts one block short -- below zero (wraps, on purpose) while
+            // ee < 32.  For the last block wanted the comparison decides nothing: todo is 0 by then.
+            uint32_t left = want, need = (ee >> 1) - 16u, mn, n1, n2, sm, st;
+            const unsigned long long b0 = stats ? clock64() : 0ull;
+            asm volatile(XLC_ALIGN "1:\n\t" XLC_B32_LOOP "s_cmp_lg_u32 %[st], 0\n\ts_cbranch_scc1 1b\n\t"
+                         : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2),
+                           [mn] "=&v"(mn), [n1] "=&v"(n1), [n2] "=&v"(n2), [todo] "+s"(left), [need] "+s"(need), [sm] "=&s"(sm),
+                           [st] "=&s"(st)
+                         : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod), [an0] "v"(a_n0), [an1] "v"(a_n1), [an2] "v"(a_n2)
+                         : "memory", "scc");
+            const uint32_t ran = (want - left) << 5;
+            if (stats) t_b32 += clock64() - b0, n_b32 += ran, ++n_runs;
+            lim = xl_chain_lim(sm);
+            ee += ran;
+            want = left;
           }
+          XLC_ANY_RUN(pl.tail);
+#undef XLC_ANY_RUN
         }
         if (e_stop > e) e = e_stop;
         if (stats) t_region += clock64() - r0, ++n_event;
@@ -336,7 +320,32 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
           const uint32_t m0 = e << XL_PH_SHIFT;
           if (m0 < K) xl_lds_post64(a_ring + (e & (XLC_RING - 1u)) * 64u * (uint32_t)sizeof(v2f), p);
           xl_lds_post(a_prod, e + 1u);
-          for (uint32_t m = m0; m < m0 + XL_PH_STRIDE && m < K; ++m) {
+          uint32_t m = m0;
+          // Every lane still in the call has the same block end in this entry and the whole entry to step (clients that joined
+          // together; not the FMA step): the hand-scheduled step up to the block end, the renormalisation, the step again to the
+          // end of the entry.  Lanes that disagree, the call's last partial entry and a second block end in the same entry take
+          // the per-step loop below (from the start, or from wherever the counted steps stopped).
+          if (!(pos.pad & XL_POS_FMA_STEP) && evs - m0 - 1u < XL_PH_STRIDE &&
+              __ballot(m0 < K && (nb != evs || m0 + XL_PH_STRIDE > K)) == 0ull && m0 < K) {
+            v2f t1, t2;
+            uint32_t todo = evs - m0;  // (1 .. 16)
+            asm volatile(XLC_ALIGN XLC_STEP_LOOP
+                         : [p] "+v"(p), [t1] "=&v"(t1), [t2] "=&v"(t2), [todo] "+s"(todo)
+                         : [inc] "v"(inc)
+                         : "scc");
+            p = xl_nco_renorm(p);
+            nb = xl_bnd_next(bnd, evs);
+            m = evs;
+            todo = m0 + XL_PH_STRIDE - evs;
+            if (todo != 0u && __ballot(nb <= m0 + XL_PH_STRIDE) == 0ull) {
+              asm volatile(XLC_ALIGN XLC_STEP_LOOP
+                           : [p] "+v"(p), [t1] "=&v"(t1), [t2] "=&v"(t2), [todo] "+s"(todo)
+                           : [inc] "v"(inc)
+                           : "scc");
+              m = m0 + XL_PH_STRIDE;
+            }
+          }
+          for (; m < m0 + XL_PH_STRIDE && m < K; ++m) {
             p = xl_nco_next_any(p, inc, bnd.flags);
             if (m + 1u == nb) {
               p = xl_nco_renorm(p);
