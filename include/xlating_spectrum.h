@@ -26,12 +26,21 @@ extern "C" {
 enum { XLATING_SPECTRUM_CU8 = 0, XLATING_SPECTRUM_CS16 = 2, XLATING_SPECTRUM_CF32 = 3 };
 
 #define XLATING_SPECTRUM_MAX_WIDTH 8192
+#define XLATING_SPECTRUM_MAX_WIDE_WIDTH 1048576
 
 typedef struct xlating_spectrum xlating_spectrum;
 
 /* 0 on success.  -EINVAL: width <= 0, width > XLATING_SPECTRUM_MAX_WIDTH, sampling_rate == 0, width > sampling_rate, an unknown
  * format or out == NULL.  -ENODEV (with a "<3>" line on stderr): no usable HIP device -- there is no CPU path.  -ENOMEM. */
 int xlating_spectrum_create(uint32_t sampling_rate, int width, int format, xlating_spectrum **out);
+
+/* The same with the cap at XLATING_SPECTRUM_MAX_WIDE_WIDTH: the same checks in the same order with the same return values, every
+ * -EINVAL decided before the device is touched.  The object is fed, read and destroyed with the functions below.  Up to
+ * XLATING_SPECTRUM_MAX_WIDTH it is the very object xlating_spectrum_create builds (same kernels, bit-identical rows).  A wider one
+ * runs each transform in two levels across workgroups, through a scratch buffer in device memory (64 MiB), and keeps `width`-sized
+ * row buffers: at width 1048576 about 160 MiB of device and 60 MiB of pinned host memory.  Everything above about rows, their
+ * completion and splits holds. */
+int xlating_spectrum_create_wide(uint32_t sampling_rate, int width, int format, xlating_spectrum **out);
 
 /* Consume n samples (complex samples: n * 2 bytes of cu8, n * 4 of cs16, n * 8 of cf32) from host memory.  The caller's buffer is
  * copied before the call returns.  0, or a negative errno (-EIO after a HIP failure; the object is then unusable). */
@@ -60,7 +69,7 @@ void xlating_spectrum_destroy(xlating_spectrum *s);
  */
 typedef struct xlating_spectrum_bank xlating_spectrum_bank;
 
-/* width and format as xlating_spectrum_create.  0, -EINVAL, -ENODEV (with a "<3>" line on stderr), -ENOMEM. */
+/* width (1 .. XLATING_SPECTRUM_MAX_WIDTH: the bank has no wide entry) and format as xlating_spectrum_create.  0, -EINVAL, -ENODEV (with a "<3>" line on stderr), -ENOMEM. */
 int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out);
 
 /* A new stream whose sample 0 is the first sample it is fed.  Returns its stream id >= 0 (ids of removed streams are reused), -EINVAL

@@ -744,6 +744,7 @@ def wire_resample_taps(req, rs, lpf_cutoff_rate=5):
 # ------------------------------------------------------------------------------------------------- spectrogram (libxlating_spectrum.so)
 SPECTRUM_SYMBOLS = ["xlating_spectrum_create", "xlating_spectrum_feed_host", "xlating_spectrum_feed_device", "xlating_spectrum_take_rows",
                     "xlating_spectrum_destroy", "spectrogram_main", "spectrogram_sighandler",
+                    "xlating_spectrum_create_wide", "spectrogram_main_wide",
                     "xlating_spectrum_bank_create", "xlating_spectrum_bank_add", "xlating_spectrum_bank_remove",
                     "xlating_spectrum_bank_feed_device", "xlating_spectrum_bank_take_rows", "xlating_spectrum_bank_rows_pending",
                     "xlating_spectrum_bank_last_feed_ops", "xlating_spectrum_bank_destroy"]
@@ -768,6 +769,8 @@ def spectrum_lib():
     S = C.CDLL(path)
     S.xlating_spectrum_create.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     S.xlating_spectrum_create.restype = C.c_int
+    S.xlating_spectrum_create_wide.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    S.xlating_spectrum_create_wide.restype = C.c_int
     S.xlating_spectrum_feed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     S.xlating_spectrum_feed_host.restype = C.c_int
     S.xlating_spectrum_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -778,6 +781,8 @@ def spectrum_lib():
     S.xlating_spectrum_destroy.restype = None
     S.spectrogram_main.argtypes = [C.c_void_p]
     S.spectrogram_main.restype = C.c_int
+    S.spectrogram_main_wide.argtypes = [C.c_void_p]
+    S.spectrogram_main_wide.restype = C.c_int
     S.xlating_spectrum_bank_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     S.xlating_spectrum_bank_create.restype = C.c_int
     S.xlating_spectrum_bank_add.argtypes = [C.c_void_p, C.c_uint32]
@@ -799,16 +804,18 @@ def spectrum_lib():
 
 
 class Spectrum:
-    """One `xlating_spectrum *` (include/xlating_spectrum.h): feed samples in pieces, take completed waterfall rows."""
+    """One `xlating_spectrum *` (include/xlating_spectrum.h): feed samples in pieces, take completed waterfall rows.
+    wide=True creates it with xlating_spectrum_create_wide: widths up to 1048576 instead of 8192."""
 
-    def __init__(self, sampling_rate, width, fmt="cu8"):
+    def __init__(self, sampling_rate, width, fmt="cu8", wide=False):
         S = spectrum_lib()
+        name = "xlating_spectrum_create_wide" if wide else "xlating_spectrum_create"
         if fmt not in SPECTRUM_FMT:
-            raise XlatingError("xlating_spectrum_create", -22)
+            raise XlatingError(name, -22)
         h = C.c_void_p()
-        code = S.xlating_spectrum_create(sampling_rate, width, SPECTRUM_FMT[fmt], C.byref(h))
+        code = getattr(S, name)(sampling_rate, width, SPECTRUM_FMT[fmt], C.byref(h))
         if code != 0:
-            raise XlatingError("xlating_spectrum_create", code)
+            raise XlatingError(name, code)
         self.h, self.W, self.fmt = h, width, fmt
 
     def feed(self, x, n=None, stream=0):
@@ -826,7 +833,7 @@ class Spectrum:
         """-> (db float32 [R, W], pixels uint8 [R, W]): every completed row not taken yet, oldest first."""
         S, parts_db, parts_px = spectrum_lib(), [], []
         while True:
-            n = 256
+            n = max(4, min(256, (1 << 26) // self.W))  # (256 rows a round up to width 262144; fewer of a wider row)
             db = np.empty((n, self.W), np.float32)
             px = np.empty((n, self.W), np.uint8)
             got = S.xlating_spectrum_take_rows(self.h, db.ctypes.data, px.ctypes.data, min(n, max_rows))
@@ -946,11 +953,13 @@ class SpectrogramRequest(C.Structure):
                 ("output_file", C.c_char_p), ("fftw_flags", C.c_char_p), ("xl_private", C.c_void_p * 6)]
 
 
-def spectrogram_main(input_file, output_file, width=1024, sampling_rate=48000, data_format="cu8", fftw_flags="FFTW_MEASURE"):
-    """spectrogram_main() of include/spectrogram.h -> its return code.  None leaves a pointer field NULL."""
+def spectrogram_main(input_file, output_file, width=1024, sampling_rate=48000, data_format="cu8", fftw_flags="FFTW_MEASURE", wide=False):
+    """spectrogram_main() of include/spectrogram.h (wide=True: spectrogram_main_wide()) -> its return code.  None leaves a pointer
+    field NULL."""
     enc = lambda v: None if v is None else str(v).encode()  # noqa: E731
     req = SpectrogramRequest(sampling_rate, width, enc(data_format), enc(input_file), enc(output_file), enc(fftw_flags))
-    return spectrum_lib().spectrogram_main(C.byref(req))
+    S = spectrum_lib()
+    return (S.spectrogram_main_wide if wide else S.spectrogram_main)(C.byref(req))
 
 
 # ------------------------------------------------------------------------------------------------- resampler bank (libxlating_resample.so)

@@ -1,4 +1,4 @@
-// xl_spectrogram.cpp -- spectrogram_main (include/spectrogram.h): file -> streaming core -> PNG.  Reference behaviour:
+// xl_spectrogram.cpp -- spectrogram_main and spectrogram_main_wide (include/spectrogram.h): file -> streaming core -> PNG.  Reference behaviour:
 // src/spectrogram/spectrogram.c:55-168 (checks, rows), iq_file.c (formats, sample count), png_util.c (8-bit gray, one row per row).
 //
 // Order: the request is checked and the input opened and counted before the device is touched, so that every refusal is the
@@ -200,7 +200,8 @@ void reader_loop(Reader &R, Input &in, uint64_t total, size_t chunk, uint32_t ss
 
 }  // namespace
 
-extern "C" int spectrogram_main(spectrogram *req) {
+// spectrogram_main (max_width 8192, xlating_spectrum_create) and spectrogram_main_wide (1048576, xlating_spectrum_create_wide)
+static int spectrogram_run(spectrogram *req, const int max_width) {
   // spectrogram.c:56-82, in its order
   if (req->input_file == nullptr) {
     fprintf(stderr, "missing input file (-i)\n");
@@ -222,8 +223,8 @@ extern "C" int spectrogram_main(spectrogram *req) {
     fprintf(stderr, "width (-w) %d exceeds the sampling rate %u\n", req->width, req->sampling_rate);
     return -EINVAL;
   }
-  if (req->width > XLATING_SPECTRUM_MAX_WIDTH) {
-    fprintf(stderr, "width (-w) %d exceeds the largest supported width %d\n", req->width, XLATING_SPECTRUM_MAX_WIDTH);
+  if (req->width > max_width) {
+    fprintf(stderr, "width (-w) %d exceeds the largest supported width %d\n", req->width, max_width);
     return -EINVAL;
   }
   // iq_file.c:13-33: the format, then the input
@@ -257,7 +258,8 @@ extern "C" int spectrogram_main(spectrogram *req) {
 
   // the device
   xlating_spectrum *s = nullptr;
-  int rc = xlating_spectrum_create(req->sampling_rate, req->width, fmt, &s);
+  int rc = max_width > XLATING_SPECTRUM_MAX_WIDTH ? xlating_spectrum_create_wide(req->sampling_rate, req->width, fmt, &s)
+                                                  : xlating_spectrum_create(req->sampling_rate, req->width, fmt, &s);
   if (rc != 0) return rc;
   Png png;
   png.fp = fopen(req->output_file, "wb");
@@ -311,3 +313,7 @@ extern "C" int spectrogram_main(spectrogram *req) {
   // (a short or interrupted input leaves fewer rows than IHDR announces, as the reference's png_write_end does)
   return png.end();
 }
+
+extern "C" int spectrogram_main(spectrogram *req) { return spectrogram_run(req, XLATING_SPECTRUM_MAX_WIDTH); }
+
+extern "C" int spectrogram_main_wide(spectrogram *req) { return spectrogram_run(req, XLATING_SPECTRUM_MAX_WIDE_WIDTH); }

@@ -9,6 +9,9 @@
 // are never transformed.  Every row whose F-th transform is in gets one finishing launch (dB, shift, pixel into d_db / d_px of its
 // slot) and a copy into the pinned host ring; take_rows waits for the latest feed.
 // Any split gives bit-identical rows: every transform sees the same samples and the same code, and max is exact.
+// An object of xlating_spectrum_create_wide with a width above 8192 differs in two places only: "launch the transforms of this span"
+// goes to the two-level transform (xl_spectrum_wide.hip) in chunks of what its scratch buffer holds, and the finishing launch is
+// that file's (a plain width's reads the row pass's bin order).  The cut, the carry, the row ring and the copies are the same.
 #include "../../include/xlating_spectrum.h"
 
 #include <errno.h>
@@ -26,6 +29,7 @@
 #include "xl_spectrum.h"
 #include "xl_spectrum_core.h"
 #include "xl_spectrum_cut.h"
+#include "xl_spectrum_wide_plan.h"
 
 struct xlating_spectrum : XlSpecSetup {
   uint32_t sr = 0, F = 0;
@@ -43,6 +47,10 @@ struct xlating_spectrum : XlSpecSetup {
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   bool stage_used[2] = {false, false};
   int stage_i = 0;
+  // a width above XL_SPEC_MAX_W: the two-level transform's scratch ([transform][k1][j2]) and how many transforms it holds
+  bool wide = false;
+  float2 *d_scratch = nullptr;
+  uint32_t scratch_T = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------------- host tables (double)
@@ -63,6 +71,74 @@ static void xl_fft_double(std::vector<std::complex<double>> &a) {  // in-place r
         a[i + k] = u + v;
         a[i + k + len / 2] = u - v;
       }
+}
+
+// the same with the twiddles from a table w[m] = exp(-2 pi i m / n): the wide widths' lengths (2^15 .. 2^21), where a cos and a sin per
+// butterfly would take seconds
+static void xl_fft_double_tab(std::vector<std::complex<double>> &a, const std::vector<std::complex<double>> &w) {
+  const size_t n = a.size();
+  for (size_t i = 1, j = 0; i < n; ++i) {
+    size_t bit = n >> 1;
+    for (; j & bit; bit >>= 1) j ^= bit;
+    j ^= bit;
+    if (i < j) std::swap(a[i], a[j]);
+  }
+  for (size_t len = 2; len <= n; len <<= 1)
+    for (size_t i = 0; i < n; i += len)
+      for (size_t k = 0; k < len / 2; ++k) {
+        const std::complex<double> u = a[i + k], v = a[i + k + len / 2] * w[k * (n / len)];
+        a[i + k] = u + v;
+        a[i + k + len / 2] = u - v;
+      }
+}
+
+static int xl_spec_upload(const std::vector<float2> &h, float2 **d) {
+  XL_SPEC_TRY(hipMalloc(d, sizeof(float2) * h.size()));
+  XL_SPEC_TRY(hipMemcpy(*d, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice));
+  return 0;
+}
+
+static std::vector<float2> xl_spec_twiddles(uint32_t n) {
+  std::vector<float2> tw(n);
+  for (uint32_t m = 0; m < n; ++m) {
+    const double ang = -2.0 * M_PI * (double)m / (double)n;
+    tw[m] = make_float2((float)cos(ang), (float)sin(ang));
+  }
+  return tw;
+}
+
+// A wide width's tables: the N-point twiddles (one rounding each: what the column passes multiply by between the levels), the two
+// levels' own twiddles, and for Bluestein the chirp and the chirp filter's spectrum over L = N, times 1 / L, in the order the row pass
+// reads it: Bs[k1 + N1 k2] at [k1 * N2 + k2].
+static int xl_spec_tables_wide(XlSpecSetup *u) {
+  const uint32_t W = u->W, N = u->N, N1 = u->N1, N2 = u->N2;
+  std::vector<std::complex<double>> w(N);
+  std::vector<float2> tw(N);
+  for (uint32_t m = 0; m < N; ++m) {
+    const double ang = -2.0 * M_PI * (double)m / (double)N;
+    w[m] = std::complex<double>(cos(ang), sin(ang));
+    tw[m] = make_float2((float)w[m].real(), (float)w[m].imag());
+  }
+  int rc = xl_spec_upload(tw, &u->d_tw);
+  if (rc == 0) rc = xl_spec_upload(xl_spec_twiddles(N1), &u->d_tw1);
+  if (rc == 0) rc = xl_spec_upload(xl_spec_twiddles(N2), &u->d_tw2);
+  if (rc != 0 || !u->blue) return rc;
+  std::vector<std::complex<double>> b(N, 0.0);
+  std::vector<float2> ch(W), bs(N);
+  for (uint32_t n = 0; n < W; ++n) {
+    const uint64_t q = (uint64_t)n * n % (2ull * W);
+    const double ang = -M_PI * (double)q / (double)W;
+    const std::complex<double> c(cos(ang), sin(ang));
+    ch[n] = make_float2((float)c.real(), (float)c.imag());
+    b[n] = std::conj(c);
+    if (n > 0) b[N - n] = std::conj(c);
+  }
+  xl_fft_double_tab(b, w);
+  for (uint32_t k = 0; k < N; ++k)
+    bs[(size_t)xl_specw_bin_pos(N1, N2, k)] = make_float2((float)(b[k].real() / N), (float)(b[k].imag() / N));
+  rc = xl_spec_upload(ch, &u->d_chirp);
+  if (rc == 0) rc = xl_spec_upload(bs, &u->d_bspec);
+  return rc;
 }
 
 static int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, float2 **d_chirp, float2 **d_bspec) {
@@ -94,8 +170,8 @@ static int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, floa
   return 0;
 }
 
-int xl_spec_setup_init(XlSpecSetup *u, int width, int format, const char *who) {
-  if (width <= 0 || width > XLATING_SPECTRUM_MAX_WIDTH ||
+int xl_spec_setup_init(XlSpecSetup *u, int width, int max_width, int format, const char *who) {
+  if (width <= 0 || width > max_width ||
       (format != XLATING_SPECTRUM_CU8 && format != XLATING_SPECTRUM_CS16 && format != XLATING_SPECTRUM_CF32))
     return -EINVAL;
   u->device = xl_hip_select_device(-1);
@@ -116,7 +192,15 @@ int xl_spec_setup_init(XlSpecSetup *u, int width, int format, const char *who) {
     XL_LOG_ERR("%s: %s", who, hipGetErrorString(e));
     return xl_errno_of_last_hip_error();
   }
-  const int rc = xl_spec_tables(u->W, u->N, u->blue, &u->d_tw, &u->d_chirp, &u->d_bspec);
+  int rc;
+  if (u->W > XL_SPEC_MAX_W) {
+    XlSpecWidePlan p;
+    if (xl_specw_plan(u->W, &p) != 0 || p.N != u->N) return -EINVAL;
+    u->N1 = p.N1, u->N2 = p.N2;
+    rc = xl_spec_tables_wide(u);
+  } else {
+    rc = xl_spec_tables(u->W, u->N, u->blue, &u->d_tw, &u->d_chirp, &u->d_bspec);
+  }
   if (rc != 0) xl_spec_setup_free(u);
   return rc;
 }
@@ -125,7 +209,9 @@ void xl_spec_setup_free(XlSpecSetup *u) {
   if (u->d_tw) (void)hipFree(u->d_tw);
   if (u->d_chirp) (void)hipFree(u->d_chirp);
   if (u->d_bspec) (void)hipFree(u->d_bspec);
-  u->d_tw = u->d_chirp = u->d_bspec = nullptr;
+  if (u->d_tw1) (void)hipFree(u->d_tw1);
+  if (u->d_tw2) (void)hipFree(u->d_tw2);
+  u->d_tw = u->d_chirp = u->d_bspec = u->d_tw1 = u->d_tw2 = nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------------------- row ring
@@ -190,7 +276,19 @@ static int xl_spec_launch_t(xlating_spectrum *s, const void *in, int64_t base, i
   XlSpecArgs a;
   a.in = in, a.base = base, a.g0 = g0, a.T = (uint32_t)T, a.F = s->F, a.sr = s->sr, a.W = s->W, a.cap = s->cap;
   a.rowmax = s->d_max, a.tw = s->d_tw, a.chirp = s->d_chirp, a.bspec = s->d_bspec, a.norm = 1.0f / (float)s->W;
-  XL_SPEC_TRY(xl_spec_launch(a, s->N, s->blue, s->fmt, st));
+  if (!s->wide) {
+    XL_SPEC_TRY(xl_spec_launch(a, s->N, s->blue, s->fmt, st));
+    return 0;
+  }
+  // the two-level transform, as many transforms at a time as the scratch holds (stream order keeps one chunk's passes and the next
+  // chunk's apart)
+  XlSpecWideArgs w;
+  w.scratch = s->d_scratch, w.tw1 = s->d_tw1, w.tw2 = s->d_tw2, w.N = s->N, w.N1 = s->N1, w.N2 = s->N2;
+  for (int64_t t = 0; t < T; t += s->scratch_T) {
+    w.a = a;
+    w.a.g0 = g0 + t, w.a.T = (uint32_t)std::min<int64_t>(s->scratch_T, T - t);
+    XL_SPEC_TRY(xl_specw_launch(w, s->blue, s->fmt, st));
+  }
   return 0;
 }
 
@@ -215,7 +313,10 @@ static int xl_spec_span(xlating_spectrum *s, const uint8_t *in, int64_t n, hipSt
   for (int64_t r = s->rows_finished; r < done;) {
     const int64_t slot = r % s->cap;
     const int64_t nr = std::min<int64_t>({done - r, (int64_t)s->cap - slot, 65535});
-    XL_SPEC_TRY(xl_spec_finish(s->d_max, s->d_db, s->d_px, s->W, s->cap, r, (uint32_t)nr, st));
+    if (s->wide)
+      XL_SPEC_TRY(xl_specw_finish(s->d_max, s->d_db, s->d_px, s->W, s->N1, s->N2, !s->blue, s->cap, r, (uint32_t)nr, st));
+    else
+      XL_SPEC_TRY(xl_spec_finish(s->d_max, s->d_db, s->d_px, s->W, s->cap, r, (uint32_t)nr, st));
     const size_t o = (size_t)slot * W;
     XL_SPEC_TRY(hipMemcpyAsync(s->h_db + o, s->d_db + o, sizeof(float) * W * nr, hipMemcpyDeviceToHost, st));
     XL_SPEC_TRY(hipMemcpyAsync(s->h_px + o, s->d_px + o, (size_t)(W * nr), hipMemcpyDeviceToHost, st));
@@ -243,10 +344,10 @@ static int xl_spec_end(xlating_spectrum *s, hipStream_t st, int rc) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- C API
-extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int format, xlating_spectrum **out) {
+static int xl_spectrum_create_cap(uint32_t sampling_rate, int width, int max_width, int format, xlating_spectrum **out, const char *who) {
   if (out == nullptr || sampling_rate == 0 || (int64_t)width > (int64_t)sampling_rate) return -EINVAL;
   XlSpecSetup u;
-  int rc = xl_spec_setup_init(&u, width, format, "xlating_spectrum_create");
+  int rc = xl_spec_setup_init(&u, width, max_width, format, who);
   if (rc == -EINVAL) return rc;  // (as the refusals above: *out is left alone)
   *out = nullptr;
   if (rc != 0) return rc;
@@ -270,9 +371,19 @@ extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int fo
     if (e == hipSuccess) e = hipMalloc(&s->d_stage[i], s->chunk * s->ssz);
   }
   if (e == hipSuccess) e = hipMalloc(&s->d_carry, (size_t)s->W * s->ssz);
+  if (s->W > XL_SPEC_MAX_W) {
+    uint64_t scratch = XL_SPECW_SCRATCH_DEFAULT;
+    if (const char *v = xl_exp_getenv("XL_EXP_SPEC_SCRATCH")) {  // test knob: the scratch buffer's size in bytes
+      const long long b = strtoll(v, nullptr, 10);
+      if (b > 0) scratch = (uint64_t)std::min<long long>(b, 1ll << 30);
+    }
+    s->wide = true;
+    s->scratch_T = (uint32_t)xl_specw_chunk(scratch, s->N);
+    if (e == hipSuccess) e = hipMalloc(&s->d_scratch, sizeof(float2) * (size_t)s->N * s->scratch_T);
+  }
   if (e != hipSuccess) {
     xl_last_hip_error = e;
-    XL_LOG_ERR("xlating_spectrum_create: %s", hipGetErrorString(e));
+    XL_LOG_ERR("%s: %s", who, hipGetErrorString(e));
     rc = xl_errno_of_last_hip_error();
   }
   // room for the rows one staging buffer can complete, and two more
@@ -283,6 +394,14 @@ extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int fo
   }
   *out = s;
   return 0;
+}
+
+extern "C" int xlating_spectrum_create(uint32_t sampling_rate, int width, int format, xlating_spectrum **out) {
+  return xl_spectrum_create_cap(sampling_rate, width, XLATING_SPECTRUM_MAX_WIDTH, format, out, "xlating_spectrum_create");
+}
+
+extern "C" int xlating_spectrum_create_wide(uint32_t sampling_rate, int width, int format, xlating_spectrum **out) {
+  return xl_spectrum_create_cap(sampling_rate, width, XLATING_SPECTRUM_MAX_WIDE_WIDTH, format, out, "xlating_spectrum_create_wide");
 }
 
 // host samples: through the two pinned staging buffers (or, pinned_src, straight from the caller's pinned memory, which it keeps
@@ -369,6 +488,7 @@ extern "C" void xlating_spectrum_destroy(xlating_spectrum *s) {
     if (s->stage_ev[i]) (void)hipEventDestroy(s->stage_ev[i]);
   }
   if (s->d_carry) (void)hipFree(s->d_carry);
+  if (s->d_scratch) (void)hipFree(s->d_scratch);
   xl_spec_setup_free(s);
   if (s->last) (void)hipEventDestroy(s->last);
   if (s->stream) (void)hipStreamDestroy(s->stream);

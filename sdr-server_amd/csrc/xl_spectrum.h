@@ -7,7 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define XL_SPEC_MAX_W 8192
+#define XL_SPEC_MAX_W 8192   // the one-workgroup kernels (xl_spectrum.hip); wider: the two-level transform (xl_spectrum_wide.hip)
 #define XL_SPEC_MAX_L 16384  // Bluestein length for W = 8191: the power of two >= 2 W - 1
 // samples of one stream that one cut (xl_spectrum_cut.h) may take -- a span of the single object's feed, a stream's count in a feed of the
 // bank: keeps every in-launch offset within 32 bits
@@ -41,6 +41,23 @@ int xl_spec_launch(const XlSpecArgs &a, uint32_t N, bool bluestein, int fmt, hip
 // db[slot * W ..] and W bytes to px[slot * W ..], and zeroes the slot's maxima for the row that reuses it.
 int xl_spec_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t cap, int64_t r0, uint32_t nrows, hipStream_t st);
 
+// The two-level transform of widths above XL_SPEC_MAX_W (xl_spectrum_wide.hip; the rules are xl_spectrum_wide_plan.h's): the same
+// transforms g0 .. g0 + T - 1 of the same stream, T at most what `scratch` holds ([transform][k1][j2], N float2 each).  Two launches
+// (plain) or three (Bluestein), stream-ordered, through the scratch.  A plain width leaves bin k1 + N1 k2 of a row at
+// rowmax[slot * W + k1 * N2 + k2]; Bluestein leaves bin k at rowmax[slot * W + k].
+struct XlSpecWideArgs {
+  XlSpecArgs a;          // tw: the N-point table (the twiddles between the two levels); bspec: Bluestein, in [k1][k2] order
+  float2 *scratch;
+  const float2 *tw1;     // N1-point twiddles
+  const float2 *tw2;     // N2-point twiddles
+  uint32_t N, N1, N2;
+};
+int xl_specw_launch(const XlSpecWideArgs &w, bool bluestein, int fmt, hipStream_t st);
+// xl_spec_finish for a wide object's rows: permuted (a plain width): column j reads its bin (the half swap first) from the row pass's
+// position; the dB is 10 * the correctly rounded log10f (xl_spectrum_wide.hip: xl_specw_db)
+int xl_specw_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t N1, uint32_t N2, bool permuted, uint32_t cap, int64_t r0,
+                    uint32_t nrows, hipStream_t st);
+
 // What a width and a format determine, the same for the single object and the bank: the transform length N (W for a power of two, else
 // the Bluestein L) and the tables on `device` (host, double, rounded to float): N-point twiddles, and for Bluestein the chirp and the chirp
 // filter's spectrum.
@@ -50,12 +67,16 @@ struct XlSpecSetup {
   bool blue = false;
   int device = 0;
   float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bspec = nullptr;
+  // a width above XL_SPEC_MAX_W (the single object's wide entry only): the split, the two levels' twiddles; d_bspec is in [k1][k2] order
+  uint32_t N1 = 0, N2 = 0;
+  float2 *d_tw1 = nullptr, *d_tw2 = nullptr;
 };
 
-// In this order: -EINVAL for a width outside 1 .. XLATING_SPECTRUM_MAX_WIDTH or an unknown format, before the device is touched; the
+// In this order: -EINVAL for a width outside 1 .. max_width (XLATING_SPECTRUM_MAX_WIDTH, or XLATING_SPECTRUM_MAX_WIDE_WIDTH from
+// xlating_spectrum_create_wide; the bank passes the former) or an unknown format, before the device is touched; the
 // device, -ENODEV with a "<3>" line that names `who` (the calling function) when there is none; N; the tables (-ENOMEM, -EIO).  The
 // device is left current.  A failed init leaves nothing to free.
-int xl_spec_setup_init(XlSpecSetup *u, int width, int format, const char *who);
+int xl_spec_setup_init(XlSpecSetup *u, int width, int max_width, int format, const char *who);
 void xl_spec_setup_free(XlSpecSetup *u);
 
 // (needs xl_common.h at the place of use)

@@ -358,7 +358,7 @@ static int xl_bank_feed(xlating_spectrum_bank *b, size_t n, const int *ids, cons
 extern "C" int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out) {
   if (out == nullptr) return -EINVAL;
   XlSpecSetup u;
-  int rc = xl_spec_setup_init(&u, width, format, "xlating_spectrum_bank_create");
+  int rc = xl_spec_setup_init(&u, width, XLATING_SPECTRUM_MAX_WIDTH, format, "xlating_spectrum_bank_create");
   if (rc == -EINVAL) return rc;  // (as the refusal above: *out is left alone)
   *out = nullptr;
   if (rc != 0) return rc;

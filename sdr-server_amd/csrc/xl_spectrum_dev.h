@@ -177,7 +177,7 @@ XL_DEV void xl_spec_finish_bin(uint32_t *rowmax, float *db, uint8_t *px, const u
   px[o + j] = xl_spec_pixel(d);
 }
 
-// The transform lengths that have kernels: powers of two 1 .. 8192 as they are, 8 .. 16384 as Bluestein lengths; the three sample formats.
+// The transform lengths that have one-workgroup kernels (widths 1 .. 8192; wider ones: xl_spectrum_wide.hip): powers of two 1 .. 8192 as they are, 8 .. 16384 as Bluestein lengths; the three sample formats.
 // launch(n, fmt, blue) gets them as std::integral_constants and enqueues its kernel<n, fmt, blue>.  0 or a hipError_t.
 template <uint32_t N, bool BLUE, class Launch>
 int xl_spec_dispatch_fmt(const int fmt, Launch &launch) {
