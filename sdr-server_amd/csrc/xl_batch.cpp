@@ -36,19 +36,18 @@
 #include <map>
 #include <new>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/xlating_batch.h"
 #include "xl_common.h"
 #include "xl_device.h"
 #include "xl_mixf_layout.h"
+#include "xl_plan.h"
 #include "xl_polyphase.h"
 #include "xl_taps.h"
 #include "xl_wide.h"
 #include "xl_xop_layout.h"
 
-#define XL_NLAUNCH 7
 #define XL_GROUP_MAX 64u  // most blocks per call
 
 namespace {
@@ -58,83 +57,6 @@ namespace {
 // readers ran while the previous launch was stepping -- the new launch never has to wait for them on a chain-bound engine.
 #define XL_NTAB (2 * XL_CHAIN_MAXCALLS)
 static inline int xl_nx(int i) { return (i + 1) % XL_NTAB; }
-
-struct Client {
-  bool alive = false;
-  uint32_t D = 0, T = 0, Tpad = 0;
-  std::vector<float> rt;  // [Tpad] interleaved re,im, zero padded
-  std::vector<int16_t> rtq;  // [T] the same taps in Q15 (xlating.c:486-487), interleaved re,im
-  float incr[2] = {1.0f, 0.0f};
-  int16_t qincr[2] = {0, 0};  // Q15 phase increment (xlating.c:548-549)
-  uint64_t consumed = 0;
-  uint32_t out_off = 0, out_cap = 0;  // the client's row in the output / phase-table images: assigned when it joins, kept for its lifetime
-  uint32_t row_len = 0;               // elements reserved for the row (out_cap rounded up to the table-entry pair)
-  uint64_t uid = 0;                   // unique over the engine's life (client ids are recycled, their taps are not)
-  uint32_t last_K = 0;
-  std::vector<uint32_t> last_Kg;  // outputs per block of the latest call
-  bool planned_mature = false;
-  bool wide = false;  // no LDS tile of the direct kernel fits its window image (xl_wide.h), or its window exceeds XL_HCAP: the wide kernel
-};
-
-// every window of the client's next outputs lies inside its own stream (no zeros below its join point are needed)
-static inline bool xl_mature(const Client &c) { return c.consumed >= (uint64_t)c.T - 1u; }
-
-struct DirectClass {
-  uint32_t D, T, rem0, hv0;
-  std::vector<int> members;
-};
-
-struct Launch {
-  int ct = 0;
-  int nw = XL_NW_DEFAULT;  // waves (tiles) per workgroup
-  uint32_t ota = 64;       // outputs per wave (smaller only when a 64-output window image exceeds the LDS)
-  std::vector<XlGroup> groups;
-  XlGroup *d_groups = nullptr;
-  size_t lds = 0;  // window image bytes of the launch (max over its groups)
-  uint32_t idle_waves = 0;  // spare waves over all groups (NCO rider slots per output tile)
-  bool all_wide = true;  // every group has an even decimation
-  uint32_t maxD = 1, minD = 0xFFFFFFFFu;
-};
-
-// A class of clients evaluated by the polyphase overlap-save path (xl_polyphase.hip) in optimized mode: all mature
-// clients of one (D, T), whatever their grid offsets -- or clients of one (D, T) that joined together and are still
-// inside their zero history (one grid, one zero_below).
-#define XL_SIDE_ONE_BLOCK_MAX 2048u  // one-block polyphase calls: side-stream chain kernel up to this many clients
-
-struct PolyClass {
-  uint32_t D = 0, Dpad = 0, T = 0, A = 0, V = 0;
-  uint32_t M = 256;          // transform length (128 or 256), V = M - A + 1
-  uint32_t ncols = 0, ncg = 0, nseg_cap = 0;
-  uint32_t rem_ref0 = 0;     // plan-time record of the shared grid's reference client (xl_grid.h)
-  uint32_t hv0 = XL_HCAP;    // plan-time valid history of the members (XL_HCAP: mature)
-  uint32_t dmax = 0;         // largest grid offset of a member
-  std::vector<int> members;
-  // The class outlives re-plans (incremental planning): a member keeps its column for its lifetime, a column that a leaving
-  // member frees is handed to the next joiner, and the branch spectra are computed for NEW columns only -- a join costs
-  // one column of R (8 D M bytes), not the class's whole image.
-  std::vector<int> col_client;        // column -> client id, -1 = free
-  std::vector<uint32_t> col_delta;    // delay the column's spectra were built with
-  std::vector<uint64_t> col_uid;      // ... and for whom (Client::uid)
-  std::map<int, uint32_t> col_of;     // client id -> column
-  uint32_t ncg_cap = 0;               // column groups the R / Y / cols buffers hold
-  bool keep = false;                  // (planning scratch: the class was taken over by the new plan)
-  // The branch spectra live in the mix launch's B-operand order (d_Rh).  mix_kind 1 (xlp_mix_mfma_kernel): scaled per column by a power
-  // of two and split in two halves; per column the scale (host) and what undoes it (device).  mix_kind 3 (xlp_mix_f32_kernel): float32
-  uint32_t mix_kind = 1, nkb = 0;
-  void *d_Rh = nullptr;
-  std::vector<float> col_scale;
-  float *d_cscale = nullptr;
-  float2 *d_X = nullptr;     // shared spectra [passes][Dpad][M][16]
-  bool ximg = false;         // ... instead in the two-half mix's A-operand form (xl_xop_layout.h: the forward launch converts each value once;
-                             // option "mix_operand_image"): [passes][M][2][2 nkb][16] 16-byte slots in the same buffer
-  // two-half mix of a cf32 stream: per segment the largest component of its shared spectra, found by the forward launch (XlpArgs::segmax):
-  // two buffers of seg_cap entries, a call uses buffer seg_par; lives and dies with d_X
-  uint32_t *d_segmax = nullptr;
-  uint32_t seg_cap = 0, seg_par = 0;
-  float2 *d_Y = nullptr;     // mixed spectra  [cg][nseg_cap][sub][bin M][CW columns] (xl_y_layout.h)
-  XlpCol *d_cols = nullptr;  // per column: output row, grid offset, NCO increment
-  int last_inv = -1;         // which inverse kernel the class's latest launch took (describe; xlp_inverse_pick): 3 / 5 / 6, -1 = none yet
-};
 
 }  // namespace
 
@@ -220,8 +142,8 @@ struct xlating_batch_t {
                               // 8-point transforms in registers (xl_inv8.hip), 6 = always the 32 x 4 cut (xl_inv32.hip: 32-point transforms
                               // in registers, whole-line loads, 256-byte store runs), 3 = always staged in LDS on dense rows with an XOR swizzle
   uint32_t mix_kernel = 1;    // option "mix_kernel": 1 (default) = two-half float16 operands on the matrix cores where the class allows them
-                              // (integer input format, D <= 64), float32 operands on the matrix cores everywhere else (cf32 input,
-                              // D > 64); 3 = float32 operands for every class (the all-float32 arithmetic of the path)
+                              // (integer input format, D <= 112), float32 operands on the matrix cores everywhere else (cf32 input,
+                              // D > 112); 3 = float32 operands for every class (the all-float32 arithmetic of the path)
   int mix_img = -1;           // option "mix_operand_image": classes on the two-half kernel of up to 8 k-blocks with an integer input format
                               // (xlp_ximg_eligible) get their shared spectra from the forward launch in the mix's operand form -- -1
                               // (default) by the size rule (xlp_ximg_pays), 1 wherever the form exists; 0 = float32 spectra, converted
@@ -621,43 +543,6 @@ extern "C" int xlating_batch_create(uint32_t sampling_freq, int input_format, ui
 
 extern "C" int xlating_batch_num_clients(const xlating_batch *b) { return b ? b->nalive : 0; }
 
-// Output rows.  A client's row (its outputs of a call, and 1/16 of that in the phase tables) is reserved when it joins and
-// stays where it is until it leaves: re-plans never move anybody's outputs.  First fit over the free extents, else the end.
-static uint32_t xl_row_alloc(xlating_batch *b, uint32_t len) {
-  for (auto it = b->free_rows.begin(); it != b->free_rows.end(); ++it) {
-    if (it->second < len) continue;
-    const uint32_t off = it->first, rest = it->second - len;
-    b->free_rows.erase(it);
-    if (rest) b->free_rows[off + len] = rest;
-    return off;
-  }
-  const uint32_t off = b->rows_end;
-  b->rows_end += len;
-  return off;
-}
-
-static void xl_row_free(xlating_batch *b, uint32_t off, uint32_t len) {
-  if (len == 0) return;
-  auto it = b->free_rows.emplace(off, len).first;
-  auto nx = std::next(it);
-  if (nx != b->free_rows.end() && it->first + it->second == nx->first) {
-    it->second += nx->second;
-    b->free_rows.erase(nx);
-  }
-  if (it != b->free_rows.begin()) {
-    auto pv = std::prev(it);
-    if (pv->first + pv->second == it->first) {
-      pv->second += it->second;
-      b->free_rows.erase(it);
-      it = pv;
-    }
-  }
-  if (it->first + it->second == b->rows_end) {  // the last extent gives the space back
-    b->rows_end = it->first;
-    b->free_rows.erase(it);
-  }
-}
-
 extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, const float *taps, size_t taps_len,
                                         int32_t center_freq) {
   if (taps_len == 0) return -1;  // like create_frequency_xlating_filter (xlating.c:496-498)
@@ -695,7 +580,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   c.out_cap = b->gcap * (b->max_samples / decimation + 1);  // xlating.c:568 per block
   c.row_len = xl_roundup(c.out_cap, 2 * XL_PH_STRIDE);  // rows start at multiples of 2 strides: the NCO role stores pairs of
                                                         // table entries as 16 bytes
-  c.out_off = xl_row_alloc(b, c.row_len);
+  c.out_off = xl_row_alloc(b->free_rows, b->rows_end, c.row_len);
   b->nalive++;
   b->dirty = true;
   // The running phase of a new client starts at 1 + 0j (xlating.c:543); slot = client id.  Any phase table
@@ -708,7 +593,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   auto rollback = [&](int code) {
     c.alive = false;
     c.rt.clear();
-    xl_row_free(b, c.out_off, c.row_len);
+    xl_row_free(b->free_rows, b->rows_end, c.out_off, c.row_len);
     c.row_len = 0;
     b->nalive--;
     return code;
@@ -751,184 +636,22 @@ extern "C" int xlating_batch_remove_client(xlating_batch *b, int id) {
   if (b == nullptr || id < 0 || (size_t)id >= b->clients.size() || !b->clients[id].alive) return -EINVAL;
   b->clients[id].alive = false;
   b->clients[id].rt.clear();
-  xl_row_free(b, b->clients[id].out_off, b->clients[id].row_len);
+  xl_row_free(b->free_rows, b->rows_end, b->clients[id].out_off, b->clients[id].row_len);
   b->clients[id].row_len = 0;
   b->nalive--;
   b->dirty = true;
   return 0;
 }
 
-// (Re)build the resident plan: classes, tiles (register-tile heights 8/4/2/1), groups, tap image, NCO table.
-// NCO riders (xl_kernels.hip) pay in a window: the launch is one round of workgroups (all resident at once -- in a
-// multi-round launch the dispatcher evens things out by itself and riders, which sit in one XCD's share of the work
-// list, measured 5-12 % slower), and the FIR work of a SIMD clearly outlasts the chain (~18.5 ns per output; when the
-// chain is the critical path -- short filters, few clients -- it is quicker alone in workgroups of its own: no
-// staging first, 16 lanes).  Measured at 505 taps, D = 42: 384..1024 clients 3-8 % faster with riders; 101 taps
-// 25 % slower.
-static bool xl_riders_window(size_t wgs, int nw, uint32_t Tpad, int ct, uint32_t K, size_t lds, int min_wgs) {
-  const size_t cap = 256 * std::max<size_t>(1, std::min<size_t>((160 * 1024) / std::max<size_t>(lds, 1), 7));
-  const double fir_us = (double)wgs * nw / 1024.0 * (double)Tpad * ct * 8.0 / 2000.0;  // 4-cycle packed FMAs at ~2 GHz
-  const double chain_us = 0.0185 * (double)K;
-  return min_wgs <= 1 || (wgs >= (size_t)min_wgs && wgs <= cap && fir_us >= 1.3 * chain_us);
+// The settings the plan's host logic reads (xl_plan.h).
+static XlPlanOpts xl_plan_opts(const xlating_batch *b) {
+  XlPlanOpts o;
+  o.fmt = b->fmt, o.max_samples = b->max_samples, o.gcap = b->gcap;
+  o.poly_mode = b->poly_mode, o.poly_min_set = b->poly_min_set, o.poly_min_clients = b->poly_min_clients, o.poly_m = b->poly_m;
+  o.mix_kernel = b->mix_kernel, o.mix_img = b->mix_img, o.riders = b->riders, o.riders_min_wgs = b->riders_min_wgs;
+  o.exp_h = b->exp_h, o.nco_side = b->nco_side, o.expected_clients = b->expected_clients;
+  return o;
 }
-
-static const int kHeights[XL_NLAUNCH] = {12, 10, 9, 8, 4, 2, 1};
-
-// Direct classes over the clients selected by `use`: key (D, T, consumed mod D, valid history).  A mature client's
-// windows never reach below its join point, so all mature clients of one grid share a class whatever their age.
-static void xl_direct_classes(const xlating_batch *b, const std::vector<bool> &use, std::vector<DirectClass> *out) {
-  out->clear();
-  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, size_t> cls_of;
-  for (size_t i = 0; i < b->clients.size(); ++i) {
-    const Client &c = b->clients[i];
-    if (!c.alive || !use[i]) continue;
-    const uint32_t rem = (uint32_t)(c.consumed % c.D);
-    const uint32_t hv = xl_mature(c) ? XL_HCAP : (uint32_t)c.consumed;
-    auto key = std::make_tuple(c.D, c.T, rem, hv);
-    auto it = cls_of.find(key);
-    if (it == cls_of.end()) {
-      it = cls_of.emplace(key, out->size()).first;
-      out->push_back(DirectClass{c.D, c.T, rem, hv, {}});
-    }
-    (*out)[it->second].members.push_back((int)i);
-  }
-}
-
-// Builds one set of direct-FIR launches over `classes`: tiles, groups, tap image rows (appended to `image`).
-static int xl_build_launches(xlating_batch *b, Launch *Ls, const std::vector<DirectClass> &classes, int big_h,
-                             std::vector<float> *image, std::vector<double> *imageq) {
-  struct TileDesc {
-    size_t cls;
-    std::vector<int> ids;
-  };
-  std::vector<TileDesc> tiles_of[XL_NLAUNCH];
-  const uint32_t cap_samples = b->max_samples * b->gcap;
-  for (int li = 0; li < XL_NLAUNCH; ++li) {
-    Ls[li].ct = kHeights[li];
-    Ls[li].lds = 0;
-    Ls[li].nw = XL_NW_DEFAULT;
-    Ls[li].all_wide = true;
-    Ls[li].maxD = 1;
-    Ls[li].minD = 0xFFFFFFFFu;
-  }
-  for (size_t k = 0; k < classes.size(); ++k) {
-    const std::vector<int> &m = classes[k].members;
-    int h = big_h;
-    if (m.size() < 8) h = m.size() > 4 ? 8 : (m.size() > 2 ? 4 : (m.size() > 1 ? 2 : 1));
-    int li = 0;
-    while (kHeights[li] != h) ++li;
-    for (size_t next = 0; next < m.size(); next += (size_t)h) {
-      const size_t cnt = std::min<size_t>((size_t)h, m.size() - next);
-      tiles_of[li].push_back(TileDesc{k, std::vector<int>(m.begin() + next, m.begin() + next + cnt)});
-    }
-  }
-
-  for (int li = 0; li < XL_NLAUNCH; ++li) {
-    Launch &L = Ls[li];
-    if (tiles_of[li].empty()) continue;
-    const int ct = L.ct;
-    int gi = -1;
-    size_t gcls = 0;
-    for (const TileDesc &td : tiles_of[li]) {
-      const DirectClass &cs = classes[td.cls];
-      const uint32_t Tpad = xl_roundup(cs.T, xl_tap_step(ct));
-      if (gi < 0 || gcls != td.cls || L.groups[gi].ntiles == (uint32_t)L.nw) {
-        L.groups.emplace_back();
-        gi = (int)L.groups.size() - 1;
-        gcls = td.cls;
-        XlGroup *g = &L.groups[gi];
-        memset(g, 0, sizeof(*g));
-        g->D = cs.D;
-        g->T = cs.T;
-        g->Tpad = Tpad;
-        g->rem0 = cs.rem0;
-        g->hv0 = cs.hv0;
-        g->wide = (cs.D % 2 == 0) ? 1u : 0u;
-        if (!g->wide) L.all_wide = false;
-        L.lds = std::max(L.lds, xl_fir_lds_bytes_ota(cs.D, Tpad, 64));
-        L.maxD = std::max(L.maxD, cs.D);
-        L.minD = std::min(L.minD, cs.D);
-      }
-      XlGroup *g = &L.groups[gi];
-      XlTile &t = g->tiles[g->ntiles++];
-      const uint32_t real_off = (uint32_t)(image->size() / 2);
-      t.tap_off = real_off;
-      t.nclients = (uint32_t)td.ids.size();  // a partial last tile keeps zero taps for the missing clients
-      image->resize(image->size() + (size_t)2 * Tpad * ct, 0.0f);
-      if (imageq) imageq->resize(image->size(), 0.0);
-      float *dst = image->data() + (size_t)2 * real_off;
-      for (size_t j = 0; j < td.ids.size(); ++j) {
-        const Client &c = b->clients[td.ids[j]];
-        t.out_off[j] = c.out_off;
-        t.incr[j] = make_float2(c.incr[0], c.incr[1]);
-        t.qincr[j] = (uint32_t)(uint16_t)c.qincr[0] | ((uint32_t)(uint16_t)c.qincr[1] << 16);
-        for (uint32_t i = 0; i < cs.T; ++i) {
-          dst[((size_t)i * ct + j) * 2] = c.rt[2 * i];
-          dst[((size_t)i * ct + j) * 2 + 1] = c.rt[2 * i + 1];
-          if (imageq) {
-            (*imageq)[(size_t)2 * real_off + ((size_t)i * ct + j) * 2] = (double)c.rtq[2 * i];
-            (*imageq)[(size_t)2 * real_off + ((size_t)i * ct + j) * 2 + 1] = (double)c.rtq[2 * i + 1];
-          }
-        }
-      }
-    }
-  }
-  // ---- spare waves for the NCO riders (xl_kernels.hip): groups with fewer tiles than the launch has waves.  The
-  // launch that carries the role (the first one with groups) gets a spare wave by splitting its last full group
-  // into 3 + 1 tiles when it has none and the engine is big enough for the balance to matter.
-  {
-    bool first = true;
-    for (int lq = 0; lq < XL_NLAUNCH; ++lq) {
-      Launch &L = Ls[lq];
-      if (L.groups.empty()) continue;
-      uint32_t idle = 0;
-      for (const XlGroup &g : L.groups) idle += (uint32_t)L.nw - g.ntiles;
-      const uint32_t kest = cap_samples / L.groups[0].D + 1;
-      if (first && idle == 0 && b->riders && L.nw == XL_NW_MAX &&
-          xl_riders_window((L.groups.size() + 1) * ((kest + 63) / 64), L.nw, L.groups[0].Tpad, L.ct, kest, L.lds,
-                           b->riders_min_wgs)) {
-        XlGroup &last = L.groups.back();
-        XlGroup extra = last;
-        extra.ntiles = 1;
-        extra.tiles[0] = last.tiles[XL_NW_MAX - 1];
-        last.ntiles = XL_NW_MAX - 1;
-        L.groups.push_back(extra);
-      }
-      // (riders are only used in one-round launches -- xl_riders_window -- where every workgroup is dispatched within
-      // ~10 us of the start, so the groups with spare waves can stay where they are: last, which suits the tail)
-      idle = 0;
-      for (XlGroup &g : L.groups) {
-        g.idle_before = idle;
-        idle += (uint32_t)L.nw - g.ntiles;
-      }
-      L.idle_waves = idle;
-      first = false;
-    }
-  }
-  for (int lq = 0; lq < XL_NLAUNCH; ++lq) {
-    Launch &L = Ls[lq];
-    L.ota = 64;
-    if (L.lds > 160 * 1024) {  // huge decimation: fewer active lanes per wave so that the window image fits
-      for (L.ota = 32; L.ota >= 8; L.ota >>= 1) {
-        size_t need = 0;
-        for (const XlGroup &g : L.groups) need = std::max(need, xl_fir_lds_bytes_ota(g.D, g.Tpad, L.ota));
-        if (need <= 160 * 1024) {
-          L.lds = need;
-          break;
-        }
-      }
-      if (L.ota < 8) return -EINVAL;  // (add_client already refused such a shape)
-    }
-  }
-  return 0;
-}
-
-// Direct FIR launches whose own work is short against the NCO chain (~25-32 us per block) gain from the side-stream chain
-// kernel on reserved CUs like the polyphase launches do; heavier ones hide the chain in their spare waves for free and
-// would only lose the reserved CUs.  Measured, 8 blocks per call, us per block fused -> side: 128 clients x 101 taps
-// (40 M complex MACs per block) 29.9 -> 27.1; 128 x 505 native (202 M) 40.5 -> 35.5; 1024 x 101 (323 M) 37.9 -> 40.4;
-// 1024 x 505 native (1615 M) 203 -> 227.
-static bool xl_direct_is_light(double macs_per_block) { return macs_per_block < 250e6; }
 
 // Uploads one launch set: its tap image (+ the Q15 image) and its group descriptors.
 static int xl_upload_launch_set(xlating_batch *b, Launch *set, const std::vector<float> &image, float2 **d_image,
@@ -968,7 +691,7 @@ static int xl_batch_build_all_set(xlating_batch *b) {
   std::vector<float> image;
   std::vector<double> imageq;
   const bool has_q15 = b->fmt != XL_FMT_CF32 && b->want_q15;
-  int rc = xl_build_launches(b, b->launches, b->classes, b->big_h, &image, has_q15 ? &imageq : nullptr);
+  int rc = xl_build_launches(xl_plan_opts(b), b->clients, b->launches, b->classes, b->big_h, &image, has_q15 ? &imageq : nullptr);
   if (rc != 0) return rc;
   rc = xl_upload_launch_set(b, b->launches, image, &b->d_taps, has_q15 ? &imageq : nullptr);
   if (rc != 0) return rc;
@@ -986,58 +709,6 @@ static int xl_batch_build_all_set(xlating_batch *b) {
   return 0;
 fail:
   return xl_errno_of_last_hip_error();
-}
-
-// Transform length of a polyphase class: the mix launch streams D x M branch-spectrum values per client and call from HBM,
-// which is what bounds it with many clients and one block per call; M = 128 halves that for ~5-10 % more arithmetic
-// (valid outputs per segment M - A + 1) while the filter is short against the segment.  Measured at D = 42, 505 taps, one
-// block per call: x1.17 at 4096 clients, x1.08 at 2048, x1.015 at 1024, x0.99 at 512 and below.
-// M = 64 (round 6): classes of more than 64 branches (9+ k-blocks of 8: the wide two-half mix, D = 65 .. 112; the float32 mixes above
-// that or on request) with up to 8 taps per branch (57+ of 64 outputs per segment valid).  A wide workgroup holds 104 KB of operands for ONE bin of 128 columns, and half the bins is half the workgroups
-// and half the operand stream (config 5 at 1024 clients: 512 workgroups = ONE round instead of two): config 5 (cf32, D = 100, 3 taps
-// per branch) 8 blocks per call at 1024 / 2048 / 4096 clients 16.9 / 29.1 / 51.0 -> 16.0 / 26.2 / 47.4 us per block, ONE block per call
-// 48.4 -> 40.8 (4096 clients: 138 -> 94); D = 72 / 100 off cu8 streams with 3 / 5 / 8 taps per branch: ahead or level at 1024 and 4096
-// clients; at 128-768 clients level with 128 and ahead of 256 (which the rule above picked there: 12.0 / 39.4 against 11.9 / 29.1 us
-// per block at 256 clients x 8 / 1 blocks per call).  Narrow classes (D <= 64) LOSE with 64 points (D = 64, 4096 clients: 59.4 -> 65.6):
-// their workgroups hold less and the inverse launch, whose tiles stay 32 KB, gains nothing.  The float32 mixes gain too (config 5 with
-// mix_kernel = 3: -4 %; D = 128 / 200 on the streamed kernel: -9 / -17 % at 1024 clients, -6 / -11 % at 256); 10-13 taps per branch: level
-// (not taken).  profiles/r06_transform_length_64.txt
-static uint32_t xl_poly_pick_m(const xlating_batch *b, uint32_t A, size_t members, uint32_t D) {
-  if (A > 64) return 256u;
-  if (b->poly_m) return A > 32 && b->poly_m == 64u ? 128u : b->poly_m;  // (forced; a class needs A <= M / 2)
-  const uint32_t nkb = (D + 7u) / 8u;
-  if (nkb > XLP_NKB_4W && A <= 8) return 64u;
-  return A <= 32 && members >= 768 ? 128u : 256u;
-}
-
-// Which mix launch a class of D branches takes (PolyClass::mix_kind): the two-half kernel (1) carries the spectra as pairs of halves
-// -- bounded by the input format, or (cf32 streams) scaled per segment by what the forward launch found (PolyClass::d_segmax) -- and
-// holds at most XLP_NKB_MAX k-blocks of 8 branches (D <= 112); the float32 matrix instruction (3) has no such condition: it is what
-// D > 112 takes, and every class on request (option "mix_kernel" = 3: all-float32 products).
-static uint32_t xl_poly_mix_kind(const xlating_batch *b, uint32_t D) {
-  const bool halves_ok = D <= 8u * XLP_NKB_MAX;
-  return (b->mix_kernel == 3u || !halves_ok) ? 3u : 1u;
-}
-
-// Whether a class's shared spectra are kept in the two-half mix's operand form (PolyClass::ximg, option "mix_operand_image"): where
-// the form exists (xlp_ximg_eligible: a constant scale and xlp_mix_mfma_kernel as the only reader) and, unless the option forces it,
-// where it measured ahead (xlp_ximg_pays, xl_plan_rules.h).
-static bool xl_poly_ximg(const xlating_batch *b, uint32_t D, uint32_t M, size_t members) {
-  if (b->mix_img == 0 || !xlp_ximg_eligible((uint32_t)b->fmt, xl_poly_mix_kind(b, D), (D + 7u) / 8u, M)) return false;
-  return b->mix_img > 0 || xlp_ximg_pays((uint32_t)members, b->gcap);
-}
-
-// Power-of-two scale of a column's branch spectra for the matrix-core mix: every component of R_b[m] = sum_a r_b[a] e^{..} is at
-// most L = max_b sum_a |r_b[a]| (the same for the delayed taps: a delay permutes the branches); scale = 2^floor(log2(RMAX / L)).
-static float xl_poly_col_scale(const Client &c, uint32_t D, uint32_t T) {
-  std::vector<double> l1(D, 0.0);
-  for (uint32_t i = 0; i < T; ++i) l1[i % D] += hypot((double)c.rt[2 * i], (double)c.rt[2 * i + 1]);
-  double L = 0.0;
-  for (double v : l1) L = std::max(L, v);
-  if (!(L > 0.0) || !std::isfinite(L)) return 1.0f;
-  int e = (int)floor(log2((double)XLP_H_RMAX / L));
-  e = std::max(-100, std::min(100, e));
-  return (float)ldexp(1.0, e);
 }
 
 // Brings the device images of a polyphase class in line with its member list: columns, branch spectra of the NEW columns.
@@ -1165,6 +836,64 @@ fail : {
   return xl_errno_of_last_hip_error();
 }
 
+// Re-creates the CU-masked stream pair for `want` reserved CUs per XCD (0: none), with every stream of the engine synchronised.
+static void xl_batch_reserve_cus(xlating_batch *b, uint32_t want) {
+  if (b->cs_masked) (void)hipStreamDestroy(b->cs_masked);
+  if (b->nco_masked) (void)hipStreamDestroy(b->nco_masked);
+  b->cs_masked = b->nco_masked = nullptr;
+  b->last_nco = nullptr;
+  b->reserve_r = 0;
+  b->last_stream = b->own_stream;  // (everything was synchronised at the top of the plan)
+  for (int i = 0; i < XL_NTAB; ++i) b->ev_done_valid[i] = false, b->tab_call[i] = 0;
+  b->done_call = 0;
+  if (want > 0u) {
+    uint32_t chain_mask[8], main_mask[8];
+    for (uint32_t wd = 0; wd < 8; ++wd) {
+      chain_mask[wd] = 0u;
+      for (uint32_t bit = 0; bit < 32; ++bit)
+        if (wd * 32u + bit < 8u * want) chain_mask[wd] |= 1u << bit;
+      main_mask[wd] = ~chain_mask[wd];
+    }
+    if (hipExtStreamCreateWithCUMask(&b->nco_masked, 8, chain_mask) == hipSuccess &&
+        hipExtStreamCreateWithCUMask(&b->cs_masked, 8, main_mask) == hipSuccess) {
+      b->reserve_r = want;
+    } else {
+      XL_LOG_ERR("CU-masked streams are not available (%s): the NCO chain kernel shares the chip", hipGetErrorString(hipGetLastError()));
+      if (b->cs_masked) (void)hipStreamDestroy(b->cs_masked);
+      if (b->nco_masked) (void)hipStreamDestroy(b->nco_masked);
+      b->cs_masked = b->nco_masked = nullptr;
+    }
+  }
+}
+
+// Uploads the wide clients' descriptors and tap images.
+static int xl_upload_wide(xlating_batch *b) {
+  std::vector<float> wt;
+  std::vector<double> wq;
+  size_t k = 0;
+  for (size_t i = 0; i < b->clients.size(); ++i) {
+    const Client &c = b->clients[i];
+    if (!c.alive || !c.wide) continue;
+    XlWideClient &w = b->wide[k++];
+    w.tap_off = (uint32_t)(wt.size() / 2);
+    wt.insert(wt.end(), c.rt.begin(), c.rt.end());
+    w.qtap_off = (uint32_t)(wq.size() / 2);
+    if (b->fmt != XL_FMT_CF32)
+      for (int16_t q : c.rtq) wq.push_back((double)q);
+  }
+  XL_TRY(xl_plan_alloc(b, (void **)&b->d_wide, b->wide.size() * sizeof(XlWideClient)));
+  XL_TRY(hipMemcpy(b->d_wide, b->wide.data(), b->wide.size() * sizeof(XlWideClient), hipMemcpyHostToDevice));
+  XL_TRY(xl_plan_alloc(b, (void **)&b->d_wtaps, wt.size() * sizeof(float)));
+  XL_TRY(hipMemcpy(b->d_wtaps, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!wq.empty()) {
+    XL_TRY(xl_plan_alloc(b, (void **)&b->d_wqtaps, wq.size() * sizeof(double)));
+    XL_TRY(hipMemcpy(b->d_wqtaps, wq.data(), wq.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return 0;
+fail:
+  return xl_errno_of_last_hip_error();
+}
+
 // (Re)build the resident plan.  INCREMENTAL where it matters: clients keep their output rows, polyphase classes keep their
 // columns and branch spectra (a join computes one column), the all-clients launch set is built only when a call needs it;
 // rebuilt every time: the class lists, the optimized-mode direct set (the few clients outside the polyphase classes) and the
@@ -1194,6 +923,7 @@ static int xl_batch_plan(xlating_batch *b) {
   b->planned_immature = 0;
   b->plan_maxD = 1;
   const uint32_t cap_samples = b->max_samples * b->gcap;
+  const XlPlanOpts o = xl_plan_opts(b);
   for (size_t i = 0; i < b->clients.size(); ++i) {
     Client &c = b->clients[i];
     if (!c.alive) continue;
@@ -1226,202 +956,25 @@ static int xl_batch_plan(xlating_batch *b) {
   }
   b->out_total = b->rows_end;
 
-  // ---- polyphase classes (optimized mode): all mature clients of one (D, T) -- many clients (its lanes are client
-  // columns and its cost per client does not depend on the tap count) with a filter long enough to be worth it
-  std::vector<bool> all_use(b->clients.size(), true), rest_use(b->clients.size(), true);
+  // ---- polyphase classes (optimized mode): the classes of the previous plan that still fit are taken over, the others released
+  std::vector<bool> all_use(b->clients.size(), true);
   for (size_t i = 0; i < b->clients.size(); ++i)
-    if (b->clients[i].wide) all_use[i] = rest_use[i] = false;
+    if (b->clients[i].wide) all_use[i] = false;
+  std::vector<bool> rest_use(all_use);
   std::vector<PolyClass> next_poly;
-  struct Pending {
-    size_t idx;
-    std::vector<uint32_t> new_cols;
-    bool fresh;
-  };
-  std::vector<Pending> pending;
-  for (PolyClass &pc : b->poly) pc.keep = false;
-  {
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<int>> by_shape;
-    for (size_t i = 0; i < b->clients.size(); ++i) {
-      const Client &c = b->clients[i];
-      if (c.alive && !c.wide) by_shape[std::make_tuple(c.D, c.T, c.planned_mature ? XL_HCAP : (uint32_t)c.consumed)].push_back((int)i);
-    }
-    for (auto &kv : by_shape) {
-      const uint32_t D = std::get<0>(kv.first), T = std::get<1>(kv.first), hv0 = std::get<2>(kv.first);
-      const std::vector<int> &m = kv.second;
-      std::vector<uint32_t> rems;
-      for (int id : m) rems.push_back((uint32_t)(b->clients[id].consumed % D));
-      std::vector<uint32_t> distinct(rems);
-      std::sort(distinct.begin(), distinct.end());
-      distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-      // An existing class of this shape whose members are (mostly) still here: same (D, T), same kind (mature), or the
-      // immature class these very clients formed when they joined together.  Its shared grid moved with the stream.
-      PolyClass *old = nullptr;
-      for (PolyClass &oc : b->poly) {
-        if (oc.keep || oc.D != D || oc.T != T) continue;
-        const bool same_kind = oc.hv0 == hv0 || (hv0 == XL_HCAP && oc.hv0 != XL_HCAP && !m.empty() && oc.col_of.count(m[0]));
-        if (same_kind) {
-          old = &oc;
-          break;
-        }
-      }
-      uint32_t ref = 0, dmax = 0;
-      bool reuse = false;
-      if (old != nullptr) {
-        ref = (old->rem_ref0 + advanced % D) % D;
-        for (uint32_t r : distinct) dmax = std::max(dmax, (ref + D - r) % D);
-        const uint32_t A = (T + dmax + D - 1) / D;
-        reuse = A == old->A && xl_poly_pick_m(b, A, m.size(), D) == old->M && xl_poly_mix_kind(b, D) == old->mix_kind &&
-                xl_poly_ximg(b, D, old->M, m.size()) == old->ximg;
-      }
-      if (!reuse) {
-        // the shared grid's reference: the member offset that keeps the largest delay of a member smallest
-        uint32_t best_ref = distinct[0], best_dmax = 0xFFFFFFFFu;
-        for (uint32_t cand : distinct) {
-          uint32_t dm = 0;
-          for (uint32_t r : distinct) dm = std::max(dm, (cand + D - r) % D);  // delta = (j0_c - j0_ref) mod D = (rem_ref - rem_c) mod D
-          if (dm < best_dmax) best_dmax = dm, best_ref = cand;
-        }
-        ref = best_ref, dmax = best_dmax;
-      }
-      const uint32_t A = (T + dmax + D - 1) / D;
-      const uint32_t M = xl_poly_pick_m(b, A, m.size(), D);
-      const bool fits = A >= 2 && A <= M / 2 && D <= 504;
-      // crossover: with the mix on the matrix cores the path costs the same whatever the filter length and little beside the
-      // recurrence in small classes (A/B at 8 blocks per call, direct kernel -> polyphase, us per block: 101 taps 37.3 -> 28.2 at
-      // 1024 clients, 124.8 -> 88.7 at 4096, 23.3 -> 22.9 at 128; 505 taps 24.8 -> 22.9 at 96 clients, 23.1 -> 22.7 at 32; cf32 10
-      // Msps, D = 100, 257 taps: 38.4 -> 23.4 at 1024 clients, 12.8 -> 11.8 at 256, 11.4 -> 11.3 at 64): 2 taps per branch, 32 clients
-      // Classes of more than XLMF_NB8_MAX k-blocks (D > 112: float32 operands re-streamed every pass, xlp_mix_f32_stream_kernel): the
-      // same 2 taps per branch from 128 clients on -- measured in round 6 at D = 128 / 200 / 400, 1.2 / 2.4 / 4.8 / 12 taps per branch,
-      // 32 .. 1024 clients (profiles/r06_plan_rules_other_shapes.txt): the path costs 10.6-11.5 us per block up to 128 clients whatever
-      // the filter, the direct kernel 11.4-11.9 at 128 clients x 2.4 taps per branch (1.04-1.07 x) and 47-62 at 1024 (1.6-2.1 x; rounds
-      // 4-5 sent those to the direct kernel: 4.5 taps per branch was the only crossover a measurement of that kernel stood behind);
-      // at 64 clients the direct kernel is still ahead up to 4.8 taps per branch.
-      const bool streamed = (D + 7u) / 8u > XLMF_NB8_MAX;
-      const size_t min_clients = b->poly_min_set ? b->poly_min_clients : (streamed ? 128u : 32u);
-      const bool pays = m.size() >= min_clients && T >= 2 * D;
-      if (b->poly_mode == 0 || !fits || (b->poly_mode < 0 && !pays)) continue;
-      PolyClass pc;
-      Pending pd;
-      pd.fresh = !reuse;
-      if (reuse) {
-        pc = std::move(*old);
-        old->keep = true;
-        old->d_X = old->d_Y = nullptr;
-        old->d_segmax = nullptr;
-        old->d_cols = nullptr;
-        old->d_Rh = nullptr;
-        old->d_cscale = nullptr;
-        // members that left give their columns back
-        std::vector<bool> here(b->clients.size(), false);
-        for (int id : m) here[id] = true;
-        for (auto it = pc.col_of.begin(); it != pc.col_of.end();) {
-          if (!here[it->first]) {
-            pc.col_client[it->second] = -1;
-            it = pc.col_of.erase(it);
-          } else {
-            ++it;
-          }
-        }
-        while (!pc.col_client.empty() && pc.col_client.back() < 0) {  // (trailing free columns shrink the class)
-          pc.col_client.pop_back();
-          pc.col_delta.pop_back();
-          pc.col_uid.pop_back();
-        }
-        pc.col_scale.resize(pc.col_client.size(), 1.0f);
-      } else {
-        pc.D = D;
-        pc.Dpad = xl_roundup(D, XLP_BSTEP);
-        pc.T = T;
-        pc.A = A;
-        pc.M = M;
-        pc.V = M - A + 1;
-        pc.mix_kind = xl_poly_mix_kind(b, D);
-        pc.nkb = (D + 7u) / 8u;
-        pc.ximg = xl_poly_ximg(b, D, M, m.size());
-      }
-      pc.keep = false;
-      pc.rem_ref0 = ref;
-      pc.hv0 = hv0;
-      pc.dmax = dmax;
-      pc.members = m;
-      // newcomers (and, for a recycled client id, a changed delay) take the free columns first, then new ones
-      size_t next_free = 0;
-      for (int id : m) {
-        const uint32_t delta = (ref + D - (uint32_t)(b->clients[id].consumed % D)) % D;
-        auto it = pc.col_of.find(id);
-        if (it != pc.col_of.end() && pc.col_delta[it->second] == delta && pc.col_uid[it->second] == b->clients[id].uid) continue;
-        uint32_t col;
-        if (it != pc.col_of.end()) {
-          col = it->second;
-        } else {
-          while (next_free < pc.col_client.size() && pc.col_client[next_free] >= 0) ++next_free;
-          if (next_free == pc.col_client.size()) {
-            pc.col_client.push_back(-1);
-            pc.col_delta.push_back(0);
-            pc.col_uid.push_back(0);
-          }
-          col = (uint32_t)next_free;
-          pc.col_client[col] = id;
-          pc.col_of[id] = col;
-        }
-        pc.col_delta[col] = delta;
-        pc.col_uid[col] = b->clients[id].uid;
-        pd.new_cols.push_back(col);
-      }
-      pc.ncols = (uint32_t)pc.col_client.size();
-      pd.idx = next_poly.size();
-      next_poly.push_back(std::move(pc));
-      pending.push_back(std::move(pd));
-      for (int id : m) rest_use[id] = false;
-    }
-  }
+  std::vector<XlPolyPending> pending;
+  xl_poly_form_classes(o, b->clients, b->poly, advanced, &next_poly, &pending, &rest_use);
   for (PolyClass &oc : b->poly)
     if (!oc.keep) xl_poly_release(b, oc);
   b->poly = std::move(next_poly);
-  xl_direct_classes(b, all_use, &b->classes);
-  if (!b->poly.empty()) xl_direct_classes(b, rest_use, &b->classes_rest);
+  xl_direct_classes(b->clients, all_use, &b->classes);
+  if (!b->poly.empty()) xl_direct_classes(b->clients, rest_use, &b->classes_rest);
   lap("classes");
 
-  // ---- register-tile height.  Every wave does the same work (64 outputs x H clients x T taps) and a CU holds
-  // floor(160 KiB / window image) workgroups of 4 waves (6 at the server-default shape).  A launch whose workgroups
-  // do not all fit runs the surplus in a second round almost alone -- latency-bound, about one lone-workgroup
-  // duration (measured 48 us of a 161 us launch at 1024 clients with H = 8: 32 x 49 = 1568 workgroups on 1536
-  // slots).  Taller tiles trade a little per-wave time for fewer workgroups: pick the height whose launch costs
-  // least in (waves on the busiest SIMD) x (work per wave).  Classes with fewer than 8 clients use one small
-  // tile.
-  int big_h = 8;
-  {
-    size_t lds1 = 0;
-    for (const DirectClass &cs : b->classes)
-      if (cs.members.size() >= 8) lds1 = std::max(lds1, xl_fir_lds_bytes_ota(cs.D, xl_roundup(cs.T, 12), 64));
-    if (lds1 > 0) {
-      const long slots = std::max<long>(1, std::min<long>((long)(160 * 1024 / lds1), 7));
-      const long cap = slots * 256;
-      long best = -1;
-      static const int cand[4] = {8, 9, 10, 12};
-      for (int h : cand) {
-        long wgs = 0;
-        for (const DirectClass &cs : b->classes) {
-          const long n = (long)cs.members.size();
-          if (n < 8) continue;
-          const long kest = b->max_samples / cs.D + 1;
-          wgs += (((n + h - 1) / h + XL_NW_MAX - 1) / XL_NW_MAX) * ((kest + 63) / 64);
-        }
-        const long full = wgs / cap, rem = wgs % cap;
-        long cost = full * slots * h;
-        if (rem) cost += std::max<long>((rem + 255) / 256, 3) * h;
-        if (best < 0 || cost < best) {
-          best = cost;
-          big_h = h;
-        }
-      }
-    }
-    if (b->exp_h == 8 || b->exp_h == 9 || b->exp_h == 10 || b->exp_h == 12) big_h = b->exp_h;
-  }
-  b->big_h = big_h;
+  b->big_h = xl_pick_tile_height(o, b->classes);
   std::vector<float> image_rest;  // tap image of the optimized-mode launch set
   if (!b->poly.empty()) {
-    int rc = xl_build_launches(b, b->launches_rest, b->classes_rest, big_h, &image_rest, nullptr);
+    int rc = xl_build_launches(o, b->clients, b->launches_rest, b->classes_rest, b->big_h, &image_rest, nullptr);
     if (rc != 0) {
       // (b->poly already holds the updated classes whose new columns have no branch spectra yet: a plan that stops here must not
       // be reused -- drop it like every other failure does)
@@ -1435,78 +988,14 @@ static int xl_batch_plan(xlating_batch *b) {
   // ---- CU reservation for the side-stream chain kernel (64 clients per workgroup = per CU, dealt round-robin to the
   // 8 XCDs): recreate the two masked streams when the number of reserved CUs changes
   {
-    const uint32_t nwg = ((uint32_t)b->nco.size() + 63u) / 64u;
-    b->macs_all = b->macs_rest = 0.0;
-    for (const DirectClass &cs : b->classes) b->macs_all += (double)cs.members.size() * cs.T / cs.D;
-    for (const DirectClass &cs : b->classes_rest) b->macs_rest += (double)cs.members.size() * cs.T / cs.D;
-    const bool light = xl_direct_is_light(b->macs_all * b->max_samples) || (!b->poly.empty() && xl_direct_is_light(b->macs_rest * b->max_samples));
-    // (one-block calls of a polyphase plan take the side stream too, up to XL_SIDE_ONE_BLOCK_MAX clients: see side_call)
-    const bool one_block_side = !b->poly.empty() && b->nco.size() <= XL_SIDE_ONE_BLOCK_MAX;
-    // (a server that knows how many clients it admits says so -- option "expected_clients" --, and the reservation is made for
-    // that many at once: the 25 ms of a stream re-creation then never fall on a call between two joins)
-    const uint32_t nwg_res = std::max(nwg, (b->expected_clients + 63u) / 64u);
-    // (one CU per chain workgroup while the recurrence bounds the call, none in a band above that, beyond it the chain launch runs in
-    // rounds on fewer CUs -- by the plan's load: launch time per unit of chain time, in clients of the measured shape: xl_plan_rules.h)
-    uint32_t load_wgs = nwg_res;
-    if (!b->poly.empty() && b->gcap >= 2) {  // (engines of one-block calls: the bands as measured by client count -- their calls are short, and nothing else was measured)
-      double ps = b->macs_rest * (double)b->max_samples * 72.0;  // (direct-kernel clients of an optimized call: ~0.072 ns per complex MAC)
-      uint32_t kmax = 1u;
-      for (const PolyClass &pc : b->poly) {
-        const uint32_t K = (b->max_samples + pc.D - 1u) / pc.D;
-        ps += (double)pc.members.size() * xl_client_launch_ps(pc.M, K, pc.V, 8u * pc.nkb, pc.mix_kind, b->gcap);
-        kmax = std::max(kmax, K);
-      }
-      for (const DirectClass &cs : b->classes_rest) kmax = std::max(kmax, (b->max_samples + cs.D - 1u) / cs.D);
-      // (scaled to the population the CUs are reserved for: option "expected_clients")
-      load_wgs = xl_plan_load_wgs(ps * (double)nwg_res / (double)std::max(nwg, 1u), kmax);
-    }
-    // (the bands have edges where the reservation jumps: stay in the band of the previous plan until the load is two workgroups past one)
-    load_wgs = xl_chain_load_with_hysteresis(load_wgs, b->reserve_band);
-    b->reserve_band = xl_chain_band(load_wgs);
-    const bool side_plan = (b->gcap >= 2 || one_block_side) && (!b->poly.empty() || light || b->nco_side > 0) && b->nco_side != 0;
-    // (the no-reservation band and the rounds were measured on polyphase plans only; a direct-only plan -- whose side-stream chain needs
-    // the masked pair, see side_call -- keeps one CU per chain workgroup, up to half the chip)
-    uint32_t want = !side_plan ? 0u : (b->poly.empty() ? ((nwg_res + 7u) / 8u <= 16u ? (nwg_res + 7u) / 8u : 0u) : xl_chain_reserve_per_xcd(nwg_res, load_wgs));
-    // A wide two-half class (9 .. 14 k-blocks: xl_mixh2.hip) runs two workgroups per CU and launches M x column groups of them -- a
-    // multiple of 512 at every 512 clients: on the 240 CUs a reservation of 16 leaves, BASELINE config 5 at 1024 clients took a third,
-    // quarter-full round of workgroups (56 us per mix launch; the launch's own timeline: profiles/r06_mix_wide_timeline.txt) -- and its
-    // forward and inverse launches lose a sixteenth of the chip as well.  No reservation for such plans: the chain workgroups take CUs as
-    // the launches' tails free them (as in the 33..47 band of the rule).
-    for (const PolyClass &pc : b->poly)
-      if (pc.mix_kind == 1u && pc.nkb > XLP_NKB_4W) want = 0u;
-    if (xl_exp_getenv("XL_EXP_NOMASK")) want = 0u;
-    if (want > 0u && xl_exp_getenv("XL_EXP_ROUNDS1")) want = std::min(16u, (nwg_res + 7u) / 8u);  // (tuning: round 3's rule, one CU per chain workgroup)
-    if (want > 0u && xl_exp_getenv("XL_EXP_RESERVE")) want = std::min(want, (uint32_t)atoi(xl_exp_getenv("XL_EXP_RESERVE")));  // (tuning: fewer CUs, more rounds)
-    // (creating a masked stream pair takes ~25 ms: grow at once, shrink only when two CUs per XCD too many are held, so that
-    // a client count hovering around a multiple of 512 does not recreate the streams at every join and leave)
-    if (want > b->reserve_r || want + 2u <= b->reserve_r || (want == 0u && b->reserve_r != 0u)) {
-      if (b->cs_masked) (void)hipStreamDestroy(b->cs_masked);
-      if (b->nco_masked) (void)hipStreamDestroy(b->nco_masked);
-      b->cs_masked = b->nco_masked = nullptr;
-      b->last_nco = nullptr;
-      b->reserve_r = 0;
-      b->last_stream = b->own_stream;  // (everything was synchronised at the top of the plan)
-      for (int i = 0; i < XL_NTAB; ++i) b->ev_done_valid[i] = false, b->tab_call[i] = 0;
-      b->done_call = 0;
-      if (want > 0u) {
-        uint32_t chain_mask[8], main_mask[8];
-        for (uint32_t wd = 0; wd < 8; ++wd) {
-          chain_mask[wd] = 0u;
-          for (uint32_t bit = 0; bit < 32; ++bit)
-            if (wd * 32u + bit < 8u * want) chain_mask[wd] |= 1u << bit;
-          main_mask[wd] = ~chain_mask[wd];
-        }
-        if (hipExtStreamCreateWithCUMask(&b->nco_masked, 8, chain_mask) == hipSuccess &&
-            hipExtStreamCreateWithCUMask(&b->cs_masked, 8, main_mask) == hipSuccess) {
-          b->reserve_r = want;
-        } else {
-          XL_LOG_ERR("CU-masked streams are not available (%s): the NCO chain kernel shares the chip", hipGetErrorString(hipGetLastError()));
-          if (b->cs_masked) (void)hipStreamDestroy(b->cs_masked);
-          if (b->nco_masked) (void)hipStreamDestroy(b->nco_masked);
-          b->cs_masked = b->nco_masked = nullptr;
-        }
-      }
-    }
+    b->macs_all = xl_direct_macs(b->classes);
+    b->macs_rest = xl_direct_macs(b->classes_rest);
+    const char *exp_reserve = xl_exp_getenv("XL_EXP_RESERVE");
+    const XlReserve rv = xl_reserve_want(o, b->nco.size(), b->classes_rest, b->poly, b->macs_all, b->macs_rest, b->reserve_band,
+                                         xl_exp_getenv("XL_EXP_NOMASK") != nullptr, xl_exp_getenv("XL_EXP_ROUNDS1") != nullptr,
+                                         exp_reserve ? atoi(exp_reserve) : -1);
+    b->reserve_band = rv.band;
+    if (xl_reserve_recreate(rv.want, b->reserve_r)) xl_batch_reserve_cus(b, rv.want);
   }
 
   lap("masked streams");
@@ -1518,29 +1007,7 @@ static int xl_batch_plan(xlating_batch *b) {
   }
   XL_TRY(xl_plan_alloc(b, (void **)&b->d_nco, b->nco.size() * sizeof(XlNcoClient)));
   XL_TRY(hipMemcpy(b->d_nco, b->nco.data(), b->nco.size() * sizeof(XlNcoClient), hipMemcpyHostToDevice));
-  if (!b->wide.empty()) {  // wide clients: descriptors and tap images
-    std::vector<float> wt;
-    std::vector<double> wq;
-    size_t k = 0;
-    for (size_t i = 0; i < b->clients.size(); ++i) {
-      const Client &c = b->clients[i];
-      if (!c.alive || !c.wide) continue;
-      XlWideClient &w = b->wide[k++];
-      w.tap_off = (uint32_t)(wt.size() / 2);
-      wt.insert(wt.end(), c.rt.begin(), c.rt.end());
-      w.qtap_off = (uint32_t)(wq.size() / 2);
-      if (b->fmt != XL_FMT_CF32)
-        for (int16_t q : c.rtq) wq.push_back((double)q);
-    }
-    XL_TRY(xl_plan_alloc(b, (void **)&b->d_wide, b->wide.size() * sizeof(XlWideClient)));
-    XL_TRY(hipMemcpy(b->d_wide, b->wide.data(), b->wide.size() * sizeof(XlWideClient), hipMemcpyHostToDevice));
-    XL_TRY(xl_plan_alloc(b, (void **)&b->d_wtaps, wt.size() * sizeof(float)));
-    XL_TRY(hipMemcpy(b->d_wtaps, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!wq.empty()) {
-      XL_TRY(xl_plan_alloc(b, (void **)&b->d_wqtaps, wq.size() * sizeof(double)));
-      XL_TRY(hipMemcpy(b->d_wqtaps, wq.data(), wq.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-  }
+  if (!b->wide.empty() && xl_upload_wide(b) != 0) goto fail;
   if (!b->poly.empty()) {
     if (xl_upload_launch_set(b, b->launches_rest, image_rest, &b->d_taps_rest, nullptr) != 0) goto fail;
   }
@@ -1568,7 +1035,7 @@ static int xl_batch_plan(xlating_batch *b) {
       XL_TRY(hipMalloc((void **)&b->d_phase_run, b->phase_cap * sizeof(float2)));
       b->phase_run_cap = b->phase_cap;
     }
-    for (const Pending &pd : pending)
+    for (const XlPolyPending &pd : pending)
       if (xl_poly_sync_device(b, b->poly[pd.idx], pd.new_cols, pd.fresh, cap_samples) != 0) goto fail;
   }
   lap("polyphase images + R kernel");
@@ -1794,19 +1261,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
     if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[hb], d_blocks, b->max_window, N, b->bps, b->d_whist[hn], s));
     if (record_ev) XL_TRY(hipEventRecord(record_ev, s));
     b->poisoned = false;
-    for (Client &c : b->clients) {
-      if (!c.alive) continue;
-      const uint32_t j0 = (uint32_t)((c.D - c.consumed % c.D) % c.D);
-      c.last_Kg.resize(G);
-      uint32_t prev = 0;
-      for (uint32_t g = 1; g <= G; ++g) {
-        const uint32_t ms = xl_grid_mstart(j0, c.D, (uint32_t)S, g);
-        c.last_Kg[g - 1] = ms - prev;
-        prev = ms;
-      }
-      c.last_K = prev;
-      c.consumed += N;
-    }
+    xl_clients_commit(b->clients, (uint32_t)S, G);
     b->trel += N;
     b->ocur = p;
     b->hcur = hn;
@@ -2195,19 +1650,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
     if (record_ev && !record_attached) XL_TRY(hipEventRecord(record_ev, s));
     // ---- everything is enqueued: commit the host-side state of the call
     b->poisoned = false;
-    for (Client &c : b->clients) {
-      if (!c.alive) continue;
-      const uint32_t j0 = (uint32_t)((c.D - c.consumed % c.D) % c.D);
-      c.last_Kg.resize(G);
-      uint32_t prev = 0;
-      for (uint32_t g = 1; g <= G; ++g) {
-        const uint32_t ms = xl_grid_mstart(j0, c.D, (uint32_t)S, g);
-        c.last_Kg[g - 1] = ms - prev;
-        prev = ms;
-      }
-      c.last_K = prev;
-      c.consumed += N;
-    }
+    xl_clients_commit(b->clients, (uint32_t)S, G);
     b->trel += N;
     b->pcur = pcur;
     b->tab = tab;

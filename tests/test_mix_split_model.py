@@ -80,7 +80,7 @@ def _mix_halves(X, R, xscale, rscale, flush_subnormals=False):
 def test_two_half_split_mix_is_as_good_as_the_fp32_chain(seed):
     X, R, L = _operands(seed)
     Yex = np.einsum("sbm,bm->sm", X.astype(np.complex128), R.astype(np.complex128))
-    rscale = 2.0 ** np.floor(np.log2(8192.0 / L))  # xl_poly_col_scale (xl_batch.cpp): the bound of the branch spectra under XLP_H_RMAX
+    rscale = 2.0 ** np.floor(np.log2(8192.0 / L))  # xl_poly_col_scale (xl_plan.cpp): the bound of the branch spectra under XLP_H_RMAX
     assert np.abs(R).max() * rscale <= 8192.0 and np.abs(X).max() * 128.0 < 65504.0
     e32 = _err(_mix_fp32_chain(X, R), Yex)
     eh = _err(_mix_halves(X, R, 128.0, rscale), Yex)

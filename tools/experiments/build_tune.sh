@@ -10,7 +10,7 @@ hipcc $FLAGS -fno-slp-vectorize -c $C/xl_mixh.hip -o $V/tune_xl_mixh.o &
 hipcc $FLAGS -fno-slp-vectorize -c $C/xl_mixh2.hip -o $V/tune_xl_mixh2.o &
 wait
 OBJS=""
-for o in xl_kernels xl_polyphase xl_inv8 xl_inv32 xl_mixf32 xl_mixh xl_mixh2 xl_filter xl_batch xl_sinks xl_common lpf xl_taps xl_wire; do
+for o in xl_kernels xl_polyphase xl_inv8 xl_inv32 xl_mixf32 xl_mixh xl_mixh2 xl_filter xl_batch xl_plan xl_sinks xl_common lpf xl_taps xl_wire; do
   case $o in xl_batch|xl_mixh|xl_mixh2) OBJS="$OBJS $V/tune_$o.o";; *) OBJS="$OBJS $B/$o.o";; esac
 done
 hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libtune.so $OBJS -lm -lz -lpthread
