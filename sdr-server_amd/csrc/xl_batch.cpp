@@ -71,9 +71,7 @@ struct xlating_batch_t {
   hipStream_t last_stream = nullptr;  // caller stream of the latest call
   hipEvent_t dep_ev = nullptr;        // orders a call on a new stream behind the previous call's stream
   // Side-stream NCO chain (calls of several blocks): the next call's phase table is tabulated by xl_nco_chain_kernel on
-  // nco_stream while this call's launches run on the caller's stream.  ev_chain[t]: the tabulation of table t is complete (the
-  // caller's stream waits for it before the first launch that reads the table); ev_done[t]: the launches that read
-  // table t have been passed by the caller's stream (nco_stream waits for it before overwriting that table).
+  // nco_stream while this call's launches run on the caller's stream (the look-ahead state below).
   hipStream_t nco_stream = nullptr;
   // CU reservation: the chain kernel needs whole CUs (one wave per SIMD) and finds them only if nothing else is resident
   // there -- behind a launch that fills the chip its workgroups waited for the next kernel boundary (measured: chain
@@ -81,25 +79,11 @@ struct xlating_batch_t {
   // mask of `reserve_r` CUs per XCD (mask bit b = XCD b % 8, CU b / 8 of it; tools/ubench_cumask.hip) and the engine's
   // own compute stream for side-stream calls, cs_masked, with the complement.  Callers that pass XL_STREAM_ENGINE get it.
   hipStream_t cs_masked = nullptr;
-  hipStream_t last_nco = nullptr;    // the side stream of the latest chain launch
   unsigned long long *d_chain_stats = nullptr;  // tuning (XL_EXP_CHAIN_STATS): per chain workgroup cycles / ticks of the latest launch
   hipStream_t nco_masked = nullptr;  // the side stream that goes with cs_masked; nco_stream (unmasked) serves callers' own streams
   uint32_t reserve_r = 0;
   int reserve_band = -1;  // band of the reservation rule the latest plan was in (xl_chain_band; -1: none yet): hysteresis at the band edges
   uint32_t expected_clients = 0;  // option "expected_clients": the CUs are reserved for this many clients from the first plan on
-  hipEvent_t ev_chain[XL_NTAB] = {}, ev_done[XL_NTAB] = {};  // per phase table
-  bool ev_done_valid[XL_NTAB] = {};
-  hipStream_t ev_done_stream[XL_NTAB] = {};  // where ev_done[t] was recorded
-  // Round 4: a launch that carries a completion event keeps the queue ~8 us from starting the next launch (a fifth of a one-block
-  // call), and in the steady side-stream pattern only ONE call in `chain_calls` needs its event: a chain launch made at call k
-  // overwrites the tables last read by calls k-7 .. k-4, and call k-4 is the previous chain-launching call.  So side-stream calls
-  // record ev_done only when they launch a chain; tab_call[] / done_call let a chain launch check that the latest recorded event
-  // post-dates every reader of its tables (calls run in order: an event behind call j covers all calls <= j), and fall back to an
-  // event recorded on the spot when it does not (irregular patterns only).
-  uint64_t tab_call[XL_NTAB] = {};  // ncalls + 1 of the latest call that read table t (0: never)
-  uint64_t done_call = 0;           // ncalls + 1 of the latest call that recorded an ev_done (0: none)
-  int done_tab = 0;                 // ... and which one
-  bool spec_on_side = false;  // the look-ahead table was produced on nco_stream (ev_chain must be waited for)
   double macs_all = 0.0, macs_rest = 0.0;  // complex MACs per sample of a block: all clients' direct launches / those outside `poly`
   int nco_side = -1;          // option "nco_side_stream": 1 always, 0 never (NCO role inside the launches), -1: calls of >= 2 blocks
   bool poisoned = false;              // a launch failed mid-call: device state is undefined, every later call fails
@@ -136,7 +120,6 @@ struct xlating_batch_t {
   bool poly_min_set = false;        // "polyphase_min_clients" was given: it holds for every class (else 32 where the mix runs on the matrix cores)
   uint32_t poly_min_clients = 32;   // XL_EXP_POLY_MIN (tuning): smallest class that takes the polyphase path under the size rule
   uint32_t poly_m = 0;        // option "polyphase_m": force the transform length (64 / 128 / 256); 0 = by the size rule
-  int num_cus = 256;
   uint32_t inv_reg = 0;       // option "inverse_kernel", M = 128 classes: 0 (default) = by the launch's size (xlp_inverse_pick: the 8-lane kernel
                               // for launches of up to 2048 tiles, the LDS transform up to 8192, the 32 x 4 cut beyond), 5 = always eight lanes per column, 16- and
                               // 8-point transforms in registers (xl_inv8.hip), 6 = always the 32 x 4 cut (xl_inv32.hip: 32-point transforms
@@ -181,12 +164,6 @@ struct xlating_batch_t {
   short2 *d_qphtab = nullptr;  // Q15 phase table (every XL_PH_STRIDE-th phase)
   bool last_q15 = false;       // the latest call produced cs16 outputs
   XlNcoClient *d_nco = nullptr;
-  // Rings of XL_NTAB phase buffers and phase tables: [pcur] = committed running phases, [pcur + 1] = after the next call,
-  // [pcur + 2] = after the one behind it (a chain launch may tabulate two calls ahead); table [tab] = the latest call's.
-  float2 *d_phase[XL_NTAB] = {};
-  int pcur = 0;
-  size_t phase_cap = 0;
-  float2 *d_phtab[XL_NTAB] = {};
   float2 *d_out[2] = {nullptr, nullptr};
   int ocur = 0;  // d_out[ocur] holds the latest call's outputs
   size_t out_alloc = 0;
@@ -194,6 +171,12 @@ struct xlating_batch_t {
   size_t h_out_alloc = 0;
   bool fetched = false;
 
+  // Rings of XL_NTAB phase buffers and phase tables: [pcur] = committed running phases, [pcur + 1] = after the next call,
+  // [pcur + 2] = after the one behind it (a chain launch may tabulate two calls ahead); table [tab] = the latest call's.
+  float2 *d_phase[XL_NTAB] = {};
+  int pcur = 0;
+  size_t phase_cap = 0;
+  float2 *d_phtab[XL_NTAB] = {};
   int tab = 0;              // table used by the latest call
   // Look-ahead: tables [tab + 1] .. [tab + spec_n] hold the phases of the next spec_n calls assuming spec_S samples x
   // spec_G blocks each (the phases after them: d_phase[pcur + 1 ..]); produced by the latest call's launches (spec_n = 1)
@@ -201,6 +184,22 @@ struct xlating_batch_t {
   int spec_n = 0;
   uint32_t spec_S = 0, spec_G = 0, spec_flags = 0;
   int spec_ev = 0;
+  bool spec_on_side = false;  // the look-ahead table was produced on nco_stream (ev_chain must be waited for)
+  hipStream_t last_nco = nullptr;  // the side stream of the latest chain launch
+  // ev_chain[t]: the tabulation of table t is complete (the caller's stream waits for it before the first launch that reads the
+  // table); ev_done[t]: the launches that read table t have been passed by the caller's stream (nco_stream waits for it before
+  // overwriting that table).
+  hipEvent_t ev_chain[XL_NTAB] = {}, ev_done[XL_NTAB] = {};  // per phase table
+  bool ev_done_valid[XL_NTAB] = {};
+  // Round 4: a launch that carries a completion event keeps the queue ~8 us from starting the next launch (a fifth of a one-block
+  // call), and in the steady side-stream pattern only ONE call in `chain_calls` needs its event: a chain launch made at call k
+  // overwrites the tables last read by calls k-7 .. k-4, and call k-4 is the previous chain-launching call.  So side-stream calls
+  // record ev_done only when they launch a chain; tab_call[] / done_call let a chain launch check that the latest recorded event
+  // post-dates every reader of its tables (calls run in order: an event behind call j covers all calls <= j), and fall back to an
+  // event recorded on the spot when it does not (irregular patterns only).
+  uint64_t tab_call[XL_NTAB] = {};  // ncalls + 1 of the latest call that read table t (0: never)
+  uint64_t done_call = 0;           // ncalls + 1 of the latest call that recorded an ev_done (0: none)
+  int done_tab = 0;                 // ... and which one
   bool waited_valid = false;  // stream waited_stream has waited for ev_chain[waited_ev] since that event was last recorded
   int waited_ev = 0;
   hipStream_t waited_stream = nullptr;
@@ -481,7 +480,8 @@ extern "C" int xlating_batch_create_grouped(uint32_t sampling_freq, int input_fo
     const size_t bbytes = (size_t)b->max_samples * b->gcap * b->bps + 16;
     XL_TRY(hipSetDevice(dev));
     XL_TRY(hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
-    if (hipDeviceGetAttribute(&b->num_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || b->num_cus <= 0) b->num_cus = 256;
+    int cus = 0;  // (nothing reads the count at present; the query stays among the runtime calls that create makes)
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     XL_TRY(hipEventCreateWithFlags(&b->dep_ev, hipEventDisableTiming));
     XL_TRY(hipStreamCreateWithFlags(&b->nco_stream, hipStreamNonBlocking));
     for (int i = 0; i < XL_NTAB; ++i) {
@@ -1117,563 +1117,561 @@ static uint32_t xl_batch_wide_maxk(const xlating_batch *b, const XlPos &pos) {
   return k;
 }
 
-static hipError_t xl_batch_wide_launch(xlating_batch *b, int mode, const void *d_blocks, uint32_t N, int hb, const XlPos &pos,
-                                       uint32_t maxKw, const float2 *phtab, float2 *out, hipStream_t s) {
+#define XL_STREAM_ENGINE_P (reinterpret_cast<hipStream_t>((intptr_t)-1))
+
+// What one call is given, decides and carries from stage to stage (xl_batch_run).
+struct XlCall {
+  // inputs
+  const void *d_blocks;
+  size_t S;    // samples per block
+  unsigned G;  // blocks
+  uint32_t N;  // S * G
+  int mode;    // normalised: the x86 variants are XL_MODE_OPTIMIZED with their flags in pos.pad
+  XlPos pos;
+  hipStream_t s;
+  hipEvent_t wait_ev, record_ev;
+  // decisions
+  uint32_t maxK, maxKw;  // the most outputs any client / any wide client (a launch of their own) produces in this call
+  bool use_poly, side, fuse;
+  int p;  // parity of this call: output buffer
+  int hb, hn, tab, pcur, chain_ev;
+  int spec_left;  // look-ahead calls that stay valid behind this one (a chain launch covers up to two)
+  bool tab_from_s;
+  // does this call record ev_done[tab]?  Side-stream calls: only the ones that launch a chain (see tab_call); non-side calls
+  // after a side stream was used: always
+  bool want_done;
+  // running flags
+  bool chain_wait;  // this call's table comes from the side stream: wait for it before the first reader
+  bool rolled, nco_fused;
+  bool done_attached;    // ev_done[tab] rides on the call's last launch
+  bool record_attached;  // the caller's record_ev rides on the last launch instead (no ev_done wanted there)
+  int launched_n;
+  hipEvent_t f0, f1;  // timing: around the call's launches
+  bool ended;         // xl_call_begin ended the call: it returns `ret`
+  int ret;
+};
+
+#define XL_STAGE static inline __attribute__((always_inline))  // stages and their helpers: one caller's body, cut for reading only
+// A stage returns 0, or nonzero after a failed HIP call (xl_batch_run maps it).  xl_call_begin may also end the call on its own:
+// a refusal's errno, or 0 for an engine without clients.
+XL_STAGE int xl_call_end(XlCall &c, int ret) {
+  c.ended = true, c.ret = ret;
+  return 0;
+}
+
+// The first reader of a table that came from the side stream waits for its chain launch, once per stream and launch.
+XL_STAGE hipError_t xl_call_chain_wait(xlating_batch *b, XlCall &c) {
+  if (!c.chain_wait) return hipSuccess;
+  const hipError_t e = hipStreamWaitEvent(c.s, b->ev_chain[c.chain_ev], 0);
+  if (e != hipSuccess) return e;
+  c.chain_wait = false;
+  b->waited_valid = true, b->waited_ev = c.chain_ev, b->waited_stream = c.s;
+  return hipSuccess;
+}
+
+// The first launch of a call also rolls the raw history into d_hist[hn] (XlFirArgs, XlpArgs).
+template <class Args>
+XL_STAGE void xl_call_roll_args(const xlating_batch *b, XlCall &c, Args &a) {
+  a.hist_out = b->d_hist[c.hn], a.hist_units = XL_HCAP * (b->bps / 2), a.block_units = c.N * (b->bps / 2);
+  c.rolled = true;
+}
+
+// A direct launch's arguments, as far as the float and the Q15 family fill them alike.
+XL_STAGE void xl_call_fir_args(const xlating_batch *b, const XlCall &c, const Launch &L, XlFirArgs &a) {
+  memset(&a, 0, sizeof(a));
+  a.in0 = b->d_hist[c.hb], a.n0 = XL_HCAP, a.in1 = c.d_blocks, a.n1 = c.N;
+  a.fmt = b->fmt, a.pos = c.pos;
+  a.groups = L.d_groups, a.ngroups = (uint32_t)L.groups.size(), a.ota = L.ota;
+  const uint32_t Kl = (c.N + L.minD - 1) / L.minD;  // (an upper bound of the launch's largest output count)
+  a.xtiles = (std::min(Kl, c.maxK) + L.ota - 1) / L.ota;
+  a.out = b->d_out[c.p];
+}
+
+// The wide clients' launch (see xl_batch_wide_maxk); Q15 calls pass no float table.
+static hipError_t xl_batch_wide_launch(xlating_batch *b, const XlCall &c, const float2 *phtab) {
   XlWideArgs w;
   memset(&w, 0, sizeof(w));
   const bool big = b->max_window != 0;
-  w.in0 = big ? b->d_whist[hb] : b->d_hist[hb];
+  w.in0 = big ? b->d_whist[c.hb] : b->d_hist[c.hb];
   w.n0 = w.hcap = big ? b->max_window : XL_HCAP;
-  w.in1 = d_blocks;
-  w.n1 = N;
-  w.fmt = b->fmt;
-  w.pos = pos;
-  w.clients = b->d_wide;
-  w.nclients = (uint32_t)b->wide.size();
-  w.xtiles = (maxKw + 63u) / 64u;
-  w.parts = mode == XL_MODE_OPTIMIZED ? xl_wide_parts(b->wide_tpad_max) : 1u;
-  w.taps = b->d_wtaps;
-  w.phtab = phtab;
-  w.out = out;
-  w.qtaps = b->d_wqtaps;
-  w.qphtab = b->d_qphtab;
-  return xl_launch_wide(mode == XL_MODE_Q15 ? 2 : (mode == XL_MODE_OPTIMIZED ? 1 : 0), w, s);
+  w.in1 = c.d_blocks, w.n1 = c.N;
+  w.fmt = b->fmt, w.pos = c.pos;
+  w.clients = b->d_wide, w.nclients = (uint32_t)b->wide.size();
+  w.xtiles = (c.maxKw + 63u) / 64u;
+  w.parts = c.mode == XL_MODE_OPTIMIZED ? xl_wide_parts(b->wide_tpad_max) : 1u;
+  w.taps = b->d_wtaps, w.phtab = phtab, w.out = b->d_out[c.p];
+  w.qtaps = b->d_wqtaps, w.qphtab = b->d_qphtab;
+  return xl_launch_wide(c.mode == XL_MODE_Q15 ? 2 : (c.mode == XL_MODE_OPTIMIZED ? 1 : 0), w, c.s);
 }
 
-// One call: G blocks of S samples each, contiguous at d_blocks.
-#define XL_STREAM_ENGINE_P (reinterpret_cast<hipStream_t>((intptr_t)-1))
+// Everything is enqueued: commit the host-side state of the call (both families).
+XL_STAGE void xl_call_commit(xlating_batch *b, const XlCall &c) {
+  b->poisoned = false;
+  xl_clients_commit(b->clients, (uint32_t)c.S, c.G);
+  b->trel += c.N, b->ocur = c.p, b->hcur = c.hn;
+  b->ncalls++, b->calls_since_plan++;
+}
 
-// One call: G blocks of S samples each, contiguous at d_blocks.  s_in: the caller's stream, or XL_STREAM_ENGINE_P = the
-// engine's own compute stream (the CU-masked one for calls whose NCO chain runs on the side stream).  wait_ev / record_ev:
-// optional events of the caller, waited for before / recorded after the call's work on that stream.
-static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len, unsigned G, int mode, hipStream_t s_in,
-                        hipEvent_t wait_ev = nullptr, hipEvent_t record_ev = nullptr) {
-  const size_t S = input_len / 2;
-  hipStream_t s = s_in;
+// XL_TUNING (XL_EXP_POLY_TRACE): arms the polyphase trace buffer in front of the one launch of a class that is traced, or
+// dumps it behind that launch.  (Plain builds trace nothing and never get here.)
+static hipError_t xl_ptrace(xlating_batch *b, XlpArgs &pa, hipStream_t s, bool arm) {
+#ifdef XL_TUNING
+  const size_t n = 32768;
+  if (!arm) return pa.trace = nullptr, xl_dump_trace(b->poly_trace, b->d_ptrace, n, s);
+  hipError_t e = b->d_ptrace ? hipSuccess : hipMalloc((void **)&b->d_ptrace, n * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemsetAsync(b->d_ptrace, 0, n * sizeof(unsigned long long), s);
+  if (e == hipSuccess) pa.trace = b->d_ptrace;
+  return e;
+#else
+  return hipSuccess;
+#endif
+}
+
+// Stage 1: checks, re-plan, what runs where, the stream.
+XL_STAGE int xl_call_begin(xlating_batch *b, XlCall &c) {
+  const size_t S = c.S;
+  const unsigned G = c.G;
   if (S > b->max_samples || G < 1 || G > b->gcap ||
-      (mode != XL_MODE_NATIVE && mode != XL_MODE_OPTIMIZED && mode != XL_MODE_Q15 && mode != XL_MODE_OPTIMIZED_X86 &&
-       mode != XL_MODE_OPTIMIZED_X86_FMA) ||
-      (mode == XL_MODE_Q15 && b->fmt == XL_FMT_CF32))
-    return -EINVAL;
+      (c.mode != XL_MODE_NATIVE && c.mode != XL_MODE_OPTIMIZED && c.mode != XL_MODE_Q15 && c.mode != XL_MODE_OPTIMIZED_X86 &&
+       c.mode != XL_MODE_OPTIMIZED_X86_FMA) ||
+      (c.mode == XL_MODE_Q15 && b->fmt == XL_FMT_CF32))
+    return xl_call_end(c, -EINVAL);
   // the x86 AVX build's optimized variant = the optimized arithmetic with the phase never renormalised (xlating.c:338-339):
   // the stream position carries the flag to every kernel that walks phases (xl_grid.h: XL_POS_NORENORM)
-  const uint32_t pos_flags = mode == XL_MODE_OPTIMIZED_X86 ? XL_POS_NORENORM
-                             : (mode == XL_MODE_OPTIMIZED_X86_FMA ? (XL_POS_NORENORM | XL_POS_FMA_STEP) : 0u);
-  if (mode == XL_MODE_OPTIMIZED_X86 || mode == XL_MODE_OPTIMIZED_X86_FMA) mode = XL_MODE_OPTIMIZED;
-  if (mode == XL_MODE_Q15 && !b->want_q15) {  // (the Q15 tap image is built from the first Q15 call on)
+  const uint32_t pos_flags = c.mode == XL_MODE_OPTIMIZED_X86 ? XL_POS_NORENORM
+                             : (c.mode == XL_MODE_OPTIMIZED_X86_FMA ? (XL_POS_NORENORM | XL_POS_FMA_STEP) : 0u);
+  if (c.mode == XL_MODE_OPTIMIZED_X86 || c.mode == XL_MODE_OPTIMIZED_X86_FMA) c.mode = XL_MODE_OPTIMIZED;
+  if (c.mode == XL_MODE_Q15 && !b->want_q15) {  // (the Q15 tap image is built from the first Q15 call on)
     b->want_q15 = true;
     b->all_built = false;
   }
-  if (b->poisoned) return -EIO;
+  if (b->poisoned) return xl_call_end(c, -EIO);
   // a client that was still inside its zero-history when the plan was built may be mature by now: it then joins
   // the class of its grid (direct kernel) / its (D, T) class (polyphase) -- re-plan
   if (!b->dirty && b->planned_immature > 0)
-    for (const Client &c : b->clients)
-      if (c.alive && !c.planned_mature && xl_mature(c)) {
+    for (const Client &cl : b->clients)
+      if (cl.alive && !cl.planned_mature && xl_mature(cl)) {
         b->dirty = true;
         break;
       }
   if (!b->dirty && (uint64_t)b->trel + (uint64_t)S * G >= (1ull << 31)) b->dirty = true;  // re-base the classes' stream records
   if (b->dirty) {
     int rc = xl_batch_plan(b);
-    if (rc != 0) return rc;
+    if (rc != 0) return xl_call_end(c, rc);
   }
   if (G > 1 && S < b->plan_maxD && !b->nco.empty()) {
     XL_LOG_ERR("a call of %u blocks needs blocks of at least the largest decimation (%u samples); got %zu", G, b->plan_maxD, S);
-    return -EINVAL;
+    return xl_call_end(c, -EINVAL);
   }
-  XlPos pos;
-  pos.trel = b->trel;
-  pos.S = (uint32_t)S;
-  pos.G = G;
-  pos.pad = pos_flags;
+  c.pos.trel = b->trel, c.pos.S = (uint32_t)S, c.pos.G = G, c.pos.pad = pos_flags;
+  c.N = (uint32_t)(S * G);
+  c.p = (int)(b->ncalls & 1), c.hb = b->hcur, c.hn = b->hcur ^ 1;
   // optimized mode: the polyphase classes leave the direct launches (tiny calls stay direct: a segment is 128 or 256
   // branch samples whatever the call holds)
-  uint32_t maxK = 0;  // the most outputs any client produces in this call
-  for (const DirectClass &cs : b->classes) maxK = std::max(maxK, xl_grid_dyn(cs.D, cs.T, cs.rem0, cs.hv0, pos).K);
-  const uint32_t maxKw = xl_batch_wide_maxk(b, pos);  // (the wide clients: a launch of their own)
-  const bool use_poly = mode == XL_MODE_OPTIMIZED && !b->poly.empty() && maxK >= 2 * XLP_M_MAX;
-  if (!use_poly && !b->nco.empty()) {  // this call runs the all-clients launch set: build it if the plan has not yet
+  c.maxK = 0;
+  for (const DirectClass &cs : b->classes) c.maxK = std::max(c.maxK, xl_grid_dyn(cs.D, cs.T, cs.rem0, cs.hv0, c.pos).K);
+  c.maxKw = xl_batch_wide_maxk(b, c.pos);
+  c.use_poly = c.mode == XL_MODE_OPTIMIZED && !b->poly.empty() && c.maxK >= 2 * XLP_M_MAX;
+  if (!c.use_poly && !b->nco.empty()) {  // this call runs the all-clients launch set: build it if the plan has not yet
     int rc = xl_batch_build_all_set(b);
-    if (rc != 0) return rc;
+    if (rc != 0) return xl_call_end(c, rc);
   }
-  const bool light = xl_direct_is_light((use_poly ? b->macs_rest : b->macs_all) * (double)S);
-  // One-block calls (the reference's call granularity) on the polyphase path: the three launches are short since the mix runs on
-  // the matrix cores, and a slice of the recurrence inside each made every one of them last as long as its slice (1024 clients:
-  // 50.2 us per block; the chain kernel beside them, four calls per launch: 47.7; 128 clients: 40.4 -> 29.2; 4096: 129 -> 134,
-  // hence the limit)
-  const bool one_block_side = G == 1 && use_poly && b->nco.size() <= XL_SIDE_ONE_BLOCK_MAX;
-  const bool side_call = mode != XL_MODE_Q15 && (b->nco_side > 0 || (b->nco_side < 0 && (G >= 2 || one_block_side) && (use_poly || (light && b->cs_masked && s == XL_STREAM_ENGINE_P))));  // (a caller's own, unmasked stream would keep filling the chain's CUs)
-  if (s == XL_STREAM_ENGINE_P) s = (side_call && b->cs_masked) ? b->cs_masked : b->own_stream;
-  // Calls depend on each other through the engine's device state (history, phases, tables): a call on another stream than the
-  // previous one is ordered behind it.  (Overlapping consecutive one-block calls through two compute streams -- round 4's
-  // "pipeline_calls" -- cost this runtime more in cross-stream events than it gained: profiles/r04_one_block_pipelining.txt.)
-  if (s != b->last_stream) {
-    XL_TRY(hipEventRecord(b->dep_ev, b->last_stream));
-    XL_TRY(hipStreamWaitEvent(s, b->dep_ev, 0));
-  }
-  b->last_stream = s;
-  b->fetched = false;
-  if (wait_ev) XL_TRY(hipStreamWaitEvent(s, wait_ev, 0));
-  if (b->nco.empty()) {
-    if (record_ev) XL_TRY(hipEventRecord(record_ev, s));
-    return 0;
-  }
-
-  if (mode == XL_MODE_Q15) {
-    // ---- the Q15 family (xlating.c:92-140, 416-447): its own phase (never renormalised), the same raw history.  The
-    // float phases stay where they are; a float phase table tabulated ahead was for a call at this stream position and
-    // is dropped.
-    const int p = (int)(b->ncalls & 1);
-    const int hb = b->hcur, hn = b->hcur ^ 1;
-    const uint32_t N = (uint32_t)(S * G);
-    if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[b->spec_ev], 0));
-    b->spec_n = 0;
-    b->poisoned = true;
-    XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, (uint32_t)b->nco.size(), b->d_qphase, b->d_qphtab, pos, s));
-    bool rolled = false;
-    for (int lq = 0; lq < XL_NLAUNCH && maxK > 0; ++lq) {
-      Launch &L = b->launches[lq];
-      if (L.groups.empty()) continue;
-      XlFirArgs a;
-      memset(&a, 0, sizeof(a));
-      a.in0 = b->d_hist[hb];
-      a.n0 = XL_HCAP;
-      a.in1 = d_blocks;
-      a.n1 = N;
-      a.fmt = b->fmt;
-      a.pos = pos;
-      a.groups = L.d_groups;
-      a.ngroups = (uint32_t)L.groups.size();
-      a.ota = L.ota;
-      a.xtiles = (std::min((N + L.minD - 1) / L.minD, maxK) + L.ota - 1) / L.ota;
-      a.out = b->d_out[p];
-      if (!rolled) {
-        a.hist_out = b->d_hist[hn];
-        a.hist_units = XL_HCAP * (b->bps / 2);
-        a.block_units = N * (b->bps / 2);
-        rolled = true;
-      }
-      XL_TRY(xl_launch_fir_q15_batch(L.ct, L.nw, a, b->d_qtaps, b->d_qphtab, L.lds, s));
-    }
-    if (!rolled) XL_TRY(xl_launch_update_history(b->d_hist[hb], d_blocks, XL_HCAP, N, b->bps, b->d_hist[hn], s));
-    if (maxKw > 0) XL_TRY(xl_batch_wide_launch(b, XL_MODE_Q15, d_blocks, N, hb, pos, maxKw, nullptr, b->d_out[p], s));
-    if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[hb], d_blocks, b->max_window, N, b->bps, b->d_whist[hn], s));
-    if (record_ev) XL_TRY(hipEventRecord(record_ev, s));
-    b->poisoned = false;
-    xl_clients_commit(b->clients, (uint32_t)S, G);
-    b->trel += N;
-    b->ocur = p;
-    b->hcur = hn;
-    b->ncalls++;
-    b->calls_since_plan++;
-    b->last_q15 = true;
-    return 0;
-  }
-  b->last_q15 = false;
-
   {
-    const int p = (int)(b->ncalls & 1);  // parity of this call: output buffer
-    const int hb = b->hcur, hn = b->hcur ^ 1;
-    const uint32_t N = (uint32_t)(S * G);
+    const bool light = xl_direct_is_light((c.use_poly ? b->macs_rest : b->macs_all) * (double)S);
     // Who tabulates the NEXT call's phases: the NCO role inside this call's launches (fuse), or xl_nco_chain_kernel on
     // the side stream, concurrently with them (side).  The side stream pays for calls of several blocks on the
     // polyphase path, whose three launches are short against the chain (measured, 8 blocks per call: 42.7 -> 36.8 us per
     // block at 1024 clients, 30.7 -> 28.8 at 128); a direct FIR launch hides the chain in its spare waves for free and
     // would only lose the chain kernel's CUs (1024 clients, native: 203 -> 212 us per block), and with one block per
     // call the cross-stream events cost more than the overlap gains (51.3 -> 58.6).
-    const bool side = side_call;
-    bool nco_fused = false;
-    bool chain_wait = false;  // this call's table comes from the side stream: wait for it before the first reader
+    // One-block calls (the reference's call granularity) on the polyphase path: the three launches are short since the mix runs on
+    // the matrix cores, and a slice of the recurrence inside each made every one of them last as long as its slice (1024 clients:
+    // 50.2 us per block; the chain kernel beside them, four calls per launch: 47.7; 128 clients: 40.4 -> 29.2; 4096: 129 -> 134,
+    // hence the limit)
+    const bool one_block_side = G == 1 && c.use_poly && b->nco.size() <= XL_SIDE_ONE_BLOCK_MAX;
+    c.side = c.mode != XL_MODE_Q15 && (b->nco_side > 0 || (b->nco_side < 0 && (G >= 2 || one_block_side) && (c.use_poly || (light && b->cs_masked && c.s == XL_STREAM_ENGINE_P))));  // (a caller's own, unmasked stream would keep filling the chain's CUs)
+  }
+  if (c.s == XL_STREAM_ENGINE_P) c.s = (c.side && b->cs_masked) ? b->cs_masked : b->own_stream;
+  // Calls depend on each other through the engine's device state (history, phases, tables): a call on another stream than the
+  // previous one is ordered behind it.  (Overlapping consecutive one-block calls through two compute streams -- round 4's
+  // "pipeline_calls" -- cost this runtime more in cross-stream events than it gained: profiles/r04_one_block_pipelining.txt.)
+  if (c.s != b->last_stream) {
+    XL_TRY(hipEventRecord(b->dep_ev, b->last_stream));
+    XL_TRY(hipStreamWaitEvent(c.s, b->dep_ev, 0));
+  }
+  b->last_stream = c.s;
+  b->fetched = false;
+  if (c.wait_ev) XL_TRY(hipStreamWaitEvent(c.s, c.wait_ev, 0));
+  if (b->nco.empty()) {
+    if (c.record_ev) XL_TRY(hipEventRecord(c.record_ev, c.s));
+    return xl_call_end(c, 0);
+  }
+  return 0;
+fail:
+  return 1;
+}
 
-    // ---- this call's phase table: tabulated ahead by the previous call's launches if the shape guess was right
-    const int tab = xl_nx(b->tab);
-    int pcur = b->pcur;
-    int spec_left = 0;  // look-ahead calls that stay valid behind this one (a chain launch covers up to two)
-    const int chain_ev = b->spec_ev;
-    bool tab_from_s = true;
-    if (b->spec_n > 0 && b->spec_S == S && b->spec_G == G && b->spec_flags == pos_flags) {
-      tab_from_s = !b->spec_on_side;
-      // (the second call of a chain launch's pair: this stream has already waited for that launch)
-      chain_wait = b->spec_on_side && !(b->waited_valid && b->waited_ev == chain_ev && b->waited_stream == s);
-      spec_left = b->spec_n - 1;
-    } else {
-      // (a look-ahead of the wrong shape may still be running on the side stream, on these very buffers)
-      if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[chain_ev], 0));
-      if (b->spec_n > 0) b->chain_ahead = 1;  // (a wrong guess: look less far ahead until the guesses hold again)
-      if (b->ev_done_valid[tab]) XL_TRY(hipStreamWaitEvent(s, b->ev_done[tab], 0));  // (same stream normally: a no-op)
-      XL_TRY(xl_batch_nco(b, pos, tab, s));
-    }
-    pcur = xl_nx(pcur);  // the phases written by that tabulation are now the committed ones
-    b->spec_n = 0;       // (from here on a failure poisons the engine)
-    b->poisoned = true;
-    // (with a look-ahead table still in hand the launches carry no NCO role: the call after this one has its table)
+// Stage 2: the Q15 family (xlating.c:92-140, 416-447), a whole call: its own phase (never renormalised), the same raw
+// history.  The float phases stay where they are; a float phase table tabulated ahead was for a call at this stream
+// position and is dropped.
+XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
+  hipStream_t s = c.s;
+  if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[b->spec_ev], 0));
+  b->spec_n = 0;
+  b->poisoned = true;
+  XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, (uint32_t)b->nco.size(), b->d_qphase, b->d_qphtab, c.pos, s));
+  for (int lq = 0; lq < XL_NLAUNCH && c.maxK > 0; ++lq) {
+    Launch &L = b->launches[lq];
+    if (L.groups.empty()) continue;
+    XlFirArgs a;
+    xl_call_fir_args(b, c, L, a);
+    if (!c.rolled) xl_call_roll_args(b, c, a);
+    XL_TRY(xl_launch_fir_q15_batch(L.ct, L.nw, a, b->d_qtaps, b->d_qphtab, L.lds, s));
+  }
+  if (!c.rolled) XL_TRY(xl_launch_update_history(b->d_hist[c.hb], c.d_blocks, XL_HCAP, c.N, b->bps, b->d_hist[c.hn], s));
+  if (c.maxKw > 0) XL_TRY(xl_batch_wide_launch(b, c, nullptr));
+  if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[c.hb], c.d_blocks, b->max_window, c.N, b->bps, b->d_whist[c.hn], s));
+  if (c.record_ev) XL_TRY(hipEventRecord(c.record_ev, s));
+  xl_call_commit(b, c);
+  b->last_q15 = true;
+  return 0;
+fail:
+  return 1;
+}
+
+// Stage 3: this call's phase table: tabulated ahead by the previous call's launches if the shape guess was right.
+XL_STAGE int xl_call_table(xlating_batch *b, XlCall &c) {
+  hipStream_t s = c.s;
+  c.tab = xl_nx(b->tab), c.pcur = b->pcur, c.chain_ev = b->spec_ev;
+  c.tab_from_s = true;
+  if (b->spec_n > 0 && b->spec_S == c.S && b->spec_G == c.G && b->spec_flags == c.pos.pad) {
+    c.tab_from_s = !b->spec_on_side;
+    // (the second call of a chain launch's pair: this stream has already waited for that launch)
+    c.chain_wait = b->spec_on_side && !(b->waited_valid && b->waited_ev == c.chain_ev && b->waited_stream == s);
+    c.spec_left = b->spec_n - 1;
+  } else {
+    // (a look-ahead of the wrong shape may still be running on the side stream, on these very buffers)
+    if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[c.chain_ev], 0));
+    if (b->spec_n > 0) b->chain_ahead = 1;  // (a wrong guess: look less far ahead until the guesses hold again)
+    if (b->ev_done_valid[c.tab]) XL_TRY(hipStreamWaitEvent(s, b->ev_done[c.tab], 0));  // (same stream normally: a no-op)
+    XL_TRY(xl_batch_nco(b, c.pos, c.tab, s));
+  }
+  c.pcur = xl_nx(c.pcur);  // the phases written by that tabulation are now the committed ones
+  b->spec_n = 0;           // (from here on a failure poisons the engine)
+  b->poisoned = true;
+  // (with a look-ahead table still in hand the launches carry no NCO role: the call after this one has its table)
 #ifdef XL_TUNING
-    const bool fuse = !side && spec_left == 0 && !b->exp_nofuse;  // tuning: tabulate by a launch of its own before every call
+  c.fuse = !c.side && c.spec_left == 0 && !b->exp_nofuse;  // tuning: tabulate by a launch of its own before every call
 #else
-    const bool fuse = !side && spec_left == 0;
+  c.fuse = !c.side && c.spec_left == 0;
 #endif
-    int launched_n = 0;
+  return 0;
+fail:
+  return 1;
+}
 
-    // ---- side stream: the NEXT call's table (same shape assumed) into table[tab ^ 1], concurrently with the launches
-    // below.  That table was last read by the previous call's launches (ev_done), the committed phases d_phase[pcur]
-    // were written by the tabulation of THIS call's table (earlier on the same side stream, or on `s`: ordered below).
-    if (side && spec_left == 0) {
-      // (the CU-masked pair of streams goes together: a chain kernel confined to CUs that the caller's own, unmasked
-      // stream keeps filling would wait for kernel boundaries)
-      hipStream_t ns = (s == b->cs_masked && b->nco_masked) ? b->nco_masked : b->nco_stream;
-      if (ns != b->last_nco) {  // consecutive chains depend on each other through the phase buffers
-        if (b->last_nco) {
-          XL_TRY(hipEventRecord(b->dep_ev, b->last_nco));
-          XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
-        }
-        b->last_nco = ns;
-      }
-      if (tab_from_s) {  // this call's table was tabulated on `s` (just now, or by the previous call's launches): order the side stream behind it
-        XL_TRY(hipEventRecord(b->dep_ev, s));
+// Stage 4 (side-stream calls without a look-ahead table left): the NEXT call's table (same shape assumed) into
+// table[tab ^ 1], concurrently with the launches of the stages below.  That table was last read by the previous call's
+// launches (ev_done), the committed phases d_phase[pcur] were written by the tabulation of THIS call's table (earlier on
+// the same side stream, or on `s`: ordered below).
+XL_STAGE int xl_call_chain(xlating_batch *b, XlCall &c) {
+  hipStream_t s = c.s;
+  // (the CU-masked pair of streams goes together: a chain kernel confined to CUs that the caller's own, unmasked
+  // stream keeps filling would wait for kernel boundaries)
+  hipStream_t ns = (s == b->cs_masked && b->nco_masked) ? b->nco_masked : b->nco_stream;
+  if (ns != b->last_nco) {  // consecutive chains depend on each other through the phase buffers
+    if (b->last_nco) {
+      XL_TRY(hipEventRecord(b->dep_ev, b->last_nco));
+      XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
+    }
+    b->last_nco = ns;
+  }
+  if (c.tab_from_s) {  // this call's table was tabulated on `s` (just now, or by the previous call's launches): order the side stream behind it
+    XL_TRY(hipEventRecord(b->dep_ev, s));
+    XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
+  }
+  XlChainCalls cc;
+  memset(&cc, 0, sizeof(cc));
+  cc.n = (uint32_t)std::min<int>(std::max(std::min(b->chain_calls, b->chain_ahead), 1), (int)XL_CHAIN_MAXCALLS);
+  b->chain_ahead = std::min(2 * b->chain_ahead, (int)XL_CHAIN_MAXCALLS);  // (this launch is made because the previous one's calls were all used)
+  int tt[XL_CHAIN_MAXCALLS];
+  for (int i = 0, t = c.tab, pp = c.pcur; i < (int)cc.n; ++i) {
+    t = xl_nx(t), pp = xl_nx(pp);
+    cc.tab[i] = b->d_phtab[t];
+    cc.state_out[i] = b->d_phase[pp];
+    tt[i] = t;
+  }
+  // the tables' last readers (XL_NTAB - 1 - i calls back): one wait for the latest of them covers the earlier ones that
+  // were recorded on the same stream (every wait is a queue packet of its own, ~4 us in front of the chain launch)
+  {
+    uint64_t need = 0;  // the latest call that read one of these tables
+    for (int i = 0; i < (int)cc.n; ++i) need = std::max(need, b->tab_call[tt[i]]);
+    if (need != 0) {
+      if (b->done_call >= need) {
+        XL_TRY(hipStreamWaitEvent(ns, b->ev_done[b->done_tab], 0));
+      } else if (!c.tab_from_s) {  // (tab_from_s: the side stream was just ordered behind everything on `s`)
+        XL_TRY(hipEventRecord(b->dep_ev, s));  // all earlier calls' launches precede this point of `s`
         XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
       }
-      XlChainCalls cc;
-      memset(&cc, 0, sizeof(cc));
-      cc.n = (uint32_t)std::min<int>(std::max(std::min(b->chain_calls, b->chain_ahead), 1), (int)XL_CHAIN_MAXCALLS);
-      b->chain_ahead = std::min(2 * b->chain_ahead, (int)XL_CHAIN_MAXCALLS);  // (this launch is made because the previous one's calls were all used)
-      int tt[XL_CHAIN_MAXCALLS];
-      for (int i = 0, t = tab, pp = pcur; i < (int)cc.n; ++i) {
-        t = xl_nx(t), pp = xl_nx(pp);
-        cc.tab[i] = b->d_phtab[t];
-        cc.state_out[i] = b->d_phase[pp];
-        tt[i] = t;
-      }
-      // the tables' last readers (XL_NTAB - 1 - i calls back): one wait for the latest of them covers the earlier ones that
-      // were recorded on the same stream (every wait is a queue packet of its own, ~4 us in front of the chain launch)
-      {
-        uint64_t need = 0;  // the latest call that read one of these tables
-        for (int i = 0; i < (int)cc.n; ++i) need = std::max(need, b->tab_call[tt[i]]);
-        if (need != 0) {
-          if (b->done_call >= need) {
-            XL_TRY(hipStreamWaitEvent(ns, b->ev_done[b->done_tab], 0));
-          } else if (!tab_from_s) {  // (tab_from_s: the side stream was just ordered behind everything on `s`)
-            XL_TRY(hipEventRecord(b->dep_ev, s));  // all earlier calls' launches precede this point of `s`
-            XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
-          }
-        }
-      }
-      XL_TRY(xl_launch_nco_chain(b->d_nco, (uint32_t)b->nco.size(), b->d_phase[pcur], cc, xl_grid_next(pos),
-                                 b->d_chain_stats, ns, b->ev_chain[xl_nx(tab)]));
-      launched_n = (int)cc.n;
-      b->waited_valid = false;  // (ev_chain[xl_nx(tab)] now stands for this launch)
     }
-
-    // ---- the launches on the caller's stream: window images from [d_hist[hb] | blocks], phases from table[tab] ->
-    // d_out[p]; the first launch also rolls the raw history into d_hist[hn], and the launches tabulate table[tab ^ 1]
-    // for the next call
-    hipEvent_t f0 = nullptr, f1 = nullptr;
-    if (b->timing && (maxK > 0 || maxKw > 0) && b->ncalls % b->timing_every == 0) {
-      for (int i = 0; i < 2; ++i) {
-        hipEvent_t ev;
-        XL_TRY(xl_batch_timing_event(b, &ev));
-        b->ev.push_back(ev);
-      }
-      f0 = b->ev[b->ev.size() - 2];
-      f1 = b->ev[b->ev.size() - 1];
-    }
-    bool rolled = false;
-    bool done_attached = false;  // ev_done[tab] rides on the call's last launch
-    // does this call record ev_done[tab]?  Side-stream calls: only the ones that launch a chain (see tab_call); non-side calls
-    // after a side stream was used: always
-    const bool want_done = (side || b->last_nco != nullptr) && (!side || launched_n > 0);
-    bool record_attached = false;  // the caller's record_ev rides on the last launch instead (no ev_done wanted there)
-    Launch *const Ls = use_poly ? b->launches_rest : b->launches;
-    if (f0) XL_TRY(hipEventRecord(f0, s));
-    if (maxK > 0) {
-      for (int lq = 0; lq < XL_NLAUNCH; ++lq) {
-        Launch &L = Ls[lq];
-        if (L.groups.empty()) continue;
-        XlFirArgs a;
-        memset(&a, 0, sizeof(a));
-        a.in0 = b->d_hist[hb];
-        a.n0 = XL_HCAP;
-        a.in1 = d_blocks;
-        a.n1 = N;
-        a.fmt = b->fmt;
-        a.pos = pos;
-        a.groups = L.d_groups;
-        a.ngroups = (uint32_t)L.groups.size();
-        a.ota = L.ota;
-        const uint32_t Kl = (N + L.minD - 1) / L.minD;  // (an upper bound of the launch's largest output count)
-        a.xtiles = (std::min(Kl, maxK) + L.ota - 1) / L.ota;
-        // wave-priority segments pay when the launch is about one round of workgroups, and cost when new
-        // workgroups keep arriving (they would outrank nearly finished ones): enable up to two rounds
-        const size_t wgs = (size_t)a.ngroups * a.xtiles;
-        const size_t cap = 256 * std::max<size_t>(1, std::min<size_t>((160 * 1024) / std::max<size_t>(L.lds, 1), 7));
-        const bool flat = (b->exp_flags & 2u) || wgs > 2 * cap;
-        a.flags = (L.all_wide ? 1u : 0u) | (flat ? 2u : 0u) | 4u | ((b->nco_prio & 3u) << 4);
-        a.taps = use_poly ? b->d_taps_rest : b->d_taps;
-        a.phtab = b->d_phtab[tab];
-        a.out = b->d_out[p];
-        if (!rolled) {
-          a.hist_out = b->d_hist[hn];
-          a.hist_units = XL_HCAP * (b->bps / 2);
-          a.block_units = N * (b->bps / 2);
-          rolled = true;
-          if (fuse) {
-            a.nco_clients = b->d_nco;
-            a.nco_nclients = (uint32_t)b->nco.size();
-            const uint32_t slots = L.idle_waves * a.xtiles;
-            const uint32_t want = (a.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
-            if (b->riders && slots > 0 && (uint64_t)slots * 64u >= a.nco_nclients &&
-                xl_riders_window(wgs, L.nw, L.groups[0].Tpad, L.ct, maxK, L.lds, b->riders_min_wgs)) {
-              a.nco_slots = std::min(slots, want);
-              a.nco_lanes = (a.nco_nclients + a.nco_slots - 1) / a.nco_slots;
-            } else {
-              a.nco_wpw = std::max<uint32_t>(1, std::min<uint32_t>(b->nco_wpw, (uint32_t)L.nw));
-              a.nco_blocks = (a.nco_nclients + XL_NCO_LANES * a.nco_wpw - 1) / (XL_NCO_LANES * a.nco_wpw);
-            }
-            a.nco_state_in = b->d_phase[pcur];
-            a.nco_state_out = b->d_phase[xl_nx(pcur)];
-            a.nco_tab = b->d_phtab[xl_nx(tab)];
-            nco_fused = true;
-          }
-        }
-#ifdef XL_TUNING
-        size_t trace_n = 0;
-        if (b->exp_trace) {
-          trace_n = ((size_t)a.nco_blocks + (size_t)8 * ((a.ngroups * a.xtiles + 7) / 8)) * XL_NW_MAX * 6;
-          if (trace_n > b->trace_cap) {
-            if (b->d_trace) (void)hipFree(b->d_trace);
-            b->d_trace = nullptr;
-            XL_TRY(hipMalloc((void **)&b->d_trace, trace_n * sizeof(unsigned long long)));
-            b->trace_cap = trace_n;
-          }
-          XL_TRY(hipMemsetAsync(b->d_trace, 0, trace_n * sizeof(unsigned long long), s));
-          a.trace = b->d_trace;
-        }
-#endif
-        if (chain_wait) {
-          XL_TRY(hipStreamWaitEvent(s, b->ev_chain[chain_ev], 0));
-          chain_wait = false;
-          b->waited_valid = true, b->waited_ev = chain_ev, b->waited_stream = s;
-        }
-        XL_TRY(xl_launch_fir(L.ct, mode, L.nw, a, L.lds, s));
-#ifdef XL_TUNING
-        if (b->exp_trace) XL_TRY(xl_dump_trace(b->exp_trace, b->d_trace, trace_n, s));
-#endif
-      }
-      if (use_poly) {
-        for (PolyClass &pc : b->poly) {
-          XlpArgs pa;
-          memset(&pa, 0, sizeof(pa));
-          if (!rolled) {  // the forward launch also rolls the raw history
-            pa.hist_out = b->d_hist[hn];
-            pa.hist_units = XL_HCAP * (b->bps / 2);
-            pa.block_units = N * (b->bps / 2);
-            pa.roll_blocks = 32;
-            rolled = true;
-          }
-          pa.in0 = b->d_hist[hb];
-          pa.n0 = XL_HCAP;
-          pa.in1 = d_blocks;
-          pa.n1 = N;
-          pa.fmt = (uint32_t)b->fmt;
-          pa.pos = pos;
-          // the class's shared grid in this call (xl_grid.h): one D-step ahead of the reference client's output 0
-          const XlDyn dref = xl_grid_dyn(pc.D, pc.T, pc.rem_ref0, pc.hv0, pos);
-          pa.j0_ref = dref.j0;
-          pa.base = dref.base - pc.D;
-          pa.Kq = xl_merge_points(pc.D, pos);
-          pa.zero_below = dref.zero_below;  // (0 for mature members: nothing below their join points is weighted)
-          pa.D = pc.D;
-          pa.Dpad = pc.Dpad;
-          pa.T = pc.T;
-          pa.A = pc.A;
-          pa.V = pc.V;
-          pa.M = pc.M;
-          pa.nseg = (pa.Kq + pc.V - 1) / pc.V;
-          pa.nseg_cap = pc.nseg_cap;
-          if (pa.nseg > pa.nseg_cap) {
-            XL_LOG_ERR("internal: %u segments exceed the plan's capacity %u", pa.nseg, pa.nseg_cap);
-            goto fail;
-          }
-          pa.ncg = pc.ncg;
-          pa.exp = b->poly_exp;
-          pa.inv_reg = b->inv_reg;
-          pa.mix_kind = pc.mix_kind;
-          pa.nkb = pc.nkb;
-          pa.mix_pp = b->mix_pp;
-          pa.Rh = pc.d_Rh;
-          pa.cscale = pc.d_cscale;
-          pa.segmax = pc.d_segmax;
-          pa.seg_par = pc.seg_par;
-          pa.seg_cap = pc.seg_cap;
-          pc.seg_par ^= 1u;  // (a failed call leaves stale maxima behind at worst: a smaller scale than necessary, never a wrong one)
-          pa.W = b->d_W;
-          pa.X = pc.d_X;
-          pa.ximg = pc.ximg ? 1u : 0u;
-          pa.Y = pc.d_Y;
-          pa.cols = pc.d_cols;
-          pa.phtab = b->d_phtab[tab];
-          pa.out = b->d_out[p];
-          // the NEXT call's phase recurrence rides in these launches (a direct launch above carries all of it if there is
-          // one): TWO slices, forward | inverse -- never the mix launch: no launch that issues matrix instructions hosts the role
-          // 
-          const bool carry = fuse && !nco_fused;
-          const uint32_t sl1 = std::min(b->poly_slice_fi, 60000u);
-          if (carry) {
-            pa.nco_clients = b->d_nco;
-            pa.nco_nclients = (uint32_t)b->nco.size();
-            pa.nco_blocks = (pa.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
-            pa.nco_tab = b->d_phtab[xl_nx(tab)];
-            pa.nco_prio = b->nco_prio;
-            pa.nco_k0 = 0;
-            pa.nco_k1 = sl1;
-            pa.nco_state_src = b->d_phase[pcur];
-            pa.nco_state_dst = b->d_phase_run;
-          }
-          hipEvent_t pe[4] = {nullptr, nullptr, nullptr, nullptr};
-          if (b->timing == 2) {
-            for (int i = 0; i < 4; ++i) {
-              XL_TRY(xl_batch_timing_event(b, &pe[i]));
-              b->ev_poly.push_back(pe[i]);
-            }
-            XL_TRY(hipEventRecord(pe[0], s));
-          }
-          // the call's last launch carries the "table has been read" event the side stream waits for
-          const bool last_launch = side && rolled && &pc == &b->poly.back() && maxKw == 0;  // (a wide launch follows: it reads the table too)
-#ifdef XL_TUNING
-          const bool trace_fwd = b->poly_trace && xl_exp_getenv("XL_EXP_POLY_TRACE_FWD");  // (the forward launch instead)
-          if (trace_fwd) {
-            if (!b->d_ptrace) XL_TRY(hipMalloc((void **)&b->d_ptrace, 32768 * sizeof(unsigned long long)));
-            XL_TRY(hipMemsetAsync(b->d_ptrace, 0, 32768 * sizeof(unsigned long long), s));
-            pa.trace = b->d_ptrace;
-          }
-#endif
-          XL_TRY(xlp_launch_forward(pa, s));
-#ifdef XL_TUNING
-          if (trace_fwd) {
-            pa.trace = nullptr;
-            XL_TRY(xl_dump_trace(b->poly_trace, b->d_ptrace, 32768, s));
-          }
-#endif
-          if (pe[1]) XL_TRY(hipEventRecord(pe[1], s));
-          pa.roll_blocks = 0;
-          pa.nco_blocks = 0;  // (no role in the mix launch)
-#ifdef XL_TUNING
-          const bool trace_inv = b->poly_trace && !trace_fwd && xl_exp_getenv("XL_EXP_POLY_TRACE_INV");  // (the inverse launch instead)
-          if (b->poly_trace && !trace_inv && !trace_fwd) {  // timeline of the mix launch (work waves' span + each NCO wave)
-            if (!b->d_ptrace) XL_TRY(hipMalloc((void **)&b->d_ptrace, 32768 * sizeof(unsigned long long)));
-            XL_TRY(hipMemsetAsync(b->d_ptrace, 0, 32768 * sizeof(unsigned long long), s));
-            pa.trace = b->d_ptrace;
-          }
-#endif
-          XL_TRY(xlp_launch_mix(pa, s));
-          pa.nco_skip = 0;
-#ifdef XL_TUNING
-          if (b->poly_trace && !trace_inv && !trace_fwd) {
-            pa.trace = nullptr;
-            XL_TRY(xl_dump_trace(b->poly_trace, b->d_ptrace, 32768, s));
-          }
-#endif
-          if (pe[2]) XL_TRY(hipEventRecord(pe[2], s));
-          if (carry) {
-            pa.nco_tab = b->d_phtab[xl_nx(tab)];
-            pa.nco_blocks = (pa.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
-            pa.nco_k0 = sl1;
-            pa.nco_k1 = 65536;
-            pa.nco_state_src = b->d_phase_run;
-            if (b->inv_skip_at > 0) {
-              pa.nco_skip_at = b->inv_skip_at;
-              pa.nco_skip = pa.nco_blocks;
-            }
-            pa.nco_state_dst = b->d_phase[xl_nx(pcur)];
-            nco_fused = true;
-          }
-#ifdef XL_TUNING
-          if (trace_inv) {
-            if (!b->d_ptrace) XL_TRY(hipMalloc((void **)&b->d_ptrace, 32768 * sizeof(unsigned long long)));
-            XL_TRY(hipMemsetAsync(b->d_ptrace, 0, 32768 * sizeof(unsigned long long), s));
-            pa.trace = b->d_ptrace;
-          }
-#endif
-          if (chain_wait) {  // (the forward and mix launches do not read the table)
-            XL_TRY(hipStreamWaitEvent(s, b->ev_chain[chain_ev], 0));
-            chain_wait = false;
-            b->waited_valid = true, b->waited_ev = chain_ev, b->waited_stream = s;
-          }
-          {
-            const bool attach = last_launch
-#ifdef XL_TUNING
-                                && !trace_inv
-#endif
-                ;
-            XL_TRY(xlp_launch_inverse(pa, s, attach ? (want_done ? b->ev_done[tab] : record_ev) : nullptr));
-            pc.last_inv = (int)xlp_inverse_pick(pa.M, pa.inv_reg, pa.nseg * pa.ncg * 4u);
-            done_attached = attach && want_done;
-            record_attached = attach && !want_done && record_ev != nullptr;
-          }
-#ifdef XL_TUNING
-          if (trace_inv) {
-            pa.trace = nullptr;
-            XL_TRY(xl_dump_trace(b->poly_trace, b->d_ptrace, 32768, s));
-          }
-#endif
-          if (pe[3]) XL_TRY(hipEventRecord(pe[3], s));
-        }
-      }
-    }
-    if (maxKw > 0) {  // the wide clients, behind the launches above on the same stream
-      if (chain_wait) {
-        XL_TRY(hipStreamWaitEvent(s, b->ev_chain[chain_ev], 0));
-        chain_wait = false;
-        b->waited_valid = true, b->waited_ev = chain_ev, b->waited_stream = s;
-      }
-      XL_TRY(xl_batch_wide_launch(b, mode, d_blocks, N, hb, pos, maxKw, b->d_phtab[tab], b->d_out[p], s));
-    }
-    if (f1) XL_TRY(hipEventRecord(f1, s));
-    if (!rolled)  // no client produced output in this call (tiny block): roll the history on its own
-      XL_TRY(xl_launch_update_history(b->d_hist[hb], d_blocks, XL_HCAP, N, b->bps, b->d_hist[hn], s));
-    if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[hb], d_blocks, b->max_window, N, b->bps, b->d_whist[hn], s));
-    // table[tab] has been read by everything enqueued so far (only the side stream ever waits for this)
-    // -- and a LATER side-stream chain launch may find this slot in its ring even when this call ran no side stream
-    // (alternating modes, alternating caller streams, nco_calls_per_launch < 4): once a side stream has been used the
-    // event is recorded for every call.  Engines that never use the side stream never pay for it.
-    if (side || b->last_nco != nullptr) b->tab_call[tab] = b->ncalls + 1;
-    if (want_done) {
-      if (!done_attached) XL_TRY(hipEventRecord(b->ev_done[tab], s));
-      b->ev_done_valid[tab] = true;
-      b->ev_done_stream[tab] = s;
-      b->done_call = b->ncalls + 1;
-      b->done_tab = tab;
-    } else {
-      b->ev_done_valid[tab] = false;
-    }
-
-    if (record_ev && !record_attached) XL_TRY(hipEventRecord(record_ev, s));
-    // ---- everything is enqueued: commit the host-side state of the call
-    b->poisoned = false;
-    xl_clients_commit(b->clients, (uint32_t)S, G);
-    b->trel += N;
-    b->pcur = pcur;
-    b->tab = tab;
-    b->ocur = p;
-    b->hcur = hn;
-    b->ncalls++;
-    b->calls_since_plan++;
-    // ---- the NEXT call's phases, guessing it has the same shape, were tabulated inside the launches above;
-    // without them (tiny call, or the tuning switch) the next call tabulates for itself
-    if (launched_n > 0) {
-      b->spec_n = launched_n;
-      b->spec_on_side = true;
-      b->spec_ev = xl_nx(tab);
-    } else if (spec_left > 0) {
-      b->spec_n = spec_left;  // (same launch, same event)
-    } else if (nco_fused) {
-      b->spec_n = 1;
-      b->spec_on_side = false;
-    }
-    b->spec_S = (uint32_t)S;
-    b->spec_G = G;
-    b->spec_flags = pos_flags;
   }
+  XL_TRY(xl_launch_nco_chain(b->d_nco, (uint32_t)b->nco.size(), b->d_phase[c.pcur], cc, xl_grid_next(c.pos),
+                             b->d_chain_stats, ns, b->ev_chain[xl_nx(c.tab)]));
+  c.launched_n = (int)cc.n;
+  b->waited_valid = false;  // (ev_chain[xl_nx(tab)] now stands for this launch)
+  return 0;
+fail:
+  return 1;
+}
+
+// Stage 5: the launches on the caller's stream begin: window images from [d_hist[hb] | blocks], phases from table[tab] ->
+// d_out[p]; the first launch also rolls the raw history into d_hist[hn], and the launches tabulate table[tab ^ 1]
+// for the next call.  Here: the call's timing events, whether it records ev_done[tab], and the direct launches of its launch
+// set.  Only the first launch of a call rolls the history and may carry the NCO role.
+XL_STAGE int xl_call_direct(xlating_batch *b, XlCall &c) {
+  hipStream_t s = c.s;
+  Launch *const Ls = c.use_poly ? b->launches_rest : b->launches;
+  if (b->timing && (c.maxK > 0 || c.maxKw > 0) && b->ncalls % b->timing_every == 0) {
+    for (int i = 0; i < 2; ++i) {
+      hipEvent_t ev;
+      XL_TRY(xl_batch_timing_event(b, &ev));
+      b->ev.push_back(ev);
+    }
+    c.f0 = b->ev[b->ev.size() - 2], c.f1 = b->ev[b->ev.size() - 1];
+  }
+  c.want_done = (c.side || b->last_nco != nullptr) && (!c.side || c.launched_n > 0);
+  if (c.f0) XL_TRY(hipEventRecord(c.f0, s));
+  for (int lq = 0; lq < XL_NLAUNCH && c.maxK > 0; ++lq) {
+    Launch &L = Ls[lq];
+    if (L.groups.empty()) continue;
+    XlFirArgs a;
+    xl_call_fir_args(b, c, L, a);
+    // wave-priority segments pay when the launch is about one round of workgroups, and cost when new
+    // workgroups keep arriving (they would outrank nearly finished ones): enable up to two rounds
+    const size_t wgs = (size_t)a.ngroups * a.xtiles;
+    const size_t cap = 256 * std::max<size_t>(1, std::min<size_t>((160 * 1024) / std::max<size_t>(L.lds, 1), 7));
+    const bool flat = (b->exp_flags & 2u) || wgs > 2 * cap;
+    a.flags = (L.all_wide ? 1u : 0u) | (flat ? 2u : 0u) | 4u | ((b->nco_prio & 3u) << 4);
+    a.taps = c.use_poly ? b->d_taps_rest : b->d_taps;
+    a.phtab = b->d_phtab[c.tab];
+    if (!c.rolled) {
+      xl_call_roll_args(b, c, a);
+      if (c.fuse) {
+        a.nco_clients = b->d_nco;
+        a.nco_nclients = (uint32_t)b->nco.size();
+        const uint32_t slots = L.idle_waves * a.xtiles;
+        const uint32_t want = (a.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
+        if (b->riders && slots > 0 && (uint64_t)slots * 64u >= a.nco_nclients &&
+            xl_riders_window(wgs, L.nw, L.groups[0].Tpad, L.ct, c.maxK, L.lds, b->riders_min_wgs)) {
+          a.nco_slots = std::min(slots, want);
+          a.nco_lanes = (a.nco_nclients + a.nco_slots - 1) / a.nco_slots;
+        } else {
+          a.nco_wpw = std::max<uint32_t>(1, std::min<uint32_t>(b->nco_wpw, (uint32_t)L.nw));
+          a.nco_blocks = (a.nco_nclients + XL_NCO_LANES * a.nco_wpw - 1) / (XL_NCO_LANES * a.nco_wpw);
+        }
+        a.nco_state_in = b->d_phase[c.pcur], a.nco_state_out = b->d_phase[xl_nx(c.pcur)];
+        a.nco_tab = b->d_phtab[xl_nx(c.tab)];
+        c.nco_fused = true;
+      }
+    }
+#ifdef XL_TUNING
+    size_t trace_n = 0;
+    if (b->exp_trace) {
+      trace_n = ((size_t)a.nco_blocks + (size_t)8 * ((a.ngroups * a.xtiles + 7) / 8)) * XL_NW_MAX * 6;
+      if (trace_n > b->trace_cap) {
+        if (b->d_trace) (void)hipFree(b->d_trace);
+        b->d_trace = nullptr;
+        XL_TRY(hipMalloc((void **)&b->d_trace, trace_n * sizeof(unsigned long long)));
+        b->trace_cap = trace_n;
+      }
+      XL_TRY(hipMemsetAsync(b->d_trace, 0, trace_n * sizeof(unsigned long long), s));
+      a.trace = b->d_trace;
+    }
+#endif
+    XL_TRY(xl_call_chain_wait(b, c));
+    XL_TRY(xl_launch_fir(L.ct, c.mode, L.nw, a, L.lds, s));
+#ifdef XL_TUNING
+    if (b->exp_trace) XL_TRY(xl_dump_trace(b->exp_trace, b->d_trace, trace_n, s));
+#endif
+  }
+  return 0;
+fail:
+  return 1;
+}
+
+// Stage 6: one polyphase class: forward, mix and inverse launch, with the two slices of the NCO role.  `last`: the call's
+// last class.
+XL_STAGE int xl_call_poly_class(xlating_batch *b, XlCall &c, PolyClass &pc, bool last) {
+  hipStream_t s = c.s;
+  XlpArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  if (!c.rolled) {  // the forward launch also rolls the raw history
+    xl_call_roll_args(b, c, pa);
+    pa.roll_blocks = 32;
+  }
+  pa.in0 = b->d_hist[c.hb], pa.n0 = XL_HCAP, pa.in1 = c.d_blocks, pa.n1 = c.N;
+  pa.fmt = (uint32_t)b->fmt, pa.pos = c.pos;
+  // the class's shared grid in this call (xl_grid.h): one D-step ahead of the reference client's output 0
+  const XlDyn dref = xl_grid_dyn(pc.D, pc.T, pc.rem_ref0, pc.hv0, c.pos);
+  pa.j0_ref = dref.j0;
+  pa.base = dref.base - pc.D;
+  pa.Kq = xl_merge_points(pc.D, c.pos);
+  pa.zero_below = dref.zero_below;  // (0 for mature members: nothing below their join points is weighted)
+  pa.D = pc.D, pa.Dpad = pc.Dpad, pa.T = pc.T, pa.A = pc.A, pa.V = pc.V, pa.M = pc.M;
+  pa.nseg = (pa.Kq + pc.V - 1) / pc.V;
+  pa.nseg_cap = pc.nseg_cap;
+  if (pa.nseg > pa.nseg_cap) {
+    XL_LOG_ERR("internal: %u segments exceed the plan's capacity %u", pa.nseg, pa.nseg_cap);
+    return 1;  // (the engine is poisoned: -EIO)
+  }
+  pa.ncg = pc.ncg, pa.mix_kind = pc.mix_kind, pa.nkb = pc.nkb;
+  pa.exp = b->poly_exp, pa.inv_reg = b->inv_reg, pa.mix_pp = b->mix_pp;
+  pa.Rh = pc.d_Rh, pa.cscale = pc.d_cscale;
+  pa.segmax = pc.d_segmax, pa.seg_par = pc.seg_par, pa.seg_cap = pc.seg_cap;
+  pc.seg_par ^= 1u;  // (a failed call leaves stale maxima behind at worst: a smaller scale than necessary, never a wrong one)
+  pa.W = b->d_W, pa.X = pc.d_X, pa.ximg = pc.ximg ? 1u : 0u, pa.Y = pc.d_Y, pa.cols = pc.d_cols;
+  pa.phtab = b->d_phtab[c.tab], pa.out = b->d_out[c.p];
+  // the NEXT call's phase recurrence rides in these launches (a direct launch above carries all of it if there is
+  // one): TWO slices, forward | inverse -- never the mix launch: no launch that issues matrix instructions hosts the role
+  // 
+  const bool carry = c.fuse && !c.nco_fused;
+  const uint32_t sl1 = std::min(b->poly_slice_fi, 60000u);
+  if (carry) {
+    pa.nco_clients = b->d_nco, pa.nco_nclients = (uint32_t)b->nco.size();
+    pa.nco_blocks = (pa.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
+    pa.nco_tab = b->d_phtab[xl_nx(c.tab)], pa.nco_prio = b->nco_prio;
+    pa.nco_k0 = 0, pa.nco_k1 = sl1;
+    pa.nco_state_src = b->d_phase[c.pcur], pa.nco_state_dst = b->d_phase_run;
+  }
+  // the call's last launch carries the "table has been read" event the side stream waits for
+  const bool last_launch = c.side && c.rolled && last && c.maxKw == 0;  // (a wide launch follows: it reads the table too)
+  // XL_EXP_POLY_TRACE: timeline of the mix launch (2: work waves' span + each NCO wave), of the forward launch instead (1:
+  // XL_EXP_POLY_TRACE_FWD) or of the inverse launch instead (3: XL_EXP_POLY_TRACE_INV)
+#ifdef XL_TUNING
+  const int traced = !b->poly_trace ? 0 : (xl_exp_getenv("XL_EXP_POLY_TRACE_FWD") ? 1 : (xl_exp_getenv("XL_EXP_POLY_TRACE_INV") ? 3 : 2));
+#else
+  const int traced = 0;
+#endif
+  hipEvent_t pe[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (b->timing == 2) {
+    for (int i = 0; i < 4; ++i) {
+      XL_TRY(xl_batch_timing_event(b, &pe[i]));
+      b->ev_poly.push_back(pe[i]);
+    }
+    XL_TRY(hipEventRecord(pe[0], s));
+  }
+  if (traced == 1) XL_TRY(xl_ptrace(b, pa, s, true));
+  XL_TRY(xlp_launch_forward(pa, s));
+  if (traced == 1) XL_TRY(xl_ptrace(b, pa, s, false));
+  if (pe[1]) XL_TRY(hipEventRecord(pe[1], s));
+  pa.roll_blocks = 0;
+  pa.nco_blocks = 0;  // (no role in the mix launch)
+  if (traced == 2) XL_TRY(xl_ptrace(b, pa, s, true));
+  XL_TRY(xlp_launch_mix(pa, s));
+  pa.nco_skip = 0;
+  if (traced == 2) XL_TRY(xl_ptrace(b, pa, s, false));
+  if (pe[2]) XL_TRY(hipEventRecord(pe[2], s));
+  if (carry) {
+    pa.nco_tab = b->d_phtab[xl_nx(c.tab)];
+    pa.nco_blocks = (pa.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
+    pa.nco_k0 = sl1, pa.nco_k1 = 65536;
+    pa.nco_state_src = b->d_phase_run, pa.nco_state_dst = b->d_phase[xl_nx(c.pcur)];
+    if (b->inv_skip_at > 0) pa.nco_skip_at = b->inv_skip_at, pa.nco_skip = pa.nco_blocks;
+    c.nco_fused = true;
+  }
+  if (traced == 3) XL_TRY(xl_ptrace(b, pa, s, true));
+  XL_TRY(xl_call_chain_wait(b, c));  // (the forward and mix launches do not read the table)
+  {
+    const bool attach = last_launch && traced != 3;  // (a traced inverse launch carries no event)
+    XL_TRY(xlp_launch_inverse(pa, s, attach ? (c.want_done ? b->ev_done[c.tab] : c.record_ev) : nullptr));
+    pc.last_inv = (int)xlp_inverse_pick(pa.M, pa.inv_reg, pa.nseg * pa.ncg * 4u);
+    c.done_attached = attach && c.want_done;
+    c.record_attached = attach && !c.want_done && c.record_ev != nullptr;
+  }
+  if (traced == 3) XL_TRY(xl_ptrace(b, pa, s, false));
+  if (pe[3]) XL_TRY(hipEventRecord(pe[3], s));
+  return 0;
+fail:
+  return 1;
+}
+
+// Stage 7: the wide clients, behind the launches above on the same stream, and the history rolls that no launch carried.
+XL_STAGE int xl_call_wide_and_rolls(xlating_batch *b, XlCall &c) {
+  hipStream_t s = c.s;
+  if (c.maxKw > 0) {
+    XL_TRY(xl_call_chain_wait(b, c));
+    XL_TRY(xl_batch_wide_launch(b, c, b->d_phtab[c.tab]));
+  }
+  if (c.f1) XL_TRY(hipEventRecord(c.f1, s));
+  if (!c.rolled)  // no client produced output in this call (tiny block): roll the history on its own
+    XL_TRY(xl_launch_update_history(b->d_hist[c.hb], c.d_blocks, XL_HCAP, c.N, b->bps, b->d_hist[c.hn], s));
+  if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[c.hb], c.d_blocks, b->max_window, c.N, b->bps, b->d_whist[c.hn], s));
+  return 0;
+fail:
+  return 1;
+}
+
+// Stage 8: the "table has been read" event, the caller's event, the host commit and the look-ahead handed to the next call.
+XL_STAGE int xl_call_finish(xlating_batch *b, XlCall &c) {
+  hipStream_t s = c.s;
+  const int tab = c.tab;
+  // table[tab] has been read by everything enqueued so far (only the side stream ever waits for this)
+  // -- and a LATER side-stream chain launch may find this slot in its ring even when this call ran no side stream
+  // (alternating modes, alternating caller streams, nco_calls_per_launch < 4): once a side stream has been used the
+  // event is recorded for every call.  Engines that never use the side stream never pay for it.
+  if (c.side || b->last_nco != nullptr) b->tab_call[tab] = b->ncalls + 1;
+  if (c.want_done) {
+    if (!c.done_attached) XL_TRY(hipEventRecord(b->ev_done[tab], s));
+    b->ev_done_valid[tab] = true;
+    b->done_call = b->ncalls + 1, b->done_tab = tab;
+  } else {
+    b->ev_done_valid[tab] = false;
+  }
+  if (c.record_ev && !c.record_attached) XL_TRY(hipEventRecord(c.record_ev, s));
+  xl_call_commit(b, c);
+  b->pcur = c.pcur, b->tab = tab;
+  // ---- the NEXT call's phases, guessing it has the same shape, were tabulated inside the launches above;
+  // without them (tiny call, or the tuning switch) the next call tabulates for itself
+  if (c.launched_n > 0) {
+    b->spec_n = c.launched_n;
+    b->spec_on_side = true;
+    b->spec_ev = xl_nx(tab);
+  } else if (c.spec_left > 0) {
+    b->spec_n = c.spec_left;  // (same launch, same event)
+  } else if (c.nco_fused) {
+    b->spec_n = 1;
+    b->spec_on_side = false;
+  }
+  b->spec_S = (uint32_t)c.S, b->spec_G = c.G, b->spec_flags = c.pos.pad;
+  return 0;
+fail:
+  return 1;
+}
+
+// One call: G blocks of S samples each, contiguous at d_blocks.  s_in: the caller's stream, or XL_STREAM_ENGINE_P = the
+// engine's own compute stream (the CU-masked one for calls whose NCO chain runs on the side stream).  wait_ev / record_ev:
+// optional events of the caller, waited for before / recorded after the call's work on that stream.
+static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len, unsigned G, int mode, hipStream_t s_in,
+                        hipEvent_t wait_ev = nullptr, hipEvent_t record_ev = nullptr) {
+  XlCall c;
+  memset(&c, 0, sizeof(c));
+  c.d_blocks = d_blocks, c.S = input_len / 2, c.G = G, c.mode = mode;
+  c.s = s_in, c.wait_ev = wait_ev, c.record_ev = record_ev;
+  if (xl_call_begin(b, c)) goto fail;
+  if (c.ended) return c.ret;
+  if (c.mode == XL_MODE_Q15) {
+    if (xl_call_q15(b, c)) goto fail;
+    return 0;
+  }
+  b->last_q15 = false;
+  if (xl_call_table(b, c)) goto fail;
+  if (c.side && c.spec_left == 0 && xl_call_chain(b, c)) goto fail;
+  if (xl_call_direct(b, c)) goto fail;
+  if (c.maxK > 0 && c.use_poly)
+    for (PolyClass &pc : b->poly)
+      if (xl_call_poly_class(b, c, pc, &pc == &b->poly.back())) goto fail;
+  if (xl_call_wide_and_rolls(b, c)) goto fail;
+  if (xl_call_finish(b, c)) goto fail;
   return 0;
 fail:
   return b->poisoned ? -EIO : xl_errno_of_last_hip_error();

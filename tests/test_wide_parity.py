@@ -128,7 +128,7 @@ def test_batch_wide_every_format_and_mode(fmt):
 @pytest.mark.parametrize("fmt", ["cu8", "cs8", "cs16", "cf32"])
 def test_batch_wide_x86_modes_drift_and_renormalising_call(fmt, flavour):
     """XL_MODE_OPTIMIZED_X86 / _X86_FMA with wide clients: the wide launch's phases (xl_wide.hip xl_wide_phase) must follow the flags that
-    xl_batch.cpp xl_batch_run carries in pos.pad (XL_POS_NORENORM / XL_POS_FMA_STEP).  53 blocks in calls of 8 and 1, the phase never
+    xl_batch.cpp xl_call_begin puts into pos.pad (XL_POS_NORENORM / XL_POS_FMA_STEP).  53 blocks in calls of 8 and 1, the phase never
     renormalised, against Oracle(renorm=False, fma_step=...); a renormalising native call in between (bit-exact); phases bit for bit."""
     n = 65536
     fma = flavour.endswith("fma")
@@ -164,7 +164,7 @@ def _geometry(shape):
 @pytest.mark.parametrize("variant", ["native", "optimized"])
 @pytest.mark.parametrize("shape", ["20m_max_window", "10m_default_ring"])
 def test_batch_wide_ragged_device_blocks_late_fetch(shape, variant):
-    """xl_batch.cpp look-ahead in xl_batch_run (the next call's phase table tabulated for the previous call's length), xl_grid.h
+    """xl_batch.cpp look-ahead in xl_call_table (the next call's phase table tabulated for the previous call's length), xl_grid.h
     xl_grid_dyn_cap and xl_wide.hip xl_wide_load4 on single blocks of ragged lengths -- full, 100002, below D, below T, 8 bytes -- fed
     as device buffers on the caller's (torch) stream, fetched only now and then; a wide client joins mid-stream."""
     import torch
@@ -337,7 +337,7 @@ def test_admission_edge_tap_multiples_4_and_12(T):
 
 
 def test_grouped_call_shorter_than_wide_decimation_is_refused():
-    """xl_batch.cpp xl_batch_run: a call of G >= 2 blocks needs blocks of at least the largest decimation (plan_maxD, the wide clients'
+    """xl_batch.cpp xl_call_begin: a call of G >= 2 blocks needs blocks of at least the largest decimation (plan_maxD, the wide clients'
     included; xl_grid.h xl_bnd_next needs S >= D) -- G = 4 blocks of 1500 samples next to a D = 2000 wide client return -EINVAL, also
     right after a client joined (the plan is rebuilt inside the refused call), and leave every stream intact: the next calls match the
     oracle, a single block of 1500 samples is accepted, phases bit for bit at the end."""
