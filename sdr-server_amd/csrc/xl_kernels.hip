@@ -154,6 +154,24 @@ XL_DEV uint32_t xl_chain_event(uint32_t ev) {
   XLC_MUL "v_and_b32 %[off], 0x7fff, %[off]\n\t" XLC_ADD                                  \
   XLC_STEP2("v_add_u32 %[addr], %[off], %[base]", "s_cmp_lg_u32 %[todo], 0")              \
   XLC_STEPS10 "s_cbranch_scc1 1b\n\t"
+// A run of 8 entries from a ring slot that is a multiple of 8 (xl_chain_plan8), as the body of a counted loop inside the same asm
+// block: the slots at immediates off [addr] as in the 32-entry block (the run never runs over the ring's end), and ONE count post,
+// address update and exit test per 8 entries, in the shadows of the eighth entry's first steps; [todo8] counts the runs still wanted
+// (>= 1 on entry).  One taken branch per 8 entries instead of one per entry.
+#define XLC_B8_LOOP                                                                        \
+  "2:\n\t" XLC_E7("0", "512", "1024", "1536", "2048", "2560", "3072")                    \
+  XLC_MUL "ds_write_b64 %[addr], %[p] offset:3584\n\t" XLC_ADD                           \
+  XLC_STEP2("v_add_u32 %[cnt], 8, %[cnt]", "s_sub_u32 %[todo8], %[todo8], 1")            \
+  XLC_MUL "ds_write_b32 %[paddr], %[cnt]\n\t" XLC_ADD                                    \
+  XLC_MUL "v_add_u32 %[off], 0x1000, %[off]\n\t" XLC_ADD                                 \
+  XLC_MUL "v_and_b32 %[off], 0x7fff, %[off]\n\t" XLC_ADD                                 \
+  XLC_STEP2("v_add_u32 %[addr], %[off], %[base]", "s_cmp_lg_u32 %[todo8], 0")            \
+  XLC_STEPS10 "s_cbranch_scc1 2b\n\t"
+// Either loop as a part of a head or tail block, skipped when its count is zero.  Test and branch in front are 4 bytes each, and one
+// 4-byte s_nop behind pairs with the loop's own closing branch: a part is a multiple of 8 bytes, whatever follows it stays on an
+// 8-byte boundary.
+#define XLC_ANY_PART "s_cmp_eq_u32 %[todo], 0\n\ts_cbranch_scc1 3f\n\t" XLC_ANY_LOOP "3:\n\ts_nop 0\n\t"
+#define XLC_B8_PART "s_cmp_eq_u32 %[todo8], 0\n\ts_cbranch_scc1 4f\n\t" XLC_B8_LOOP "4:\n\ts_nop 0\n\t"
 // [todo] plain steps and nothing else (the entry that holds a block end: the steps before and after the renormalisation)
 #define XLC_STEP_LOOP "1:\n\t" XLC_STEP2("s_sub_u32 %[todo], %[todo], 1", "s_cmp_lg_u32 %[todo], 0") "s_cbranch_scc1 1b\n\t"
 // A whole entry without bookkeeping, the ring slot at an immediate offset: 16 steps (the entry's phase goes into the ring in
@@ -259,30 +277,33 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
                                                     // step of an -mfma reference build takes the per-step path throughout)
         const unsigned long long r0 = stats ? clock64() : 0ull;
         if ((e << XL_PH_SHIFT) < K) {  // (a lane whose call has ended sits the region out; the others' mask is constant in it)
-          // head of single entries up to the next 32-entry boundary of the ring, 32-entry blocks, tail of single entries
-          // (xl_chain_plan.h): three asm blocks per region at the most, nothing climbs and nothing is chosen in between
-          const XlChainPlan pl = xl_chain_plan(e, e_stop, XLC_RING, 32u);
+          // head (single entries up to the next multiple of 8 ring slots, 8-entry runs up to the next 32-entry boundary), 32-entry
+          // blocks, tail (8-entry runs, single entries) (xl_chain_plan8, xl_chain_plan.h): three asm blocks per region at the most,
+          // nothing climbs and nothing is chosen in between
+          const XlChainPlan8 pl = xl_chain_plan8(e, e_stop, XLC_RING, 32u, 8u);
           uint32_t ee = e;
           v2f t1, t2;
-          // a run of N any-slot entries from ee on (N < 32 and the ring holds 64: one drain check covers the run, the loop needs no poll)
-#define XLC_ANY_RUN(N)                                                                                                       \
-  if ((N) != 0u) {                                                                                                           \
-    uint32_t todo = (N);                                                                                                     \
-    if (ee + todo > lim) {                                                                                                   \
+          // N1 any-slot entries and N8 aligned 8-entry runs from ee on, in the order PARTS names (fewer than 32 entries, and the ring
+          // holds 64: one drain check covers them, the loops need no poll)
+#define XLC_COVER_RUN(N1, N8, PARTS)                                                                                         \
+  if ((N1) + (N8) != 0u) {                                                                                                   \
+    uint32_t todo = (N1), todo8 = (N8);                                                                                      \
+    const uint32_t total = todo + 8u * todo8;                                                                                \
+    if (ee + total > lim) {                                                                                                  \
       const unsigned long long d0 = stats ? clock64() : 0ull;                                                                \
-      lim = xl_chain_wait_drained(ee + todo, a_n0, a_n1, a_n2);                                                              \
+      lim = xl_chain_wait_drained(ee + total, a_n0, a_n1, a_n2);                                                             \
       if (stats) t_drain += clock64() - d0, ++n_drain;                                                                       \
     }                                                                                                                        \
     uint32_t off = ((ee & (XLC_RING - 1u)) << 9) + lane * (uint32_t)sizeof(v2f); /* ring offset of entry ee, this lane */    \
     uint32_t addr = a_ring0 + off, cnt = ee;                                                                                 \
-    ee += todo;                                                                                                              \
-    asm volatile(XLC_ALIGN XLC_ANY_LOOP                                                                                      \
+    ee += total;                                                                                                             \
+    asm volatile(XLC_ALIGN PARTS                                                                                             \
                  : [p] "+v"(p), [off] "+v"(off), [addr] "+v"(addr), [cnt] "+v"(cnt), [t1] "=&v"(t1), [t2] "=&v"(t2),         \
-                   [todo] "+s"(todo)                                                                                         \
+                   [todo] "+s"(todo), [todo8] "+s"(todo8)                                                                    \
                  : [inc] "v"(inc), [base] "v"(a_ring0), [paddr] "v"(a_prod)                                                  \
                  : "memory", "scc");                                                                                         \
   }
-          XLC_ANY_RUN(pl.head);
+          XLC_COVER_RUN(pl.head1, pl.head8, XLC_ANY_PART XLC_B8_PART);
           // 32-entry blocks back to back inside one asm block while the drainers keep up (a block that starts at a multiple
           // of 32 ends where the next one may start); the drainers' counters are read during each block and weighed at its end
           for (uint32_t want = pl.blocks; want != 0u;) {
@@ -309,8 +330,8 @@ __global__ __launch_bounds__(256) void xl_nco_chain_kernel(const XlNcoClient *__
             ee += ran;
             want = left;
           }
-          XLC_ANY_RUN(pl.tail);
-#undef XLC_ANY_RUN
+          XLC_COVER_RUN(pl.tail1, pl.tail8, XLC_B8_PART XLC_ANY_PART);
+#undef XLC_COVER_RUN
         }
         if (e_stop > e) e = e_stop;
         if (stats) t_region += clock64() - r0, ++n_event;

@@ -354,13 +354,24 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   const v2f *__restrict__ ph = reinterpret_cast<const v2f *>(a.phtab);
   v2f *__restrict__ out = reinterpret_cast<v2f *>(a.out);
   const uint32_t colbase = cg * XLP_COLS + sub * CW + WPC * w;
-  uint32_t off[4], ksh[4], kc[4];
+  // Per column, what the lane's four stores need: the output index of its first point (qo = l) and the window of points
+  // that are the column's outputs in this segment.  Point qo = l + L r is output qs - ksh, qs = s V + qo, when the column
+  // is live, qo < V, qs >= ksh and qs - ksh < kc: one interval lo <= qo < hi, tested as (l - lo) + L r < hi - lo in
+  // unsigned arithmetic (a point below lo wraps far above any span; an empty interval has span 0).
+  // idx = out_off + s V + l + 1 - ksh counts from out[-1] (ksh <= 1), so that it never wraps below zero.
+  const uint32_t sV = s * a.V;
+  uint32_t idx[4], rel[4], span[4];
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
     const XlpCol c = a.cols[colbase + 4u * h + n];
-    off[n] = c.out_off;
-    ksh[n] = xl_merge_shift(a.j0_ref, c.delta, a.D);
-    kc[n] = xl_merge_outputs(a.j0_ref, c.delta, a.D, a.pos);
+    const uint32_t ksh = xl_merge_shift(a.j0_ref, c.delta, a.D);
+    const uint32_t end = ksh + xl_merge_outputs(a.j0_ref, c.delta, a.D, a.pos);  // shared points below this one are the column's
+    const uint32_t lo = ksh > sV ? ksh - sV : 0u;
+    const uint32_t left = end > sV ? end - sV : 0u;
+    const uint32_t hi = c.out_off == 0xFFFFFFFFu ? 0u : (left < a.V ? left : a.V);
+    idx[n] = c.out_off + sV + l + 1u - ksh;
+    rel[n] = l - lo;
+    span[n] = hi > lo ? hi - lo : 0u;
   }
   const uint32_t en = j / GQ, gq = j % GQ;  // expansion duty: column en of the wave, shared points s V + gq*XL_PH_STRIDE ..
   const XlpCol ce = a.cols[colbase + en];
@@ -389,15 +400,24 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   }
   __builtin_amdgcn_wave_barrier();
   const unsigned long long t_xf = a.trace ? wall_clock64() : 0ull;
+  // Epilogue without branches: the sixteen phases are read back to back, every value is scaled and rotated whether it is an
+  // output or not (finite or not, a value outside the window is never stored), and a column's four stores go at 0, L, 2 L,
+  // 3 L elements from one pointer under the window test alone.
+  v2f phs[4][4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) phs[n][r] = rows[n][P::pos(l + L * r, rs[n])];
 #pragma unroll
   for (int n = 0; n < 4; ++n) {
+    asm volatile("" : "+v"(idx[n]));  // (the 64-bit pointer is formed here, not carried through the transforms)
+    v2f *__restrict__ const po = out - 1 + idx[n];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const uint32_t qo = l + L * r, qs = s * a.V + qo;  // shared point of this value
-      if (off[n] != 0xFFFFFFFFu && qo < a.V && qs >= ksh[n] && qs - ksh[n] < kc[n]) {
-        const v2f y = u[n][r] * (1.0f / (float)M);  // exact scaling by 2^-8 / 2^-7
-        out[off[n] + (qs - ksh[n])] = xl_rotate<1>(y, rows[n][P::pos(qo, rs[n])]);
-      }
+      const v2f y = u[n][r] * (1.0f / (float)M);  // exact scaling by 2^-8 / 2^-7 / 2^-6
+      v2f z = xl_rotate<1>(y, phs[n][r]);
+      asm volatile("" : "+v"(z));  // (computed here, for every lane: not sunk behind the test)
+      if (rel[n] + L * r < span[n]) po[L * r] = z;
     }
   }
   if (a.trace && threadIdx.x == 0 && bid < 6000u) {  // tuning: start, tile loaded, transforms done, end
