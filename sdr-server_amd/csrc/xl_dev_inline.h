@@ -5,6 +5,7 @@
 #ifndef XL_DEV_INLINE_H_
 #define XL_DEV_INLINE_H_
 #include "xl_device.h"
+#include "xl_q15_narrow.h"  // xl_sat16, xl_q15_narrow_sum
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -55,8 +56,6 @@ XL_DEV v2f xl_sample_q15(const void *__restrict__ p, int fmt, uint32_t i) {
   }
   return r;
 }
-
-XL_DEV int32_t xl_sat16(int32_t v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }  // xlating.c:85-90
 
 // ------------------------------------------------------------------------------------------- complex arithmetic
 // One complex accumulator per (output, client).

@@ -1052,9 +1052,9 @@ __global__ __launch_bounds__(64 * XL_NW_MAX) void xl_fir_q15_batch_kernel(const 
   for (int c = 0; c < CT; ++c) {
     if ((uint32_t)c >= ncl) continue;
     const uint32_t off = t[2 + c], qi = t[2 + 3 * XL_CT_MAX + c];
-    // >> 15 of the int64 sums (arithmetic shift = floor), saturated (xlating.c:118-119)
-    const int32_t ar = xl_sat16((int32_t)__builtin_floor(accr[c] * (1.0 / 32768.0)));
-    const int32_t ai = xl_sat16((int32_t)__builtin_floor(acci[c] * (1.0 / 32768.0)));
+    // >> 15 of the int64 sums, cut to 32 bits, saturated (xlating.c:118-119; xl_q15_narrow.h)
+    const int32_t ar = xl_q15_narrow_sum(accr[c]);
+    const int32_t ai = xl_q15_narrow_sum(acci[c]);
     // this output's phase: the tabulated one below it, stepped m % XL_PH_STRIDE times (:126-129)
     const short2 p0 = qphtab[(off >> XL_PH_SHIFT) + (m >> XL_PH_SHIFT)];
     const int32_t ir = (int16_t)(qi & 0xFFFFu), ii = (int16_t)(qi >> 16);

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(64 * XL_WIDE_PARTS_MAX) void xl_wide_kernel(const X
 typedef const double __attribute__((address_space(4))) *cdouble_wp;
 
 // Q15 family (xlating.c:100-129) per lane, as xl_fir_q15_batch_kernel: int16 x int16 products summed exactly in float64 FMAs,
-// >> 15 (floor), saturated, rotated by the truncating Q15 phase
+// >> 15, cut to 32 bits, saturated (xl_q15_narrow.h), rotated by the truncating Q15 phase
 template <int FMT>
 __global__ __launch_bounds__(64) void xl_wide_q15_kernel(const XlWideArgs a) {
   const cu32_p cd = (cu32_p)(uintptr_t)(a.clients + blockIdx.y);
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(64) void xl_wide_q15_kernel(const XlWideArgs a) {
     acci = __builtin_fma(xi, hr, acci);
   }
   if (m >= K) return;
-  const int32_t ar = xl_sat16((int32_t)__builtin_floor(accr * (1.0 / 32768.0)));
-  const int32_t ai = xl_sat16((int32_t)__builtin_floor(acci * (1.0 / 32768.0)));
+  const int32_t ar = xl_q15_narrow_sum(accr);  // (xlating.c:118-119; xl_q15_narrow.h)
+  const int32_t ai = xl_q15_narrow_sum(acci);
   const short2 p0 = a.qphtab[(out_off >> XL_PH_SHIFT) + (m >> XL_PH_SHIFT)];
   const int32_t ir = (int16_t)(qi & 0xFFFFu), ii = (int16_t)(qi >> 16);
   int32_t pr = p0.x, pi = p0.y;

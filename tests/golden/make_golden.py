@@ -19,6 +19,9 @@ Outputs (data only -- numbers, never reference source text):
                                        "optimized" setting computes.  Head and tail of every block + block 9 in full.
   tests/golden/avx_g11_t101.npz        blocks 0-9 of the g11 shape from the reference built with -mavx but WITHOUT FMA (libref_avx.so).
   tests/golden/x86_long_g9.npz         the same AVX build over 400 blocks of the g9 shape, sampled (pins the no-renormalisation mode).
+  tests/golden/q15_wrap_t65700.npz     process_native_cs16_cs16 of the unmodified reference (canonical flags) on a window long enough
+                                       for the shifted Q15 sum to leave the int32 range (q15_extremes_cases.GOLDEN_WRAP); on its own:
+                                       python tests/golden/make_golden.py q15_wrap
   tests/golden/fast_divergence.json    how far the reference's own two builds drift apart over a long stream
                                        (canonical native vs AVX optimized; max |d| / max |y| per block).
 """
@@ -92,6 +95,7 @@ def main():
         total += sz
         print(f"{sc['name']:28s} T={taps.size:5d} D={sc['D']:4d} calls={len(sc['calls']):4d} -> {sz/1024:.1f} KiB")
     print(f"total {total/1024:.1f} KiB")
+    make_q15_wrap()
     make_fast()
 
 
@@ -167,6 +171,21 @@ def make_avx_g11():
     print(f"avx_g11_t101 -> {os.path.getsize(p)/1024:.1f} KiB")
 
 
+def make_q15_wrap():
+    """tests/golden/q15_wrap_t65700.npz: 65700 taps of 0.9999, D = 1000, fc = 0, one cs16 block of I = +32767, Q = 0 through the
+    reference's process_native_cs16_cs16.  From output 65 on the shifted sum exceeds 2^31 - 1: saturate_to_int16(int32_t) receives its
+    low 32 bits (xlating.c:118), a negative number."""
+    import q15_extremes_cases as QC
+
+    g = QC.GOLDEN_WRAP
+    ref = RefLib(g["D"], QC.wrap_taps(g["T"]), g["fc"], QC.FS, 2 * g["samples"])
+    y = ref.process(g["fmt"], QC.wrap_block(g["fmt"], g["block"], g["samples"]), "cs16")
+    ref.close()
+    p = os.path.join(HERE, "q15_wrap_t65700.npz")
+    np.savez_compressed(p, y=y)
+    print(f"q15_wrap_t65700 outputs={len(y)} -> {os.path.getsize(p)} bytes")
+
+
 def make_x86_long():
     """tests/golden/x86_long_g9.npz: the reference's AVX process_optimized_cu8_cf32 (oracle/_ref/libref_fast.so) over a LONG
     stream -- 400 server-default blocks, where its never-renormalised phasor has drifted by 1.5e-3 in amplitude -- sampled at
@@ -191,4 +210,8 @@ def make_x86_long():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["q15_wrap"]:
+        build(ref=True)
+        make_q15_wrap()
+    else:
+        main()
