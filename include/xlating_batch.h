@@ -64,7 +64,7 @@ int xlating_batch_create(uint32_t sampling_freq, int input_format, uint32_t max_
 int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint32_t max_input_buffer_length,
                                  unsigned max_group_blocks, int device, xlating_batch **batch);
 
-/* Plan options (result-neutral: every setting passes the same parity tests).  Eight of them; name / value:
+/* Plan options (result-neutral: every setting passes the same parity tests).  Nine of them; name / value:
  *   "polyphase"         -1 by the size rule (default: classes of >= 32 clients with >= 2 taps per polyphase branch), 0 never, 1
  *                       whenever the shape allows: which classes take the polyphase overlap-save path in XL_MODE_OPTIMIZED
  *   "polyphase_m"       0 by the size rule, 64, 128, 256: its transform length (the rule: 64 points for classes of more than 64 branches with up
@@ -105,6 +105,13 @@ int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint3
  *                       server's own filter) is filtered by the wide direct kernel (csrc/xl_wide.hip) in a launch of its own; with a
  *                       value set, those clients read a second raw history of that many samples (max_window x bytes per sample x 2 of
  *                       device memory, allocated when the option is set).  Settable only while the engine has no clients (-EBUSY)
+ *   "q15_kernel"        XL_MODE_Q15 calls: 0 (default) = every client on the float64 FIR launches (the exact integer sums carried in
+ *                       v_fma_f64); 1 = every client the host proves eligible on ONE matrix-core launch (csrc/q15mm/xl_q15_mm.hip: the
+ *                       same integer sums from int8 digit products, v_mfma_i32_32x32x32_i8 with exact i32 accumulation; outputs
+ *                       identical bit for bit).  Eligible: not a wide client, and every rotated Q15 tap cr in -32768 .. 32639, ci in
+ *                       -32639 .. 32639 (each has an int8 digit pair; xlating_batch_q15_matrix_admits below).  The others -- such taps,
+ *                       wide clients -- stay on the launches they have, inside the same call; xlating_batch_describe counts both sides.
+ *                       Opt-in: which engine sizes should take it by default is decided from profiles/q15_matrix_bench.txt, later
  * Returns 0, -ENOENT (unknown name), -EINVAL, -EBUSY ("max_window" with clients), -ENOMEM.  The plan is rebuilt at the next call.
  * (Launch-shaping knobs of the tuning sessions -- tile heights, riders, slices, passes per workgroup, calls per chain launch, the
  * size rule's client threshold -- are not options: they are read from XL_EXP_* environment variables when an engine is created,
@@ -112,6 +119,11 @@ int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint3
  * ignores every XL_EXP_* variable and logs one "<4>" line if any is set; rounds 1-4's measured-and-lost kernel variants are gone from
  * the library: tools/experiments/retired/.) */
 int xlating_batch_set_option(xlating_batch *batch, const char *name, long value);
+
+/* Would an XL_MODE_Q15 call of an engine with option "q15_kernel" = 1 filter this client on the matrix cores?  1 or 0, decided by the
+ * host code the plan runs (the taps quantised and rotated as for xlating_batch_add_client, then the digit proof); touches no device. */
+int xlating_batch_q15_matrix_admits(uint32_t decimation, const float *taps, size_t taps_len, int32_t center_freq,
+                                    uint32_t sampling_freq);
 
 /* Add a client whose stream starts with the NEXT block (like dsp_worker_start, dsp_worker.c:90-108).
  * `taps` is the real low-pass prototype (lpf.h); it is COPIED (unlike create_frequency_xlating_filter

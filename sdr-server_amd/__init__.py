@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = (
     ["SIMD_STATUS", "create_frequency_xlating_filter", "destroy_xlating", "create_low_pass_filter"]
     + [f"process_{v}_{i}_{o}" for v in ("native", "optimized") for i in ("cu8", "cs8", "cs16") for o in ("cf32", "cs16")]
     + ["process_native_cf32_cf32", "process_optimized_cf32_cf32", "xlating_set_optimized_x86"]
-    + ["xlating_batch_create", "xlating_batch_create_grouped", "xlating_batch_set_option", "xlating_batch_process_host_group",
+    + ["xlating_batch_create", "xlating_batch_create_grouped", "xlating_batch_set_option", "xlating_batch_q15_matrix_admits", "xlating_batch_process_host_group",
        "xlating_batch_process_device_group", "xlating_batch_process_device_group_ev", "xlating_batch_output_len_block", "xlating_batch_add_client", "xlating_batch_remove_client", "xlating_batch_num_clients",
        "xlating_batch_process_host", "xlating_batch_process_device", "xlating_batch_output_len", "xlating_batch_fetch",
        "xlating_batch_output_host", "xlating_batch_output_host_cs16", "xlating_batch_output_device", "xlating_batch_client_phase", "xlating_batch_sync",
@@ -164,6 +164,8 @@ def lib():
     L.xlating_batch_create_grouped.restype = C.c_int
     L.xlating_batch_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
     L.xlating_batch_set_option.restype = C.c_int
+    L.xlating_batch_q15_matrix_admits.argtypes = [C.c_uint32, _c_float_p, C.c_size_t, C.c_int32, C.c_uint32]
+    L.xlating_batch_q15_matrix_admits.restype = C.c_int
     L.xlating_batch_process_host_group.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int]
     L.xlating_batch_process_host_group.restype = C.c_int
     L.xlating_batch_process_device_group.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p]
@@ -286,6 +288,13 @@ class XlatingError(RuntimeError):
     def __init__(self, what, code):
         super().__init__(f"{what} failed with code {code}")
         self.code = code
+
+
+def q15_matrix_admits(decimation, taps, center_freq, sampling_freq):
+    """Would a Q15 call of an engine with option "q15_kernel" = 1 filter this client on the matrix cores?  (Host code only: no device.)"""
+    taps = np.ascontiguousarray(taps, dtype=np.float32)
+    return bool(lib().xlating_batch_q15_matrix_admits(int(decimation), taps.ctypes.data_as(_c_float_p), taps.size, int(center_freq),
+                                                      int(sampling_freq)))
 
 
 class XlatingFilter:

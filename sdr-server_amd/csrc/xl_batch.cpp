@@ -97,6 +97,14 @@ struct xlating_batch_t {
   std::map<void *, size_t> plan_caps;
   std::vector<void *> plan_spare;
   bool want_q15 = false;  // the Q15 tap image is built from the first XL_MODE_Q15 call on
+  // option "q15_kernel": 0 (default) = XL_MODE_Q15 calls run every non-wide client on the float64 launches (launches[], d_qtaps);
+  // 1 = the clients the host proves eligible (xl_q15_digits.h) on one matrix-core launch (qmm), the others on float64 launches of their
+  // own (launches_q15; d_qtaps is then THEIR image).  Built with the all-clients set (xl_batch_build_all_set).
+  uint32_t q15_kernel = 0;
+  XlQmmPlan qmm;
+  XlQmmTile *d_qmm_tiles = nullptr;
+  int8_t *d_qmm_image = nullptr;
+  Launch launches_q15[XL_NLAUNCH];
   int planned_immature = 0;  // clients that were not mature when the plan was built (they merge once they are)
   uint32_t trel = 0;         // samples consumed since the plan was built (XlPos::trel)
   uint64_t calls_since_plan = 0;  // calls run with the current plan (their outputs live in its rows)
@@ -308,11 +316,22 @@ static void xl_release_launch_set(xlating_batch *b, Launch *set) {
   }
 }
 
+// the matrix-core Q15 launch and the float64 launch set beside it (option "q15_kernel")
+static void xl_release_q15_matrix(xlating_batch *b) {
+  xl_release_launch_set(b, b->launches_q15);
+  xl_plan_release(b, b->d_qmm_tiles);
+  xl_plan_release(b, b->d_qmm_image);
+  b->d_qmm_tiles = nullptr;
+  b->d_qmm_image = nullptr;
+  b->qmm = XlQmmPlan();
+}
+
 // Drops what a plan builds from scratch every time (launch sets, tap images, NCO records).  The polyphase classes
 // survive re-plans (xl_batch_plan takes over the ones that still fit); `all` releases them too.
 static void xl_batch_free_plan(xlating_batch *b, bool all) {
   xl_release_launch_set(b, b->launches);
   xl_release_launch_set(b, b->launches_rest);
+  xl_release_q15_matrix(b);
   b->all_built = false;
   if (all) {
     for (PolyClass &pc : b->poly) xl_poly_release(b, pc);
@@ -425,6 +444,9 @@ extern "C" int xlating_batch_set_option(xlating_batch *b, const char *name, long
   } else if (n == "nco_side_stream") {
     if (value < -1 || value > 1) return -EINVAL;
     b->nco_side = (int)value;
+  } else if (n == "q15_kernel") {
+    if (value != 0 && value != 1) return -EINVAL;
+    b->q15_kernel = (uint32_t)value;
   } else if (n == "max_window") {  // an admission setting: the ring's size is fixed while clients read it
     if (value != 0 && (value <= (long)XL_HCAP || value > (1l << 20))) return -EINVAL;
     if (b->nalive > 0) return -EBUSY;
@@ -541,6 +563,21 @@ extern "C" int xlating_batch_create(uint32_t sampling_freq, int input_format, ui
   return xlating_batch_create_grouped(sampling_freq, input_format, max_input_buffer_length, 1, device, batch);
 }
 
+// Would the matrix-core Q15 launch (option "q15_kernel") carry this client?  The host code the plan runs, no device.
+extern "C" int xlating_batch_q15_matrix_admits(uint32_t decimation, const float *taps, size_t taps_len, int32_t center_freq,
+                                               uint32_t sampling_freq) {
+  if (taps == nullptr || taps_len == 0 || decimation == 0 || sampling_freq == 0 || taps_len - 1 + decimation > XL_HCAP) return 0;
+  if (xl_fir_needs_wide(decimation, (uint32_t)taps_len, 12u)) return 0;  // (a wide client: its own launch)
+  const uint32_t T = (uint32_t)taps_len, ksteps = xl_q15mm_ksteps(T);
+  if (xl_q15mm_pick_nc(decimation, ksteps) == 0u || !xl_q15mm_acc_bounded(ksteps)) return 0;
+  std::vector<float> rt(2 * (size_t)xl_roundup(T, XL_TAP_UNROLL), 0.0f);
+  std::vector<int16_t> rtq(2 * taps_len, 0);
+  float incr[2];
+  int16_t qincr[2];
+  xl_prepare_taps(taps, taps_len, center_freq, sampling_freq, decimation, rt.data(), rtq.data(), incr, qincr);
+  return xl_q15mm_admits_taps(rtq.data(), T);
+}
+
 extern "C" int xlating_batch_num_clients(const xlating_batch *b) { return b ? b->nalive : 0; }
 
 extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, const float *taps, size_t taps_len,
@@ -577,6 +614,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   c.rt.assign(2 * (size_t)Tpad, 0.0f);
   c.rtq.assign(2 * taps_len, 0);
   xl_prepare_taps(taps, taps_len, center_freq, b->fs, decimation, c.rt.data(), c.rtq.data(), c.incr, c.qincr);
+  c.qmm_digits = xl_q15mm_admits_taps(c.rtq.data(), c.T) != 0;
   c.out_cap = b->gcap * (b->max_samples / decimation + 1);  // xlating.c:568 per block
   c.row_len = xl_roundup(c.out_cap, 2 * XL_PH_STRIDE);  // rows start at multiples of 2 strides: the NCO role stores pairs of
                                                         // table entries as 16 bytes
@@ -650,6 +688,7 @@ static XlPlanOpts xl_plan_opts(const xlating_batch *b) {
   o.poly_mode = b->poly_mode, o.poly_min_set = b->poly_min_set, o.poly_min_clients = b->poly_min_clients, o.poly_m = b->poly_m;
   o.mix_kernel = b->mix_kernel, o.mix_img = b->mix_img, o.riders = b->riders, o.riders_min_wgs = b->riders_min_wgs;
   o.exp_h = b->exp_h, o.nco_side = b->nco_side, o.expected_clients = b->expected_clients;
+  o.q15_kernel = b->q15_kernel;
   return o;
 }
 
@@ -685,16 +724,39 @@ static int xl_batch_build_all_set(xlating_batch *b) {
   xl_plan_release(b, b->d_taps);
   xl_plan_release(b, b->d_qtaps);
   xl_plan_release(b, b->d_qinc);
+  xl_release_q15_matrix(b);
   b->d_taps = nullptr;
   b->d_qtaps = nullptr;
   b->d_qinc = nullptr;
   std::vector<float> image;
   std::vector<double> imageq;
   const bool has_q15 = b->fmt != XL_FMT_CF32 && b->want_q15;
-  int rc = xl_build_launches(xl_plan_opts(b), b->clients, b->launches, b->classes, b->big_h, &image, has_q15 ? &imageq : nullptr);
+  const bool matrix = has_q15 && b->q15_kernel == 1u;  // (the all-clients set then carries no Q15 image: d_qtaps is launches_q15's)
+  const bool all_q = has_q15 && !matrix;
+  int rc = xl_build_launches(xl_plan_opts(b), b->clients, b->launches, b->classes, b->big_h, &image, all_q ? &imageq : nullptr);
   if (rc != 0) return rc;
-  rc = xl_upload_launch_set(b, b->launches, image, &b->d_taps, has_q15 ? &imageq : nullptr);
+  rc = xl_upload_launch_set(b, b->launches, image, &b->d_taps, all_q ? &imageq : nullptr);
   if (rc != 0) return rc;
+  if (matrix) {
+    std::vector<bool> rest_use(b->clients.size(), true);
+    for (size_t i = 0; i < b->clients.size(); ++i)
+      if (b->clients[i].wide) rest_use[i] = false;
+    xl_build_q15mm(xl_plan_opts(b), b->clients, b->classes, &b->qmm, &rest_use);
+    std::vector<DirectClass> classes_q;
+    xl_direct_classes(b->clients, rest_use, &classes_q);
+    std::vector<float> image_q;  // (the float taps of the set: not uploaded, Q15 calls read d_qtaps only)
+    rc = xl_build_launches(xl_plan_opts(b), b->clients, b->launches_q15, classes_q, b->big_h, &image_q, &imageq);
+    if (rc != 0) return rc;
+    rc = xl_upload_launch_set(b, b->launches_q15, std::vector<float>(), &b->d_taps, &imageq);
+    if (rc != 0) return rc;
+    if (!b->qmm.tiles.empty()) {
+      XL_TRY(xl_plan_alloc(b, (void **)&b->d_qmm_tiles, b->qmm.tiles.size() * sizeof(XlQmmTile)));
+      XL_TRY(hipMemcpy(b->d_qmm_tiles, b->qmm.tiles.data(), b->qmm.tiles.size() * sizeof(XlQmmTile), hipMemcpyHostToDevice));
+      XL_TRY(xl_plan_alloc(b, (void **)&b->d_qmm_image, b->qmm.image.size()));
+      XL_TRY(hipMemcpy(b->d_qmm_image, b->qmm.image.data(), b->qmm.image.size(), hipMemcpyHostToDevice));
+      std::vector<int8_t>().swap(b->qmm.image);  // (the host copy has served)
+    }
+  }
   if (has_q15) {
     std::vector<uint32_t> qinc;
     for (const XlNcoClient &nc : b->nco) {
@@ -1316,12 +1378,27 @@ fail:
 // position and is dropped.
 XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
   hipStream_t s = c.s;
+  const bool matrix = b->q15_kernel == 1u;  // the eligible clients on the matrix cores, the float64 launches over the others
   if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[b->spec_ev], 0));
   b->spec_n = 0;
   b->poisoned = true;
   XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, (uint32_t)b->nco.size(), b->d_qphase, b->d_qphtab, c.pos, s));
+  if (matrix && !b->qmm.tiles.empty() && c.maxK > 0) {
+    XlQmmArgs m;
+    memset(&m, 0, sizeof(m));
+    m.in0 = b->d_hist[c.hb], m.n0 = XL_HCAP, m.in1 = c.d_blocks, m.n1 = c.N;
+    m.fmt = b->fmt, m.pos = c.pos;
+    m.tiles = b->d_qmm_tiles, m.ntiles = (uint32_t)b->qmm.tiles.size();
+    for (const XlQmmTile &t : b->qmm.tiles)
+      m.xtiles = std::max(m.xtiles, (xl_grid_dyn(t.D, t.T, t.rem0, t.hv0, c.pos).K + XL_QMM_WAVES * t.nc - 1u) / (XL_QMM_WAVES * t.nc));
+    m.image = b->d_qmm_image, m.qphtab = b->d_qphtab, m.out = b->d_out[c.p];
+    if (m.xtiles > 0) {
+      xl_call_roll_args(b, c, m);
+      XL_TRY(xl_launch_q15_mm(m, b->qmm.lds, s));
+    }
+  }
   for (int lq = 0; lq < XL_NLAUNCH && c.maxK > 0; ++lq) {
-    Launch &L = b->launches[lq];
+    Launch &L = matrix ? b->launches_q15[lq] : b->launches[lq];
     if (L.groups.empty()) continue;
     XlFirArgs a;
     xl_call_fir_args(b, c, L, a);
@@ -1721,6 +1798,16 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
   if (!b->wide.empty()) {
     d += " | wide: " + std::to_string(b->wide.size()) + " clients";
     if (b->max_window) d += " window<=" + std::to_string(b->max_window);
+  }
+  if (b->q15_kernel == 1u && b->fmt != XL_FMT_CF32) {
+    d += " | q15 matrix:";
+    if (!b->all_built || !b->want_q15) {
+      d += " (built by the first Q15 call)";
+    } else {
+      d += " " + std::to_string(b->qmm.nclients) + " clients x " + std::to_string(b->qmm.tiles.size()) + " tiles, float64: " +
+           std::to_string(b->qmm.fb_digits + b->qmm.fb_window) + " clients (digits " + std::to_string(b->qmm.fb_digits) + ", window " +
+           std::to_string(b->qmm.fb_window) + ")";
+    }
   }
   if (b->reserve_r) d += " | side kernel: " + std::to_string(8u * b->reserve_r) + " CUs reserved";
   if (pending) d += " | re-plan pending (client set or options changed: the next process call plans again)";

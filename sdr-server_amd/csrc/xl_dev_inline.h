@@ -57,6 +57,23 @@ XL_DEV v2f xl_sample_q15(const void *__restrict__ p, int fmt, uint32_t i) {
   return r;
 }
 
+// The epilogue of the batched Q15 FIR kernels (xl_fir_q15_batch_kernel, xl_q15_mm_kernel), per (client, output m): (ar, ai) are the
+// narrowed sums (xlating.c:118-119).  The output's phase is the tabulated one below it stepped m % XL_PH_STRIDE times (:126-129);
+// rotate, two saturating shifts (:121-124), one short2 store into the client's row.  off: the row (float2 index), qi: packed increment.
+XL_DEV void xl_q15_rotate_store(const short2 *__restrict__ qphtab, float2 *out, uint32_t off, uint32_t qi, uint32_t m, int32_t ar,
+                                int32_t ai) {
+  const short2 p0 = qphtab[(off >> XL_PH_SHIFT) + (m >> XL_PH_SHIFT)];
+  const int32_t ir = (int16_t)(qi & 0xFFFFu), ii = (int16_t)(qi >> 16);
+  int32_t pr = p0.x, pi = p0.y;
+  for (uint32_t j = m & (XL_PH_STRIDE - 1u); j > 0u; --j) {
+    const int32_t tr = pr * ir - pi * ii, ti = pr * ii + pi * ir;
+    pr = xl_sat16(tr >> 15);
+    pi = xl_sat16(ti >> 15);
+  }
+  const int32_t orr = ar * pr - ai * pi, oi = ar * pi + ai * pr;
+  reinterpret_cast<short2 *>(out + off)[m] = make_short2((short)xl_sat16(orr >> 15), (short)xl_sat16(oi >> 15));
+}
+
 // ------------------------------------------------------------------------------------------- complex arithmetic
 // One complex accumulator per (output, client).
 // MODE 0 (native): the reference's scalar expression tree, xlating.c:68 `temp += x * h` in C99 complex float:

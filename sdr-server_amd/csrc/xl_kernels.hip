@@ -1055,17 +1055,8 @@ __global__ __launch_bounds__(64 * XL_NW_MAX) void xl_fir_q15_batch_kernel(const 
     // >> 15 of the int64 sums, cut to 32 bits, saturated (xlating.c:118-119; xl_q15_narrow.h)
     const int32_t ar = xl_q15_narrow_sum(accr[c]);
     const int32_t ai = xl_q15_narrow_sum(acci[c]);
-    // this output's phase: the tabulated one below it, stepped m % XL_PH_STRIDE times (:126-129)
-    const short2 p0 = qphtab[(off >> XL_PH_SHIFT) + (m >> XL_PH_SHIFT)];
-    const int32_t ir = (int16_t)(qi & 0xFFFFu), ii = (int16_t)(qi >> 16);
-    int32_t pr = p0.x, pi = p0.y;
-    for (uint32_t j = m & (XL_PH_STRIDE - 1u); j > 0u; --j) {
-      const int32_t tr = pr * ir - pi * ii, ti = pr * ii + pi * ir;
-      pr = xl_sat16(tr >> 15);
-      pi = xl_sat16(ti >> 15);
-    }
-    const int32_t orr = ar * pr - ai * pi, oi = ar * pi + ai * pr;  // xlating.c:121-124
-    reinterpret_cast<short2 *>(a.out + off)[m] = make_short2((short)xl_sat16(orr >> 15), (short)xl_sat16(oi >> 15));
+    // this output's phase, the rotation, the store (:121-129): shared with the matrix-core kernel
+    xl_q15_rotate_store(qphtab, a.out, off, qi, m, ar, ai);
   }
 }
 

@@ -212,6 +212,60 @@ int xl_build_launches(const XlPlanOpts &o, const std::vector<Client> &clients, L
   return 0;
 }
 
+// The matrix-core Q15 launch: one tile per 32 eligible members of a direct class (one grid: clients of one (D, T) that joined at other
+// stream positions are tiles of their own).  Eligibility is proved here, per client, before anything reaches the device.
+void xl_build_q15mm(const XlPlanOpts &o, const std::vector<Client> &clients, const std::vector<DirectClass> &classes, XlQmmPlan *plan,
+                    std::vector<bool> *rest_use) {
+  *plan = XlQmmPlan();
+  uint64_t frags = 0;
+  std::vector<std::pair<size_t, std::vector<int>>> tiles;  // (class, members)
+  for (size_t k = 0; k < classes.size(); ++k) {
+    const DirectClass &cs = classes[k];
+    const uint32_t ksteps = xl_q15mm_ksteps(cs.T);
+    const bool fits = xl_q15mm_pick_nc(cs.D, ksteps) != 0u && xl_q15mm_acc_bounded(ksteps);  // proof (b)
+    std::vector<int> ok;
+    for (int id : cs.members) {
+      if (!fits)
+        plan->fb_window++;
+      else if (!clients[id].qmm_digits)  // proof (a), taken when the client joined
+        plan->fb_digits++;
+      else
+        ok.push_back(id);
+    }
+    for (size_t next = 0; next < ok.size(); next += XL_QMM_ROWS) {
+      const size_t cnt = std::min<size_t>(XL_QMM_ROWS, ok.size() - next);
+      tiles.emplace_back(k, std::vector<int>(ok.begin() + next, ok.begin() + next + cnt));
+      frags += xl_q15mm_image_bytes(cs.D, ksteps) / XL_QMM_FRAG;
+    }
+  }
+  plan->image.assign((size_t)frags * XL_QMM_FRAG, 0);
+  uint32_t frag_off = 0;
+  for (const auto &td : tiles) {
+    const DirectClass &cs = classes[td.first];
+    XlQmmTile t;
+    memset(&t, 0, sizeof(t));
+    t.D = cs.D, t.T = cs.T, t.ksteps = xl_q15mm_ksteps(cs.T);
+    t.rem0 = cs.rem0, t.hv0 = cs.hv0;
+    t.nc = xl_q15mm_pick_nc(cs.D, t.ksteps);
+    t.nclients = (uint32_t)td.second.size();
+    t.frag_off = frag_off;
+    int8_t *img = plan->image.data() + (size_t)frag_off * XL_QMM_FRAG;
+    for (size_t j = 0; j < td.second.size(); ++j) {
+      const Client &c = clients[td.second[j]];
+      t.out_off[j] = c.out_off;
+      t.qincr[j] = (uint32_t)(uint16_t)c.qincr[0] | ((uint32_t)(uint16_t)c.qincr[1] << 16);
+      t.corr_r[j] = xl_q15mm_correction(c.rtq.data(), cs.T, 0);
+      t.corr_i[j] = xl_q15mm_correction(c.rtq.data(), cs.T, 1);
+      xl_q15mm_fill_row(img, (uint32_t)j, c.rtq.data(), cs.T, cs.D, t.ksteps);
+      (*rest_use)[td.second[j]] = false;
+    }
+    frag_off += (uint32_t)(xl_q15mm_image_bytes(cs.D, t.ksteps) / XL_QMM_FRAG);
+    plan->lds = std::max(plan->lds, xl_q15mm_lds_bytes(t, o.fmt));
+    plan->nclients += t.nclients;
+    plan->tiles.push_back(t);
+  }
+}
+
 // complex MACs per sample of a block of the direct launches over `classes`
 double xl_direct_macs(const std::vector<DirectClass> &classes) {
   double macs = 0.0;

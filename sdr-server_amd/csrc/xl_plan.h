@@ -11,6 +11,7 @@
 
 #include "xl_device.h"
 #include "xl_polyphase.h"
+#include "xl_q15_mm.h"
 
 #define XL_NLAUNCH 7
 
@@ -25,6 +26,7 @@ struct XlPlanOpts {
   bool riders;
   int riders_min_wgs, exp_h, nco_side;
   uint32_t expected_clients;
+  uint32_t q15_kernel;
 };
 
 struct Client {
@@ -41,6 +43,7 @@ struct Client {
   uint32_t last_K = 0;
   std::vector<uint32_t> last_Kg;  // outputs per block of the latest call
   bool planned_mature = false;
+  bool qmm_digits = false;  // every entry of its Q15 rows has an int8 digit pair (xl_q15_digits.h, proof (a)): the matrix-core Q15 launch may carry it
   bool wide = false;  // no LDS tile of the direct kernel fits its window image (xl_wide.h), or its window exceeds XL_HCAP: the wide kernel
 };
 
@@ -141,6 +144,20 @@ int xl_build_launches(const XlPlanOpts &o, const std::vector<Client> &clients, L
                       int big_h, std::vector<float> *image, std::vector<double> *imageq);
 double xl_direct_macs(const std::vector<DirectClass> &classes);  // complex MACs per sample of a block
 int xl_pick_tile_height(const XlPlanOpts &o, const std::vector<DirectClass> &classes);
+
+// ---- the matrix-core Q15 launch (option "q15_kernel"; xl_q15_mm.h)
+struct XlQmmPlan {
+  std::vector<XlQmmTile> tiles;
+  std::vector<int8_t> image;  // the tiles' A images (xl_q15mm_fill_row)
+  size_t lds = 0;             // window image bytes of the launch (max over its tiles)
+  uint32_t nclients = 0;      // clients the launch carries
+  uint32_t fb_digits = 0;     // non-wide clients left on the float64 launches: an entry without an int8 digit pair (proof (a))
+  uint32_t fb_window = 0;     // ... no window image of the launch fits their (D, T), or proof (b) fails (no non-wide shape does either)
+};
+// Tiles of up to 32 clients per direct class over the eligible members of `classes`; the clients the launch carries are cleared in
+// `rest_use` (the float64 launch set is built over what stays set).
+void xl_build_q15mm(const XlPlanOpts &o, const std::vector<Client> &clients, const std::vector<DirectClass> &classes, XlQmmPlan *plan,
+                    std::vector<bool> *rest_use);
 
 // ---- polyphase classes
 uint32_t xl_poly_pick_m(const XlPlanOpts &o, uint32_t A, size_t members, uint32_t D);

@@ -28,4 +28,8 @@ XL_Q15_FN int32_t xl_q15_narrow_sum(double acc) {
   return xl_sat16((int32_t)(uint32_t)(uint64_t)q);
 }
 
+/* The same for a sum held as an int64 (the matrix-core FIR, xl_q15_digits.h): the reference's own line, the cut written on unsigned
+ * values.  (>> of a negative int64 is the arithmetic shift on every compiler this project builds with; the reference relies on it too.) */
+XL_Q15_FN int32_t xl_q15_narrow_sum64(int64_t sum) { return xl_sat16((int32_t)(uint32_t)(uint64_t)(sum >> 15)); }
+
 #endif /* XL_Q15_NARROW_H_ */
