@@ -64,7 +64,7 @@ int xlating_batch_create(uint32_t sampling_freq, int input_format, uint32_t max_
 int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint32_t max_input_buffer_length,
                                  unsigned max_group_blocks, int device, xlating_batch **batch);
 
-/* Plan options (result-neutral: every setting passes the same parity tests).  Nine of them; name / value:
+/* Plan options (result-neutral: every setting passes the same parity tests).  Ten of them; name / value:
  *   "polyphase"         -1 by the size rule (default: classes of >= 32 clients with >= 2 taps per polyphase branch), 0 never, 1
  *                       whenever the shape allows: which classes take the polyphase overlap-save path in XL_MODE_OPTIMIZED
  *   "polyphase_m"       0 by the size rule, 64, 128, 256: its transform length (the rule: 64 points for classes of more than 64 branches with up
@@ -112,6 +112,14 @@ int xlating_batch_create_grouped(uint32_t sampling_freq, int input_format, uint3
  *                       -32639 .. 32639 (each has an int8 digit pair; xlating_batch_q15_matrix_admits below).  The others -- such taps,
  *                       wide clients -- stay on the launches they have, inside the same call; xlating_batch_describe counts both sides.
  *                       Opt-in: which engine sizes should take it by default is decided from profiles/q15_matrix_bench.txt, later
+ *   "q15_nco"           XL_MODE_Q15 calls: 0 (default) = the truncating int16 phase recurrence (xlating.c:126-129) is tabulated in front
+ *                       of every call's launches, on the call's stream; 1 = it is tabulated a call AHEAD, on the engine's side stream
+ *                       while the call's FIR launches run, guessing that the next Q15 call has the same block length and block count
+ *                       and follows directly (a wrong guess is tabulated again on the call's stream), by a kernel whose step is the
+ *                       single filter's five instructions, unrolled (csrc/xl_kernels.hip: xl_nco_q15_ahead_kernel).  Every phase is
+ *                       still the reference's own step applied to the one before it: outputs and phases identical bit for bit.
+ *                       xlating_batch_describe counts the look-aheads used and dropped since the option was set.  May be set at any
+ *                       time; setting it waits for and drops a pending look-ahead.  Works with "q15_kernel" 0 and 1.  Opt-in
  * Returns 0, -ENOENT (unknown name), -EINVAL, -EBUSY ("max_window" with clients), -ENOMEM.  The plan is rebuilt at the next call.
  * (Launch-shaping knobs of the tuning sessions -- tile heights, riders, slices, passes per workgroup, calls per chain launch, the
  * size rule's client threshold -- are not options: they are read from XL_EXP_* environment variables when an engine is created,
@@ -187,10 +195,16 @@ int xlating_batch_output_device(xlating_batch *batch, int client_id, const void 
 
 /* Current NCO phase of a client (synchronises the engine stream). */
 int xlating_batch_client_phase(xlating_batch *batch, int client_id, float *re, float *im);
+/* Current Q15 phase of a client (XL_MODE_Q15's own int16 phase, xlating.c:546-547: 32767 + 0j at the join): the COMMITTED one, after
+ * the latest processed call, whatever option "q15_nco" has tabulated ahead.  Synchronises like xlating_batch_client_phase.
+ * 0, -EINVAL (dead id, cf32 engine), -EIO. */
+int xlating_batch_client_phase_q15(xlating_batch *batch, int client_id, int16_t *re, int16_t *im);
 
-/* Block until all enqueued work of the engine has finished. */
+/* Block until all enqueued work of the engine has finished (a Q15 phase table being tabulated a call ahead included). */
 int xlating_batch_sync(xlating_batch *batch);
-/* Without blocking: 1 if everything enqueued by the process calls so far has completed, 0 if not yet; -EINVAL, -EIO.
+/* Without blocking: 1 if everything enqueued by the process calls so far has completed, 0 if not yet; -EINVAL, -EIO.  Both this and
+ * xlating_batch_record_event cover the calls' own launches only: not a look-ahead of option "q15_nco" on the side stream, whose table
+ * nothing but the next call reads (xlating_batch_sync and xlating_batch_destroy wait for it).
  * xlating_batch_record_event: record `hip_event` (a hipEvent_t of the engine's device) behind the latest call's launches, on the
  * stream(s) they were enqueued on -- what a caller needs to make another stream wait for the latest call without a per-call
  * event (a launch that carries a completion event delays the next launch by ~8 us: a fifth of a one-block call).  0, -EINVAL, -EIO. */

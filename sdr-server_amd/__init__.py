@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     + ["xlating_batch_create", "xlating_batch_create_grouped", "xlating_batch_set_option", "xlating_batch_q15_matrix_admits", "xlating_batch_process_host_group",
        "xlating_batch_process_device_group", "xlating_batch_process_device_group_ev", "xlating_batch_output_len_block", "xlating_batch_add_client", "xlating_batch_remove_client", "xlating_batch_num_clients",
        "xlating_batch_process_host", "xlating_batch_process_device", "xlating_batch_output_len", "xlating_batch_fetch",
-       "xlating_batch_output_host", "xlating_batch_output_host_cs16", "xlating_batch_output_device", "xlating_batch_client_phase", "xlating_batch_sync",
+       "xlating_batch_output_host", "xlating_batch_output_host_cs16", "xlating_batch_output_device", "xlating_batch_client_phase", "xlating_batch_client_phase_q15", "xlating_batch_sync",
        "xlating_batch_query", "xlating_batch_record_event", "xlating_batch_timing", "xlating_batch_timing_read", "xlating_batch_timing_polyphase", "xlating_batch_timing_stride", "xlating_batch_describe", "xlating_batch_destroy",
        "xlating_hip_device_info"]
     + ["xlating_sinks_create", "xlating_sinks_attach_fd", "xlating_sinks_attach_file", "xlating_sinks_write",
@@ -194,6 +194,8 @@ def lib():
     L.xlating_batch_output_device.restype = C.c_int
     L.xlating_batch_client_phase.argtypes = [C.c_void_p, C.c_int, _c_float_p, _c_float_p]
     L.xlating_batch_client_phase.restype = C.c_int
+    L.xlating_batch_client_phase_q15.argtypes = [C.c_void_p, C.c_int, _c_i16_p, _c_i16_p]
+    L.xlating_batch_client_phase_q15.restype = C.c_int
     L.xlating_batch_sync.argtypes = [C.c_void_p]
     L.xlating_batch_sync.restype = C.c_int
     L.xlating_batch_timing.argtypes = [C.c_void_p, C.c_int]
@@ -460,6 +462,14 @@ class BatchEngine:
         if code != 0:
             raise XlatingError("xlating_batch_client_phase", code)
         return np.float32(a.value), np.float32(b.value)
+
+    def phase_q15(self, cid):
+        """The client's committed Q15 phase (re, im) after the latest processed call."""
+        a, b = C.c_int16(), C.c_int16()
+        code = lib().xlating_batch_client_phase_q15(self.h, cid, C.byref(a), C.byref(b))
+        if code != 0:
+            raise XlatingError("xlating_batch_client_phase_q15", code)
+        return int(a.value), int(b.value)
 
     def sync(self):
         code = lib().xlating_batch_sync(self.h)

@@ -44,6 +44,7 @@
 #include "xl_mixf_layout.h"
 #include "xl_plan.h"
 #include "xl_polyphase.h"
+#include "xl_q15_ahead.h"
 #include "xl_taps.h"
 #include "xl_wide.h"
 #include "xl_xop_layout.h"
@@ -168,9 +169,26 @@ struct xlating_batch_t {
   float2 *d_taps_rest = nullptr;  // tap image of the optimized-mode launch set (the clients outside the polyphase classes)
   double *d_qtaps = nullptr;   // Q15 taps as doubles, same indexing as d_taps (XL_MODE_Q15)
   uint32_t *d_qinc = nullptr;  // per nco entry: packed Q15 phase increment
-  short2 *d_qphase = nullptr;  // per slot: running Q15 phase (xlating.c:546-547: starts at 32767 + 0j)
-  short2 *d_qphtab = nullptr;  // Q15 phase table (every XL_PH_STRIDE-th phase)
+  // per slot: running Q15 phase (xlating.c:546-547: starts at 32767 + 0j): [qcur] = the committed ones.  Option "q15_nco" = 0
+  // steps them in place; = 1 every tabulation goes [qcur] -> [qcur ^ 1] and the call's commit flips qcur
+  short2 *d_qphase[2] = {nullptr, nullptr};
+  int qcur = 0;
+  // Q15 phase tables (every XL_PH_STRIDE-th phase): [qtab] = the latest call's, the other one a spare ("q15_nco" = 1: the table
+  // of the call being tabulated, in-stream or a call ahead)
+  short2 *d_qphtab[2] = {nullptr, nullptr};
+  int qtab = 0;
   bool last_q15 = false;       // the latest call produced cs16 outputs
+  // option "q15_nco": 0 (default) = xl_nco_q15_batch_kernel in front of every Q15 call's launches, in place; 1 = every tabulation
+  // by xl_nco_q15_ahead_kernel, and behind a Q15 call the NEXT call's table (same shape assumed: xl_grid_next) on nco_stream while
+  // the call's launches run.  The decisions are xl_q15_ahead.h's.
+  uint32_t q15_nco = 0;
+  bool qa_pending = false;  // a look-ahead is in flight or complete: d_qphase[qcur ^ 1] and d_qphtab[qtab ^ 1] hold (or will hold) the call at qa_pos
+  XlPos qa_pos = {};
+  // ev_qchain: the look-ahead is complete.  ev_qready (recorded on the call's stream between its table and its FIR launches): the
+  // previous call's readers of the spare table have been passed, and the phases this call commits are written -- what the
+  // look-ahead launch overwrites and reads.  Created when the option is first set to 1.
+  hipEvent_t ev_qchain = nullptr, ev_qready = nullptr;
+  uint64_t qa_used = 0, qa_dropped = 0;  // since the option was set: look-aheads that served their call / that were tabulated for nothing
   XlNcoClient *d_nco = nullptr;
   float2 *d_out[2] = {nullptr, nullptr};
   int ocur = 0;  // d_out[ocur] holds the latest call's outputs
@@ -260,6 +278,13 @@ static void xl_batch_sync_all(xlating_batch *b) {
   if (b->nco_stream) (void)hipStreamSynchronize(b->nco_stream);
   if (b->cs_masked) (void)hipStreamSynchronize(b->cs_masked);
   if (b->nco_masked) (void)hipStreamSynchronize(b->nco_masked);
+}
+
+// Option "q15_nco": forget the table tabulated a call ahead.  The caller has waited for it (xl_batch_sync_all, or the call's
+// stream waits for ev_qchain): the committed phases d_qphase[qcur] and the latest call's table are untouched by it.
+static void xl_q15_ahead_drop(xlating_batch *b) {
+  if (b->qa_pending) b->qa_dropped++;
+  b->qa_pending = false;
 }
 
 // A plan buffer of at least `bytes`: the smallest spare one that fits (and is not more than twice too big), else a fresh
@@ -360,7 +385,7 @@ extern "C" void xlating_batch_destroy(xlating_batch *b) {
   xl_batch_sync_all(b);
   xl_batch_free_plan(b, true);
   xl_plan_trim(b);
-  void *dev[] = {b->d_hist[0], b->d_hist[1], b->d_whist[0], b->d_whist[1], b->d_block, b->d_out[0], b->d_out[1], b->d_W, b->d_phase_run, b->d_qphase, b->d_qphtab};
+  void *dev[] = {b->d_hist[0], b->d_hist[1], b->d_whist[0], b->d_whist[1], b->d_block, b->d_out[0], b->d_out[1], b->d_W, b->d_phase_run, b->d_qphase[0], b->d_qphase[1], b->d_qphtab[0], b->d_qphtab[1]};
   for (void *p : dev)
     if (p) (void)hipFree(p);
   for (int i = 0; i < XL_NTAB; ++i) {
@@ -383,6 +408,8 @@ extern "C" void xlating_batch_destroy(xlating_batch *b) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : b->ev_done)
     if (e) (void)hipEventDestroy(e);
+  if (b->ev_qchain) (void)hipEventDestroy(b->ev_qchain);
+  if (b->ev_qready) (void)hipEventDestroy(b->ev_qready);
   if (b->nco_stream) (void)hipStreamDestroy(b->nco_stream);
   if (b->cs_masked) (void)hipStreamDestroy(b->cs_masked);
   if (b->nco_masked) (void)hipStreamDestroy(b->nco_masked);
@@ -447,6 +474,22 @@ extern "C" int xlating_batch_set_option(xlating_batch *b, const char *name, long
   } else if (n == "q15_kernel") {
     if (value != 0 && value != 1) return -EINVAL;
     b->q15_kernel = (uint32_t)value;
+  } else if (n == "q15_nco") {
+    if (value != 0 && value != 1) return -EINVAL;
+    if (hipSetDevice(b->device) != hipSuccess) return -EIO;
+    xl_batch_sync_all(b);  // (a look-ahead in flight writes the buffers the next tabulation writes, whatever the option then says)
+    b->qa_pending = false;
+    b->qa_used = b->qa_dropped = 0;  // (counted since the option was set)
+    if (value == 1 && b->ev_qchain == nullptr) {
+      if (hipEventCreateWithFlags(&b->ev_qchain, hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&b->ev_qready, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (b->ev_qchain) (void)hipEventDestroy(b->ev_qchain);
+        b->ev_qchain = b->ev_qready = nullptr;
+        return -ENOMEM;
+      }
+    }
+    b->q15_nco = (uint32_t)value;
   } else if (n == "max_window") {  // an admission setting: the ring's size is fixed while clients read it
     if (value != 0 && (value <= (long)XL_HCAP || value > (1l << 20))) return -EINVAL;
     if (b->nalive > 0) return -EBUSY;
@@ -626,6 +669,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   (void)hipSetDevice(b->device);
   xl_batch_sync_all(b);
   b->spec_n = 0;
+  xl_q15_ahead_drop(b);
   // Every failure from here on rolls the client back (a phantom client with an undefined phase would otherwise be
   // planned and filtered on every later call, with no id in the caller's hands to remove it).
   auto rollback = [&](int code) {
@@ -640,32 +684,37 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
     // grow all running-phase buffers or none: allocate the whole new set first, swap it in only when complete
     const size_t ncap = std::max<size_t>(1024, 2 * b->clients.size());
     float2 *np[XL_NTAB] = {};
-    short2 *nq = nullptr;
-    bool ok = hipMalloc((void **)&nq, ncap * sizeof(short2)) == hipSuccess;
+    short2 *nq[2] = {nullptr, nullptr};
+    bool ok = true;
+    for (int i = 0; ok && i < 2; ++i) ok = hipMalloc((void **)&nq[i], ncap * sizeof(short2)) == hipSuccess;
     for (int i = 0; ok && i < XL_NTAB; ++i) ok = hipMalloc((void **)&np[i], ncap * sizeof(float2)) == hipSuccess;
     for (int i = 0; ok && i < XL_NTAB; ++i)
       if (b->d_phase[i]) ok = hipMemcpy(np[i], b->d_phase[i], b->phase_cap * sizeof(float2), hipMemcpyDeviceToDevice) == hipSuccess;
-    if (ok && b->d_qphase) ok = hipMemcpy(nq, b->d_qphase, b->phase_cap * sizeof(short2), hipMemcpyDeviceToDevice) == hipSuccess;
+    for (int i = 0; ok && i < 2; ++i)
+      if (b->d_qphase[i]) ok = hipMemcpy(nq[i], b->d_qphase[i], b->phase_cap * sizeof(short2), hipMemcpyDeviceToDevice) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
       for (int i = 0; i < XL_NTAB; ++i)
         if (np[i]) (void)hipFree(np[i]);
-      if (nq) (void)hipFree(nq);
+      for (int i = 0; i < 2; ++i)
+        if (nq[i]) (void)hipFree(nq[i]);
       return rollback(-ENOMEM);
     }
     for (int i = 0; i < XL_NTAB; ++i) {
       if (b->d_phase[i]) (void)hipFree(b->d_phase[i]);
       b->d_phase[i] = np[i];
     }
-    if (b->d_qphase) (void)hipFree(b->d_qphase);
-    b->d_qphase = nq;
+    for (int i = 0; i < 2; ++i) {
+      if (b->d_qphase[i]) (void)hipFree(b->d_qphase[i]);
+      b->d_qphase[i] = nq[i];
+    }
     b->phase_cap = ncap;
   }
   {
     const float2 one = make_float2(1.0f, 0.0f);
     const short2 qone = make_short2(INT16_MAX, 0);  // xlating.c:546-547
     if (hipMemcpy(b->d_phase[b->pcur] + id, &one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
-    if (hipMemcpy(b->d_qphase + id, &qone, sizeof(qone), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
+    if (hipMemcpy(b->d_qphase[b->qcur] + id, &qone, sizeof(qone), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
   }
   return id;
 }
@@ -720,6 +769,7 @@ fail:
 static int xl_batch_build_all_set(xlating_batch *b) {
   if (b->all_built) return 0;
   xl_batch_sync_all(b);  // (launches in flight may still read the previous image)
+  xl_q15_ahead_drop(b);  // (... and a Q15 look-ahead the increments released below)
   xl_release_launch_set(b, b->launches);
   xl_plan_release(b, b->d_taps);
   xl_plan_release(b, b->d_qtaps);
@@ -973,6 +1023,7 @@ static int xl_batch_plan(xlating_batch *b) {
   xl_batch_sync_all(b);
   lap("sync");
   b->spec_n = 0;
+  xl_q15_ahead_drop(b);
   const uint32_t advanced = b->trel;  // samples since the previous plan: every plan-time stream record moves by this much
   xl_batch_free_plan(b, false);
   b->classes.clear();
@@ -1112,9 +1163,11 @@ static int xl_batch_plan(xlating_batch *b) {
       b->d_phtab[i] = nullptr;
     }
     b->out_alloc = 0;
-    if (b->d_qphtab) (void)hipFree(b->d_qphtab);
-    b->d_qphtab = nullptr;
-    XL_TRY(hipMalloc((void **)&b->d_qphtab, (want / XL_PH_STRIDE + 8) * sizeof(short2)));
+    for (int i = 0; i < 2; ++i) {
+      if (b->d_qphtab[i]) (void)hipFree(b->d_qphtab[i]);
+      b->d_qphtab[i] = nullptr;
+    }
+    for (int i = 0; i < 2; ++i) XL_TRY(hipMalloc((void **)&b->d_qphtab[i], (want / XL_PH_STRIDE + 8) * sizeof(short2)));
     for (int i = 0; i < 2; ++i) XL_TRY(hipMalloc((void **)&b->d_out[i], want * sizeof(float2)));
     for (int i = 0; i < XL_NTAB; ++i)
       XL_TRY(hipMalloc((void **)&b->d_phtab[i], (want / XL_PH_STRIDE + 8) * sizeof(float2)));  // every XL_PH_STRIDE-th phase
@@ -1249,8 +1302,8 @@ XL_STAGE void xl_call_fir_args(const xlating_batch *b, const XlCall &c, const La
   a.out = b->d_out[c.p];
 }
 
-// The wide clients' launch (see xl_batch_wide_maxk); Q15 calls pass no float table.
-static hipError_t xl_batch_wide_launch(xlating_batch *b, const XlCall &c, const float2 *phtab) {
+// The wide clients' launch (see xl_batch_wide_maxk); Q15 calls pass their own table and no float table.
+static hipError_t xl_batch_wide_launch(xlating_batch *b, const XlCall &c, const float2 *phtab, const short2 *qphtab = nullptr) {
   XlWideArgs w;
   memset(&w, 0, sizeof(w));
   const bool big = b->max_window != 0;
@@ -1262,7 +1315,7 @@ static hipError_t xl_batch_wide_launch(xlating_batch *b, const XlCall &c, const 
   w.xtiles = (c.maxKw + 63u) / 64u;
   w.parts = c.mode == XL_MODE_OPTIMIZED ? xl_wide_parts(b->wide_tpad_max) : 1u;
   w.taps = b->d_wtaps, w.phtab = phtab, w.out = b->d_out[c.p];
-  w.qtaps = b->d_wqtaps, w.qphtab = b->d_qphtab;
+  w.qtaps = b->d_wqtaps, w.qphtab = qphtab;
   return xl_launch_wide(c.mode == XL_MODE_Q15 ? 2 : (c.mode == XL_MODE_OPTIMIZED ? 1 : 0), w, c.s);
 }
 
@@ -1376,13 +1429,41 @@ fail:
 // Stage 2: the Q15 family (xlating.c:92-140, 416-447), a whole call: its own phase (never renormalised), the same raw
 // history.  The float phases stay where they are; a float phase table tabulated ahead was for a call at this stream
 // position and is dropped.
+//
+// The Q15 phase table.  Option "q15_nco" = 0: xl_nco_q15_batch_kernel on the call's stream, in place on d_qphase[qcur], into
+// d_qphtab[qtab].  = 1: xl_nco_q15_ahead_kernel, d_qphase[qcur] -> d_qphase[qcur ^ 1] into the spare table d_qphtab[qtab ^ 1] --
+// by the previous call on nco_stream if its guess (same shape, right behind it: xl_q15_ahead_serves) holds, else here on the call's
+// stream; the commit flips qcur and qtab.  Behind the commit the next call's table is started on nco_stream (xl_q15_ahead_may_launch),
+// which first waits for ev_qready: recorded between this call's table and its FIR launches, it stands for the readers of the table
+// about to be overwritten (the previous call's) and for the phases the look-ahead starts from (this call's).
 XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
   hipStream_t s = c.s;
   const bool matrix = b->q15_kernel == 1u;  // the eligible clients on the matrix cores, the float64 launches over the others
+  const bool ahead = b->q15_nco == 1u;
+  const uint32_t ncl = (uint32_t)b->nco.size();
+  const short2 *qphtab = b->d_qphtab[b->qtab];
   if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[b->spec_ev], 0));
   b->spec_n = 0;
   b->poisoned = true;
-  XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, (uint32_t)b->nco.size(), b->d_qphase, b->d_qphtab, c.pos, s));
+  if (!ahead) {
+    if (b->qa_pending) XL_TRY(hipStreamWaitEvent(s, b->ev_qchain, 0));  // (it reads the phases stepped in place below)
+    xl_q15_ahead_drop(b);
+    XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, ncl, b->d_qphase[b->qcur], b->d_qphtab[b->qtab], c.pos, s));
+  } else {
+    qphtab = b->d_qphtab[b->qtab ^ 1];
+    const bool hit = xl_q15_ahead_serves(b->qa_pending, b->qa_pos, c.pos) != 0;
+    // (a look-ahead of another shape writes the very buffers the tabulation below writes)
+    if (b->qa_pending) XL_TRY(hipStreamWaitEvent(s, b->ev_qchain, 0));
+    if (hit) {
+      b->qa_used++;
+      b->qa_pending = false;
+    } else {
+      xl_q15_ahead_drop(b);
+      XL_TRY(xl_launch_nco_q15_ahead(b->d_nco, b->d_qinc, ncl, b->d_qphase[b->qcur], b->d_qphase[b->qcur ^ 1], b->d_qphtab[b->qtab ^ 1],
+                                     c.pos, b->nco_prio, s));
+    }
+    XL_TRY(hipEventRecord(b->ev_qready, s));
+  }
   if (matrix && !b->qmm.tiles.empty() && c.maxK > 0) {
     XlQmmArgs m;
     memset(&m, 0, sizeof(m));
@@ -1391,7 +1472,7 @@ XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
     m.tiles = b->d_qmm_tiles, m.ntiles = (uint32_t)b->qmm.tiles.size();
     for (const XlQmmTile &t : b->qmm.tiles)
       m.xtiles = std::max(m.xtiles, (xl_grid_dyn(t.D, t.T, t.rem0, t.hv0, c.pos).K + XL_QMM_WAVES * t.nc - 1u) / (XL_QMM_WAVES * t.nc));
-    m.image = b->d_qmm_image, m.qphtab = b->d_qphtab, m.out = b->d_out[c.p];
+    m.image = b->d_qmm_image, m.qphtab = qphtab, m.out = b->d_out[c.p];
     if (m.xtiles > 0) {
       xl_call_roll_args(b, c, m);
       XL_TRY(xl_launch_q15_mm(m, b->qmm.lds, s));
@@ -1403,14 +1484,27 @@ XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
     XlFirArgs a;
     xl_call_fir_args(b, c, L, a);
     if (!c.rolled) xl_call_roll_args(b, c, a);
-    XL_TRY(xl_launch_fir_q15_batch(L.ct, L.nw, a, b->d_qtaps, b->d_qphtab, L.lds, s));
+    XL_TRY(xl_launch_fir_q15_batch(L.ct, L.nw, a, b->d_qtaps, qphtab, L.lds, s));
   }
   if (!c.rolled) XL_TRY(xl_launch_update_history(b->d_hist[c.hb], c.d_blocks, XL_HCAP, c.N, b->bps, b->d_hist[c.hn], s));
-  if (c.maxKw > 0) XL_TRY(xl_batch_wide_launch(b, c, nullptr));
+  if (c.maxKw > 0) XL_TRY(xl_batch_wide_launch(b, c, nullptr, qphtab));
   if (b->d_whist[0]) XL_TRY(xl_launch_update_history(b->d_whist[c.hb], c.d_blocks, b->max_window, c.N, b->bps, b->d_whist[c.hn], s));
   if (c.record_ev) XL_TRY(hipEventRecord(c.record_ev, s));
   xl_call_commit(b, c);
   b->last_q15 = true;
+  if (ahead) {
+    b->qcur ^= 1, b->qtab ^= 1;
+    if (xl_q15_ahead_may_launch(c.pos, b->planned_immature, ncl)) {
+      const XlPos next = xl_grid_next(c.pos);
+      b->poisoned = true;  // (a failed look-ahead launch leaves the spare buffers and the side stream in an unknown state)
+      XL_TRY(hipStreamWaitEvent(b->nco_stream, b->ev_qready, 0));
+      XL_TRY(xl_launch_nco_q15_ahead(b->d_nco, b->d_qinc, ncl, b->d_qphase[b->qcur], b->d_qphase[b->qcur ^ 1], b->d_qphtab[b->qtab ^ 1],
+                                     next, b->nco_prio, b->nco_stream));
+      XL_TRY(hipEventRecord(b->ev_qchain, b->nco_stream));
+      b->poisoned = false;
+      b->qa_pending = true, b->qa_pos = next;
+    }
+  }
   return 0;
 fail:
   return 1;
@@ -1809,6 +1903,8 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
            std::to_string(b->qmm.fb_window) + ")";
     }
   }
+  if (b->q15_nco == 1u)
+    d += " | q15 nco: ahead, " + std::to_string(b->qa_used) + " used, " + std::to_string(b->qa_dropped) + " dropped";
   if (b->reserve_r) d += " | side kernel: " + std::to_string(8u * b->reserve_r) + " CUs reserved";
   if (pending) d += " | re-plan pending (client set or options changed: the next process call plans again)";
   const size_t len = std::min(d.size(), n - 1);
@@ -1874,7 +1970,10 @@ extern "C" size_t xlating_batch_output_len_block(const xlating_batch *b, int id,
 extern "C" int xlating_batch_sync(xlating_batch *b) {
   if (b == nullptr) return -EINVAL;
   if (hipSetDevice(b->device) != hipSuccess) return -EIO;
-  return hipStreamSynchronize(b->last_stream) == hipSuccess ? 0 : -EIO;
+  if (hipStreamSynchronize(b->last_stream) != hipSuccess) return -EIO;
+  // (a Q15 phase table being tabulated a call ahead, option "q15_nco": enqueued work of the engine like the call's own)
+  if (b->qa_pending && hipStreamSynchronize(b->nco_stream) != hipSuccess) return -EIO;
+  return 0;
 }
 
 extern "C" int xlating_batch_query(xlating_batch *b) {
@@ -1977,6 +2076,20 @@ extern "C" int xlating_batch_client_phase(xlating_batch *b, int id, float *re, f
   // the committed ones (after the latest processed call) are d_phase[pcur]
   float2 ph;
   if (hipMemcpy(&ph, b->d_phase[b->pcur] + id, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+  *re = ph.x;
+  *im = ph.y;
+  return 0;
+}
+
+extern "C" int xlating_batch_client_phase_q15(xlating_batch *b, int id, int16_t *re, int16_t *im) {
+  if (b == nullptr || id < 0 || (size_t)id >= b->clients.size() || !b->clients[id].alive || b->fmt == XL_FMT_CF32 || re == nullptr ||
+      im == nullptr)
+    return -EINVAL;
+  if (hipSetDevice(b->device) != hipSuccess) return -EIO;
+  xl_batch_sync_all(b);
+  // (option "q15_nco": a pending look-ahead has already written the phases AFTER the next call into d_qphase[qcur ^ 1])
+  short2 ph;
+  if (hipMemcpy(&ph, b->d_qphase[b->qcur] + id, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
   *re = ph.x;
   *im = ph.y;
   return 0;

@@ -156,6 +156,10 @@ hipError_t xl_launch_fir_q15(const short2 *work, const short2 *taps, uint32_t T,
 //   qinc[i]: increment of clients[i] packed like XlTile::qincr; qstate[slot]: running Q15 phase (updated in place)
 hipError_t xl_launch_nco_q15_batch(const XlNcoClient *clients, const uint32_t *qinc, uint32_t nclients, short2 *qstate,
                                    short2 *qphtab, XlPos pos, hipStream_t s);
+// option "q15_nco": the same table from the packed five-instruction step, 16 steps unrolled per table entry; reads
+// state_src[slot], writes state_dst[slot] (different buffers), with the wave priority `prio` of the float NCO launch
+hipError_t xl_launch_nco_q15_ahead(const XlNcoClient *clients, const uint32_t *qinc, uint32_t nclients, const short2 *state_src,
+                                   short2 *state_dst, short2 *qphtab, XlPos pos, uint32_t prio, hipStream_t s);
 //   a: as for xl_launch_fir (no NCO role); qtaps: [tile][Tpad][ct] (re, im) doubles, same indexing as a.taps;
 //   outputs: short2 rows at the addresses of the float2 rows (a.out + out_off)
 hipError_t xl_launch_fir_q15_batch(int ct, int nw, const XlFirArgs &a, const double *qtaps, const short2 *qphtab,

@@ -12,6 +12,7 @@
 //   xl_move_down_kernel      history memmove                                            (xlating.c:76-79)
 //   xl_update_history_kernel raw history roll of the batch engine
 //   xl_fir_q15_kernel / xl_nco_table_q15_kernel   the Q15 family                        (xlating.c:92-140)
+//   xl_nco_q15_batch_kernel / xl_nco_q15_ahead_kernel   its phase table in the batch engine: in front of the call / a call ahead
 //
 // Work decomposition of xl_fir_kernel (the hot kernel):
 //   lane      = one output sample m (64 consecutive outputs per wave)           -> no cross-lane reduction
@@ -984,6 +985,48 @@ hipError_t xl_launch_nco_q15_batch(const XlNcoClient *clients, const uint32_t *q
   if (nclients == 0) return hipSuccess;
   hipLaunchKernelGGL(xl_nco_q15_batch_kernel, dim3((nclients + 63u) / 64u), dim3(64), 0, s, clients, qinc, nclients, qstate,
                      qphtab, pos);
+  return hipGetLastError();
+}
+
+// Option "q15_nco": the same tabulation with the single filter's five-instruction step (xl_q15_step: two v_dot2_i32_i16, two shifts,
+// one v_cvt_pk_i16_i32), in stretches of XL_PH_STRIDE outputs -- one 32-bit table store, then 16 steps unrolled -- and a tail loop.
+// Every phase is still the reference's own step applied to the one before it (the arithmetic truncates: no jumping ahead).  The
+// running phases go state_src -> state_dst (never back into state_src), so the launch may run on the side stream a call ahead of
+// the launches that read the committed phases' table (xl_batch.cpp, xl_call_q15).  -ii fits an int16: the increment components are
+// (int16)(c * 32767), |c| <= 1 (xlating.c:548-549), never -32768 (tests/test_q15_nco_cpu.py).
+__global__ __launch_bounds__(64) void xl_nco_q15_ahead_kernel(const XlNcoClient *__restrict__ cl, const uint32_t *__restrict__ qinc,
+                                                              uint32_t n, const short2 *__restrict__ state_src,
+                                                              short2 *__restrict__ state_dst, uint32_t *__restrict__ tab,
+                                                              const XlPos pos, const uint32_t prio) {
+  if (prio == 3) __builtin_amdgcn_s_setprio(3);
+  else if (prio == 2) __builtin_amdgcn_s_setprio(2);
+  else if (prio == 1) __builtin_amdgcn_s_setprio(1);
+  const uint32_t c = blockIdx.x * 64u + threadIdx.x;
+  if (c >= n) return;
+  const XlNcoClient k = cl[c];
+  const uint32_t K = xl_nco_bnd(k, pos, 0xFFFFFFFFu).K;
+  const uint32_t q = qinc[c];
+  const int32_t ir = (int16_t)(q & 0xFFFFu), ii = (int16_t)(q >> 16);
+  const uint32_t a = ((uint32_t)ir & 0xFFFFu) | ((uint32_t)(-ii) << 16), b = ((uint32_t)ii & 0xFFFFu) | ((uint32_t)ir << 16);
+  const short2 p0 = state_src[k.slot];
+  uint32_t p = ((uint32_t)(uint16_t)p0.x) | ((uint32_t)(uint16_t)p0.y << 16);
+  uint32_t *__restrict__ o = tab + (k.out_off >> XL_PH_SHIFT);
+  uint32_t m = 0;
+  for (; m + XL_PH_STRIDE <= K; m += XL_PH_STRIDE) {
+    o[m >> XL_PH_SHIFT] = p;
+#pragma unroll
+    for (uint32_t i = 0; i < XL_PH_STRIDE; ++i) p = xl_q15_step(p, a, b);
+  }
+  if (m < K) o[m >> XL_PH_SHIFT] = p;
+  for (; m < K; ++m) p = xl_q15_step(p, a, b);
+  state_dst[k.slot] = make_short2((short)(p & 0xFFFFu), (short)(p >> 16));
+}
+
+hipError_t xl_launch_nco_q15_ahead(const XlNcoClient *clients, const uint32_t *qinc, uint32_t nclients, const short2 *state_src,
+                                   short2 *state_dst, short2 *qphtab, XlPos pos, uint32_t prio, hipStream_t s) {
+  if (nclients == 0) return hipSuccess;
+  hipLaunchKernelGGL(xl_nco_q15_ahead_kernel, dim3((nclients + 63u) / 64u), dim3(64), 0, s, clients, qinc, nclients, state_src,
+                     state_dst, reinterpret_cast<uint32_t *>(qphtab), pos, prio);
   return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@ the device (its device plugins deliver blocks of `buffer_size` bytes: cu8 rtl-sd
 src/sdr/*_device.c, src/tcp_server.c:257-271).
 
   python tools/replay_iq.py capture.cu8 --format cu8 --band-rate 2016000 --band-freq 460100000 --out /tmp/out \\
-         --client 460112000:48000 --client 460050000:96000 [--gzip] [--variant optimized | native | q15 [--q15-kernel 1]]
+         --client 460112000:48000 --client 460050000:96000 [--gzip] [--variant optimized | native | q15 [--q15-kernel 1] [--q15-nco 1]]
 
 Every --client CENTER_HZ:RATE_HZ goes through the 15-byte wire request, the admission rules and
 xlating_wire_add_client, and ends up as <out>/<id>.cf32[.gz].  With --waterfall-width W every admitted client also gets a stream of a
@@ -48,12 +48,13 @@ def write_gray_png(path, pixels):
 
 
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
-           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0):
+           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0):
     """clients: [(center_hz, rate_hz)].  Returns {client_id: (center_hz, rate_hz)} of the admitted ones, the list of
     (center, rate, failure_details) of the rejected ones and the run's counters.  waterfall_width: also write <out>/<id>.png per
     admitted client whose output holds at least one row (rate samples).  any_rate: admit rates that do not divide the band rate through
     a resampler bank behind the engine.  variant "q15": the cs16 family throughout, <out>/<id>.cs16 written here, no gzip; q15_kernel:
-    the engine option of that name (1: the eligible clients' FIR on the matrix cores, the same bits)."""
+    the engine option of that name (1: the eligible clients' FIR on the matrix cores, the same bits); q15_nco: likewise (1: the Q15 phase
+    table tabulated a call ahead on the side stream, the same bits)."""
     q15 = variant == "q15"
     if q15 and gzip:
         raise ValueError("gzip is the sinks library's, which writes the cf32 family: not with variant q15")
@@ -63,6 +64,8 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
     eng = xl.BatchEngine(band_rate, fmt, buffer_size)
     if q15:
         eng.set_option("q15_kernel", q15_kernel)
+        if q15_nco:
+            eng.set_option("q15_nco", q15_nco)
     sinks = None if q15 else xl.Sinks(writer_threads=writer_threads, queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
     files, written = {}, 0  # q15: client id -> its open <id>.cs16, the bytes written to them
     admitted, rejected = {}, []
@@ -192,6 +195,8 @@ def parse_args(argv=None):
                     help="q15: the cs16 output family; every client's samples are written as <id>.cs16 (raw int16 pairs)")
     ap.add_argument("--q15-kernel", type=int, default=0, choices=[0, 1],
                     help="with --variant q15: engine option q15_kernel (1: the FIR of every eligible client on the matrix cores)")
+    ap.add_argument("--q15-nco", type=int, default=0, choices=[0, 1],
+                    help="with --variant q15: engine option q15_nco (1: the phase table of the next call tabulated on the side stream)")
     ap.add_argument("--gzip", action="store_true", help="gzip the .cf32 files (the sinks library's work: refused with --variant q15)")
     ap.add_argument("--waterfall-width", type=int, default=None, help="also write <id>.png: each client's waterfall, this many bins wide")
     ap.add_argument("--any-rate", action="store_true",
@@ -206,7 +211,7 @@ def main(argv=None):
     a = parse_args(argv)
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate,
-                          a.variant, a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel)
+                          a.variant, a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel, q15_nco=a.q15_nco)
     for cid, (c, r) in adm.items():
         print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{'cs16' if a.variant == 'q15' else 'cf32'}{'.gz' if a.gzip else ''}")
     for c, r, why in rej:
