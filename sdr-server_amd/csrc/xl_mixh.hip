@@ -38,7 +38,11 @@
 // stream has no a-priori bound: its segments are scaled by what the forward launch found, SEG below) and per column the one that
 // brings the bound of its branch spectra
 // under XLP_H_RMAX (xl_batch.cpp); the sums are multiplied by 1 / (both) before they are stored.  Halves in the subnormal
-// range only ever carry 2^-24 of the operand scale.
+// range only ever carry 2^-24 of the operand scale.  They must SURVIVE, though -- the casts of xlp_split_h, the LDS pack, the operand
+// image and the matrix instruction all keep them in the default denormal mode, and nothing but tests pins that: with the constant scale
+// a quiet integer stream (1-LSB cs16 samples: spectra x 128 near 2^-8, second halves 2^-19 .. 2^-24) has ALL its second halves there.
+// Flushed, such a stream misses the 1e-5 bar 7 to 29 times over; kept, it costs up to 4.9e-6 (5.9e-6 on the wide kernel), some 25 x the
+// float32 mix (tests/test_mix_split_model.py: the arithmetic; tests/test_quiet_levels_gpu.py: these kernels).
 //
 // Workgroup = 4 waves = (bin m, column group of 128 clients, a run of `pp` passes); wave w = the group's columns
 // 32 w .. 32 w + 31.  A wave keeps its B operands -- 2 terms x nkb k-blocks x 16 bytes per lane, read ONCE as whole 1 KB runs
