@@ -230,6 +230,9 @@ int xlating_batch_timing_polyphase(xlating_batch *batch, double ms_total[3], int
  * which arithmetic path the optimized mode takes for which class.  If the client set or an option changed and no call
  * has run since the last plan, the plan is built first; if calls HAVE run, their outputs must stay where they are until
  * the next process call, so the plan they ran with is described, followed by "| re-plan pending ...".
+ * Each polyphase class ends with "calls=N": the calls that took the class's polyphase launches so far.  An optimized call
+ * whose largest client has fewer than 512 outputs runs every client on the direct kernel and is not counted; the count is
+ * kept over re-plans that keep the class and starts at 0 for a class that is formed anew.
  * Returns the length written (excluding NUL). */
 int xlating_batch_describe(xlating_batch *batch, char *buf, size_t buf_len);
 

@@ -1761,6 +1761,7 @@ XL_STAGE int xl_call_poly_class(xlating_batch *b, XlCall &c, PolyClass &pc, bool
   }
   if (traced == 3) XL_TRY(xl_ptrace(b, pa, s, false));
   if (pe[3]) XL_TRY(hipEventRecord(pe[3], s));
+  ++pc.calls;
   return 0;
 fail:
   return 1;
@@ -1878,6 +1879,7 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
                                : (pc.last_inv >= 0 ? pc.last_inv : (int)xlp_inverse_pick(pc.M, 0u, ((kq_full + pc.V - 1u) / pc.V) * pc.ncg * 4u));
       d += k == 6 ? " inv=cut32" : (k == 5 ? " inv=lanes8" : (k == 3 ? " inv=lds" : " inv=auto"));
     }
+    d += " calls=" + std::to_string(pc.calls);  // (calls that took the class's polyphase launches, not the direct fall-back)
   }
   if (!b->poly.empty()) {
     d += " | optimized-mode direct:";

@@ -105,6 +105,8 @@ struct PolyClass {
   float2 *d_Y = nullptr;     // mixed spectra  [cg][nseg_cap][sub][bin M][CW columns] (xl_y_layout.h)
   XlpCol *d_cols = nullptr;  // per column: output row, grid offset, NCO increment
   int last_inv = -1;         // which inverse kernel the class's latest launch took (describe; xlp_inverse_pick): 3 / 5 / 6, -1 = none yet
+  uint64_t calls = 0;        // calls that enqueued the class's three launches (describe: "calls=N"); a call that falls back to the direct
+                             // kernel does not count.  Carried over re-plans that keep the class, 0 for a class formed anew
 };
 
 // ---- output rows: free extents (offset -> length) below rows_end
