@@ -2,6 +2,7 @@
 #ifndef XL_COMMON_H_
 #define XL_COMMON_H_
 
+#include <errno.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -27,6 +28,18 @@ int xl_errno_of_last_hip_error(void);
       XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__); \
       goto fail;                                                                           \
     }                                                                                      \
+  } while (0)
+
+// XL_TRY for a function without a `fail:` label that returns an errno: records and logs the same way, then returns -ENOMEM for an
+// allocation failure and -EIO for anything else.  expr: a hipError_t, or the int a launch wrapper returns (0 or a hipError_t).
+#define XL_TRY_RET(expr)                                                                        \
+  do {                                                                                          \
+    hipError_t xl_e_ = (hipError_t)(expr);                                                      \
+    if (xl_e_ != hipSuccess) {                                                                  \
+      xl_last_hip_error = xl_e_;                                                                \
+      XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__); \
+      return xl_e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                                     \
+    }                                                                                           \
   } while (0)
 
 // journald "warning" line

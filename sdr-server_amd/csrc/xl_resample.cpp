@@ -9,8 +9,8 @@
 // that grows as streams are added; per distinct (L, M, taps) one phase-major tap table, reference-counted; one output arena, carved per
 // feed from the host-computed output counts, which holds the latest feed's outputs and grows (after a wait) when a feed needs more.
 // One feed = one table of runs written into pinned memory and uploaded by one copy, the ragged resampling launch, the carry launch.
-// The pinned tables are multi-buffered behind events, so a feed does not wait for the previous one; every feed is ordered behind the
-// previous feed's work by an event, so the single device table, the carries and the arena need no copies of their own.
+// The ring of pinned tables, the single device table and the growth of the carry array, with the rules of their lifetimes, are
+// xl_bank_host.h's (shared with the spectrum bank); a feed does not wait for the previous one.
 #include "../../include/xlating_resample.h"
 #include "../../include/xlating_resample_q15.h"
 
@@ -22,25 +22,15 @@
 #include <new>
 #include <vector>
 
+#include "xl_bank_host.h"
 #include "xl_common.h"
 #include "xl_resample.h"
 #include "xl_resample_cut.h"
 #include "xl_resample_q15.h"
 #include "xl_resample_q15_quant.h"
 
-#define XL_RS_TABLES 4
 #define XL_RS_MAX_STREAMS 65536
 #define XL_RS_COUNT_MAX ((size_t)1 << 30)
-
-#define XL_RS_TRY(expr)                                                                         \
-  do {                                                                                          \
-    hipError_t xl_e_ = (hipError_t)(expr);                                                      \
-    if (xl_e_ != hipSuccess) {                                                                  \
-      xl_last_hip_error = xl_e_;                                                                \
-      XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__); \
-      return xl_e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                                     \
-    }                                                                                           \
-  } while (0)
 
 namespace {
 
@@ -62,13 +52,6 @@ struct XlRsStream {
   size_t out_off = 0, out_n = 0;
 };
 
-struct XlRsPinned {
-  void *h = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-
 }  // namespace
 
 struct xlating_resample_bank {
@@ -80,16 +63,13 @@ struct xlating_resample_bank {
   uint32_t exp_flags = 0;       // Q15, measurement knob XL_EXP_RSQ: run flags forced on every run (XL_RSQ_WIDE, XL_RSQ_TAPS_IN_PLACE)
   bool fed = false, broken = false;
   uint32_t cap_streams = 0;
-  char *d_carry = nullptr;  // [cap_streams][XL_RS_CARRY_SLOT] samples
+  void *d_carry = nullptr;  // [cap_streams][XL_RS_CARRY_SLOT] samples
   std::vector<XlRsStream> streams;
   std::vector<int> free_ids;
   unsigned nlive = 0;
   std::vector<XlRsTaps *> tables;
   uint64_t feed_no = 0;
-  XlRsPinned tab[XL_RS_TABLES];
-  int tab_i = 0;
-  void *d_tab = nullptr;
-  size_t d_tab_cap = 0;
+  XlTableRing ring;  // the feeds' tables of runs
   char *d_out = nullptr;  // the arena (samples)
   size_t out_cap = 0, out_used = 0;
   uint64_t out_no = 0;      // generation: the feed whose outputs the arena holds
@@ -141,24 +121,9 @@ static uint32_t xl_rs_gcd(uint32_t a, uint32_t c) {
 // carry slots for `need` streams: the array is replaced by a larger one and the present streams' carries move over
 static int xl_rs_reserve_streams(xlating_resample_bank *b, uint32_t need) {
   if (need <= b->cap_streams) return 0;
-  uint32_t cap = b->cap_streams ? b->cap_streams * 2u : 64u;
-  while (cap < need) cap *= 2u;
-  const size_t slot = (size_t)XL_RS_CARRY_SLOT * b->esz;
-  if (b->fed) XL_RS_TRY(hipEventSynchronize(b->last));
-  char *carry = nullptr;
-  hipError_t e = hipMalloc(&carry, slot * cap);
-  if (e == hipSuccess) e = hipMemsetAsync(carry, 0, slot * cap, b->own);
-  if (e == hipSuccess && b->cap_streams > 0) e = hipMemcpyAsync(carry, b->d_carry, slot * b->cap_streams, hipMemcpyDeviceToDevice, b->own);
-  if (e == hipSuccess) e = hipStreamSynchronize(b->own);
-  if (e != hipSuccess) {
-    xl_last_hip_error = e;
-    XL_LOG_ERR("resampler bank: carries of %u streams: %s", cap, hipGetErrorString(e));
-    if (carry) (void)hipFree(carry);
-    return e == hipErrorOutOfMemory ? -ENOMEM : -EIO;
-  }
-  if (b->d_carry) (void)hipFree(b->d_carry);
-  b->d_carry = carry, b->cap_streams = cap;
-  return 0;
+  if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
+  const XlStreamArray a[] = {{&b->d_carry, (size_t)XL_RS_CARRY_SLOT * b->esz, true}};
+  return xl_streams_grow(&b->cap_streams, need, a, b->own, "resampler bank: carries");
 }
 
 // [p][q] = v[p + q L], zero beyond len; `pad` more zero elements behind it
@@ -220,22 +185,6 @@ static void xl_rs_taps_release(xlating_resample_bank *b, XlRsTaps *t) {
   delete t;
 }
 
-// a pinned table of at least `bytes`, free for writing
-static int xl_rs_pinned(xlating_resample_bank *b, size_t bytes, XlRsPinned **out) {
-  XlRsPinned &t = b->tab[b->tab_i];
-  b->tab_i = (b->tab_i + 1) % XL_RS_TABLES;
-  if (t.used) XL_RS_TRY(hipEventSynchronize(t.ev));
-  if (t.cap < bytes) {
-    if (t.h) (void)hipHostFree(t.h);
-    t.h = nullptr, t.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1u << 16);
-    XL_RS_TRY(hipHostMalloc(&t.h, cap, hipHostMallocDefault));
-    t.cap = cap;
-  }
-  *out = &t;
-  return 0;
-}
-
 template <class K>
 static int xl_rs_feed(xlating_resample_bank *b, size_t n, const int *ids, const void *const *dev_samples, const size_t *counts,
                       hipStream_t st) {
@@ -262,9 +211,9 @@ static int xl_rs_feed(xlating_resample_bank *b, size_t n, const int *ids, const 
     nruns += counts[i] > 0, any_carry |= counts[i] > 0 && s.t->Q > 1u;
   }
   if (wgs >= ((uint64_t)1 << 31)) return -ENOMEM;  // (the ragged launch counts its workgroups in 32 bits)
-  XL_RS_TRY(hipSetDevice(b->device));
+  XL_TRY_RET(hipSetDevice(b->device));
   if (need > b->out_cap) {  // the arena grows, once the feeds that write and the callers that read the present one are through
-    if (b->fed) XL_RS_TRY(hipEventSynchronize(b->last));
+    if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
     if (b->d_out) (void)hipFree(b->d_out);
     b->d_out = nullptr, b->out_cap = 0, b->out_used = 0, b->out_no = 0;
     const size_t cap = std::max<size_t>(need + need / 2, 1024);
@@ -278,22 +227,19 @@ static int xl_rs_feed(xlating_resample_bank *b, size_t n, const int *ids, const 
   }
   // the table of runs: written in pinned memory, one run per stream that consumes anything
   const size_t bytes = nruns * sizeof(Run);
-  XlRsPinned *t = nullptr;
+  XlRingTable *t = nullptr;
   if (nruns > 0) {
-    const int rc = xl_rs_pinned(b, bytes, &t);
-    if (rc != 0) return rc;  // (-ENOMEM: nothing consumed)
-    if (b->d_tab_cap < bytes) {
-      if (b->fed) XL_RS_TRY(hipEventSynchronize(b->last));  // (the previous feed reads the table that is replaced)
-      if (b->d_tab) (void)hipFree(b->d_tab);
-      b->d_tab = nullptr, b->d_tab_cap = 0;
-      if (hipMalloc(&b->d_tab, bytes * 2) != hipSuccess) return -EIO;
-      b->d_tab_cap = bytes * 2;
+    XL_TRY_RET(xl_ring_acquire(&b->ring, bytes, &t));  // (-ENOMEM: nothing consumed)
+    if (b->ring.d_cap < bytes) {
+      if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));  // (the previous feed reads the table that is replaced)
+      // (an oddity kept as it is: -EIO whatever the error, the bank broken, and xl_last_hip_error not set)
+      if (xl_ring_dev_grow(&b->ring, bytes) != hipSuccess) return -EIO;
     }
   }
   b->launches = b->copies = 0;
   b->out_no = b->feed_no, b->out_used = need;
   Run *runs = nruns > 0 ? static_cast<Run *>(t->h) : nullptr;
-  Sample *const d_out = reinterpret_cast<Sample *>(b->d_out), *const d_carry = reinterpret_cast<Sample *>(b->d_carry);
+  Sample *const d_out = reinterpret_cast<Sample *>(b->d_out), *const d_carry = static_cast<Sample *>(b->d_carry);
   uint32_t W = 0;
   size_t off = 0, k = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -315,21 +261,19 @@ static int xl_rs_feed(xlating_resample_bank *b, size_t n, const int *ids, const 
     s.P += counts[i];
   }
   if (nruns == 0) return 0;
-  if (b->fed) XL_RS_TRY(hipStreamWaitEvent(st, b->last, 0));
-  XL_RS_TRY(hipMemcpyAsync(b->d_tab, t->h, bytes, hipMemcpyHostToDevice, st));
-  XL_RS_TRY(hipEventRecord(t->ev, st));
-  t->used = true;
+  if (b->fed) XL_TRY_RET(hipStreamWaitEvent(st, b->last, 0));
+  XL_TRY_RET(xl_ring_upload(&b->ring, t, bytes, st));
   b->copies += 1;
-  const Run *d_runs = static_cast<const Run *>(b->d_tab);
+  const Run *d_runs = static_cast<const Run *>(b->ring.d_tab);
   if (W > 0) {
-    XL_RS_TRY(K::launch(d_runs, (uint32_t)nruns, W, st));
+    XL_TRY_RET(K::launch(d_runs, (uint32_t)nruns, W, st));
     b->launches += 1;
   }
   if (any_carry) {
-    XL_RS_TRY(K::carry(d_runs, (uint32_t)nruns, st));
+    XL_TRY_RET(K::carry(d_runs, (uint32_t)nruns, st));
     b->launches += 1;
   }
-  XL_RS_TRY(hipEventRecord(b->last, st));
+  XL_TRY_RET(hipEventRecord(b->last, st));
   b->fed = true;
   return 0;
 }
@@ -354,7 +298,7 @@ static int xl_rs_create(bool q15, const char *who, xlating_resample_bank **out) 
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->last, hipEventDisableTiming);
-  for (int i = 0; i < XL_RS_TABLES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->tab[i].ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = xl_ring_init(&b->ring);
   if (e != hipSuccess) {
     xl_last_hip_error = e;
     XL_LOG_ERR("%s: %s", who, hipGetErrorString(e));
@@ -373,7 +317,7 @@ static int xl_rs_add(xlating_resample_bank *b, uint32_t L, uint32_t M, const flo
     const bool reuse = !b->free_ids.empty();
     const size_t id = reuse ? (size_t)b->free_ids.back() : b->streams.size();
     if (id >= XL_RS_MAX_STREAMS) return -ENOMEM;
-    XL_RS_TRY(hipSetDevice(b->device));
+    XL_TRY_RET(hipSetDevice(b->device));
     int rc = xl_rs_reserve_streams(b, (uint32_t)id + 1u);
     if (rc != 0) return rc;
     XlRsTaps *t = nullptr;
@@ -395,12 +339,12 @@ static int xl_rs_add(xlating_resample_bank *b, uint32_t L, uint32_t M, const flo
 static int xl_rs_remove(xlating_resample_bank *b, bool q15, int stream_id) {
   if (!xl_rs_live(b, q15, stream_id)) return -EINVAL;
   XlRsStream &s = b->streams[(size_t)stream_id];
-  if (!b->broken) XL_RS_TRY(hipSetDevice(b->device));
+  if (!b->broken) XL_TRY_RET(hipSetDevice(b->device));
   if (s.P > 0 && !b->broken) {  // the id's next use starts from zero history
     const size_t slot = (size_t)XL_RS_CARRY_SLOT * b->esz;
-    if (b->fed) XL_RS_TRY(hipEventSynchronize(b->last));
-    XL_RS_TRY(hipMemsetAsync(b->d_carry + (size_t)stream_id * slot, 0, slot, b->own));
-    XL_RS_TRY(hipStreamSynchronize(b->own));
+    if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
+    XL_TRY_RET(hipMemsetAsync(static_cast<char *>(b->d_carry) + (size_t)stream_id * slot, 0, slot, b->own));
+    XL_TRY_RET(hipStreamSynchronize(b->own));
   }  // (a stream that consumed nothing was in no launch: its table, if it is the last user, is read by nothing)
   xl_rs_taps_release(b, s.t);
   s.live = false, s.t = nullptr, s.out_n = 0;
@@ -440,18 +384,18 @@ static int xl_rs_output_device(xlating_resample_bank *b, bool q15, int stream_id
 static int xl_rs_fetch(xlating_resample_bank *b, bool q15) {
   if (!xl_rs_is(b, q15)) return -EINVAL;
   if (b->broken) return -EIO;
-  XL_RS_TRY(hipSetDevice(b->device));
-  if (b->fed) XL_RS_TRY(hipEventSynchronize(b->last));
+  XL_TRY_RET(hipSetDevice(b->device));
+  if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
   if (b->out_used > b->h_cap) {
     if (b->h_out) (void)hipHostFree(b->h_out);
     b->h_out = nullptr, b->h_cap = 0;
     const size_t cap = std::max<size_t>(b->out_used + b->out_used / 2, 1u << 16);
-    XL_RS_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_out), cap * b->esz, hipHostMallocDefault));
+    XL_TRY_RET(hipHostMalloc(reinterpret_cast<void **>(&b->h_out), cap * b->esz, hipHostMallocDefault));
     b->h_cap = cap;
   }
   if (b->out_used > 0) {
-    XL_RS_TRY(hipMemcpyAsync(b->h_out, b->d_out, b->out_used * b->esz, hipMemcpyDeviceToHost, b->own));
-    XL_RS_TRY(hipStreamSynchronize(b->own));
+    XL_TRY_RET(hipMemcpyAsync(b->h_out, b->d_out, b->out_used * b->esz, hipMemcpyDeviceToHost, b->own));
+    XL_TRY_RET(hipStreamSynchronize(b->own));
   }
   b->h_no = b->out_no;
   return 0;
@@ -498,11 +442,7 @@ static void xl_rs_destroy(xlating_resample_bank *b) {
     if (t->d) (void)hipFree(t->d);
     delete t;
   }
-  for (XlRsPinned &t : b->tab) {
-    if (t.h) (void)hipHostFree(t.h);
-    if (t.ev) (void)hipEventDestroy(t.ev);
-  }
-  if (b->d_tab) (void)hipFree(b->d_tab);
+  xl_ring_destroy(&b->ring);
   if (b->d_out) (void)hipFree(b->d_out);
   if (b->h_out) (void)hipHostFree(b->h_out);
   if (b->d_carry) (void)hipFree(b->d_carry);

@@ -3,7 +3,7 @@
 //
 // The scheme is xl_resample.hip's: the host writes one run per stream (XlRsQ15Run) with the running sum of workgroups; a workgroup
 // finds its run by binary search and computes a tile of XL_RS_TILE consecutive outputs of that ONE stream, one output per thread, at
-// t = p0 + k * M on the grid of the input upsampled by L (32-bit arithmetic inside the tile, one 64-bit division for the tile).
+// t = p0 + k * M on the grid of the input upsampled by L (xl_resample_dev.h: xl_rs_tile, and the carry launch's body, are shared).
 // A tile's outputs read the inputs n_first - (Q - 1) .. n_last.  When that window fits XL_RSQ_LDS_SPAN it is staged in LDS once -- the
 // part below the feed's first sample from the stream's carry -- one 32-bit word per sample (re low, im high); a wider window (a
 // decimating stream of large M / L) is read in place.
@@ -17,6 +17,7 @@
 // 24 KiB of LDS per workgroup: six workgroups per CU.
 // INTEGER VALU ONLY, no matrix instructions and no packed FP32 (Makefile: RESAMPLE_Q15_FLAGS): these launches run behind and beside
 // the engine's matrix-core launches.
+#include "xl_resample_dev.h"
 #include "xl_resample_q15.h"
 
 namespace {
@@ -49,89 +50,52 @@ __device__ __forceinline__ xl_cs16 xl_rsq_out(const bool wide, const uint32_t Q,
 __global__ void __launch_bounds__(XL_RS_TILE) xl_rsq_kernel(const XlRsQ15Run *__restrict__ runs, const uint32_t nruns) {
   __shared__ xl_cs16 win[XL_RSQ_LDS_SPAN];
   __shared__ uint32_t tapw[XL_RSQ_LDS_TAPS / 2u];
-  const uint32_t w = blockIdx.x, tid = threadIdx.x;
-  uint32_t lo = 0u, hi = nruns;  // the last run with wsum <= w (runs[0].wsum == 0; a run without outputs shares its successor's wsum)
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) / 2u;
-    if (runs[mid].wsum <= w) lo = mid; else hi = mid;
-  }
-  const XlRsQ15Run r = runs[lo];
-  const uint32_t k0 = (w - r.wsum) * XL_RS_TILE;  // the tile's first output; < nout < 2^31
-  if (k0 >= r.nout) return;                       // (never: the host counts the workgroups from nout)
-  const uint32_t nv = min(XL_RS_TILE, r.nout - k0);
-  const uint32_t K = r.Q - 1u;
-  // the tile's first output: input nt (relative to src, 0 <= nt < cnt), phase pt
-  const uint64_t t0 = (uint64_t)r.p0 + (uint64_t)k0 * r.M;
-  const int32_t nt = r.n0 + (int32_t)(t0 / r.L);
-  const uint32_t pt = (uint32_t)(t0 % r.L);
-  const uint32_t Mq = r.M / r.L, Mr = r.M % r.L;
-  // this thread's output: input nt + dn, phase p (dn wraps harmlessly in a thread past the tile's outputs, which computes nothing)
-  const uint32_t u = pt + tid * Mr;
-  const uint32_t dn = tid * Mq + u / r.L;
-  const uint32_t p = u % r.L;
-  // the window: inputs nt - K .. nt + dn of the tile's last output
-  const uint32_t ul = pt + (nv - 1u) * Mr;
-  const uint64_t span = (uint64_t)(nv - 1u) * Mq + ul / r.L + r.Q;
+  const uint32_t tid = threadIdx.x;
+  XlRsQ15Run r;
+  XlRsTile t;
+  if (!xl_rs_tile(runs, nruns, r, t)) return;
+  const uint32_t K = t.K;
   const bool wide = (r.flags & XL_RSQ_WIDE) != 0u;
   const uint32_t ntaps = r.L * r.Q;  // <= 4096 * 1024
   const bool taps_lds = ntaps <= XL_RSQ_LDS_TAPS && (r.flags & XL_RSQ_TAPS_IN_PLACE) == 0u;
-  const bool win_lds = span <= XL_RSQ_LDS_SPAN;
+  const bool win_lds = t.span <= XL_RSQ_LDS_SPAN;
   // (all three are the same in every thread of the workgroup: the barrier below is met by all or by none)
   if (taps_lds) {
     const uint32_t *__restrict__ tw = reinterpret_cast<const uint32_t *>(r.table);  // (padded to whole words by the host)
     for (uint32_t i = tid; i < (ntaps + 1u) / 2u; i += XL_RS_TILE) tapw[i] = tw[i];
   }
   if (win_lds) {
-    const int32_t first = nt - (int32_t)K;
-    for (uint32_t i = tid; i < (uint32_t)span; i += XL_RS_TILE) {
+    const int32_t first = t.nt - (int32_t)K;
+    for (uint32_t i = tid; i < (uint32_t)t.span; i += XL_RS_TILE) {
       const int32_t idx = first + (int32_t)i;
       win[i] = idx < 0 ? r.carry[(int32_t)K + idx] : r.src[idx];
     }
   }
   if (taps_lds || win_lds) __syncthreads();
-  if (tid >= nv) return;
-  const int16_t *taps = reinterpret_cast<const int16_t *>(tapw) + p * r.Q;
-  const int16_t *__restrict__ tapg = r.table + (size_t)p * r.Q;
+  if (tid >= t.nv) return;
+  const int16_t *taps = reinterpret_cast<const int16_t *>(tapw) + t.p * r.Q;
+  const int16_t *__restrict__ tapg = r.table + (size_t)t.p * r.Q;
   const auto h_lds = [&](const uint32_t q) -> int32_t { return taps[q]; };
   const auto h_mem = [&](const uint32_t q) -> int32_t { return tapg[q]; };
   xl_cs16 y;
   if (win_lds) {
-    const uint32_t base = dn + K;
+    const uint32_t base = t.dn + K;
     const auto x = [&](const uint32_t q) -> xl_cs16 { return win[base - q]; };
     y = taps_lds ? xl_rsq_out(wide, r.Q, h_lds, x) : xl_rsq_out(wide, r.Q, h_mem, x);
   } else {
-    const int32_t n = nt + (int32_t)dn;
+    const int32_t n = t.nt + (int32_t)t.dn;
     const auto x = [&](const uint32_t q) -> xl_cs16 {
       const int32_t idx = n - (int32_t)q;
       return idx < 0 ? r.carry[(int32_t)K + idx] : r.src[idx];
     };
     y = taps_lds ? xl_rsq_out(wide, r.Q, h_lds, x) : xl_rsq_out(wide, r.Q, h_mem, x);
   }
-  r.out[k0 + tid] = y;
+  r.out[t.k0 + tid] = y;
 }
 
-// one workgroup per stream of the feed: carry = concat(carry, src[0 .. cnt))[-(Q - 1):], as xl_rs_carry_kernel with 4-byte samples.
-// A feed shorter than the carry shifts it, and the move overlaps itself: every thread reads its (up to four) samples, the workgroup
-// meets, then they are written.
+// one workgroup per stream of the feed (xl_resample_dev.h), with 4-byte samples
 __global__ void __launch_bounds__(256) xl_rsq_carry_kernel(const XlRsQ15Run *__restrict__ runs) {
-  const XlRsQ15Run r = runs[blockIdx.x];
-  const uint32_t K = r.Q - 1u;
-  if (K == 0u || r.cnt == 0u) return;
-  xl_cs16 v[XL_RS_CARRY_SLOT / 256u];
-#pragma unroll
-  for (uint32_t j = 0u; j < XL_RS_CARRY_SLOT / 256u; ++j) {
-    const uint32_t i = threadIdx.x + j * 256u;
-    if (i < K) {
-      const uint64_t s = (uint64_t)i + r.cnt;  // position in concat(carry, src)
-      v[j] = s < K ? r.carry[s] : r.src[s - K];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (uint32_t j = 0u; j < XL_RS_CARRY_SLOT / 256u; ++j) {
-    const uint32_t i = threadIdx.x + j * 256u;
-    if (i < K) r.carry[i] = v[j];
-  }
+  xl_rs_carry_body<XlRsQ15Run, xl_cs16>(runs);
 }
 
 }  // namespace

@@ -93,8 +93,8 @@ static void xl_fft_double_tab(std::vector<std::complex<double>> &a, const std::v
 }
 
 static int xl_spec_upload(const std::vector<float2> &h, float2 **d) {
-  XL_SPEC_TRY(hipMalloc(d, sizeof(float2) * h.size()));
-  XL_SPEC_TRY(hipMemcpy(*d, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice));
+  XL_TRY_RET(hipMalloc(d, sizeof(float2) * h.size()));
+  XL_TRY_RET(hipMemcpy(*d, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -147,8 +147,8 @@ static int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, floa
     const double ang = -2.0 * M_PI * (double)m / (double)N;
     tw[m] = make_float2((float)cos(ang), (float)sin(ang));
   }
-  XL_SPEC_TRY(hipMalloc(d_tw, sizeof(float2) * N));
-  XL_SPEC_TRY(hipMemcpy(*d_tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+  XL_TRY_RET(hipMalloc(d_tw, sizeof(float2) * N));
+  XL_TRY_RET(hipMemcpy(*d_tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
   if (!blue) return 0;
   // chirp c[n] = exp(-i pi (n^2 mod 2W) / W); the filter b[m] = conj(c[|m|]) on -(W-1) .. W-1, wrapped into L
   std::vector<std::complex<double>> c(W), b(N, 0.0);
@@ -163,10 +163,10 @@ static int xl_spec_tables(uint32_t W, uint32_t N, bool blue, float2 **d_tw, floa
   std::vector<float2> ch(W), bs(N);
   for (uint32_t n = 0; n < W; ++n) ch[n] = make_float2((float)c[n].real(), (float)c[n].imag());
   for (uint32_t m = 0; m < N; ++m) bs[m] = make_float2((float)(b[m].real() / N), (float)(b[m].imag() / N));
-  XL_SPEC_TRY(hipMalloc(d_chirp, sizeof(float2) * W));
-  XL_SPEC_TRY(hipMemcpy(*d_chirp, ch.data(), sizeof(float2) * W, hipMemcpyHostToDevice));
-  XL_SPEC_TRY(hipMalloc(d_bspec, sizeof(float2) * N));
-  XL_SPEC_TRY(hipMemcpy(*d_bspec, bs.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
+  XL_TRY_RET(hipMalloc(d_chirp, sizeof(float2) * W));
+  XL_TRY_RET(hipMemcpy(*d_chirp, ch.data(), sizeof(float2) * W, hipMemcpyHostToDevice));
+  XL_TRY_RET(hipMalloc(d_bspec, sizeof(float2) * N));
+  XL_TRY_RET(hipMemcpy(*d_bspec, bs.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -266,8 +266,8 @@ static int xl_spec_reserve(xlating_spectrum *s, int64_t P1, hipStream_t st) {
   if (need > (int64_t)1 << 30) return -ENOMEM;
   uint32_t cap = s->cap * 2;
   while ((int64_t)cap < need) cap *= 2;
-  if (s->fed) XL_SPEC_TRY(hipEventSynchronize(s->last));
-  XL_SPEC_TRY(hipStreamSynchronize(st));  // (this feed's earlier spans: `last` is recorded at the end of a feed)
+  if (s->fed) XL_TRY_RET(hipEventSynchronize(s->last));
+  XL_TRY_RET(hipStreamSynchronize(st));  // (this feed's earlier spans: `last` is recorded at the end of a feed)
   return xl_spec_rows_alloc(s, cap);
 }
 
@@ -277,7 +277,7 @@ static int xl_spec_launch_t(xlating_spectrum *s, const void *in, int64_t base, i
   a.in = in, a.base = base, a.g0 = g0, a.T = (uint32_t)T, a.F = s->F, a.sr = s->sr, a.W = s->W, a.cap = s->cap;
   a.rowmax = s->d_max, a.tw = s->d_tw, a.chirp = s->d_chirp, a.bspec = s->d_bspec, a.norm = 1.0f / (float)s->W;
   if (!s->wide) {
-    XL_SPEC_TRY(xl_spec_launch(a, s->N, s->blue, s->fmt, st));
+    XL_TRY_RET(xl_spec_launch(a, s->N, s->blue, s->fmt, st));
     return 0;
   }
   // the two-level transform, as many transforms at a time as the scratch holds (stream order keeps one chunk's passes and the next
@@ -287,7 +287,7 @@ static int xl_spec_launch_t(xlating_spectrum *s, const void *in, int64_t base, i
   for (int64_t t = 0; t < T; t += s->scratch_T) {
     w.a = a;
     w.a.g0 = g0 + t, w.a.T = (uint32_t)std::min<int64_t>(s->scratch_T, T - t);
-    XL_SPEC_TRY(xl_specw_launch(w, s->blue, s->fmt, st));
+    XL_TRY_RET(xl_specw_launch(w, s->blue, s->fmt, st));
   }
   return 0;
 }
@@ -300,13 +300,13 @@ static int xl_spec_span(xlating_spectrum *s, const uint8_t *in, int64_t n, hipSt
   const XlSpecCut c = xl_spec_cut(s->sr, W, s->P, n);
   // the transform that straddles P: its first samples are in the carry
   if (c.carry_app > 0)
-    XL_SPEC_TRY(hipMemcpyAsync(s->d_carry + c.carry_have * ssz, in, (size_t)(c.carry_app * ssz), hipMemcpyDeviceToDevice, st));
+    XL_TRY_RET(hipMemcpyAsync(s->d_carry + c.carry_have * ssz, in, (size_t)(c.carry_app * ssz), hipMemcpyDeviceToDevice, st));
   if (c.carry_done && (rc = xl_spec_launch_t(s, s->d_carry, c.carry_t0, c.carry_g, 1, st)) != 0) return rc;
   // the transforms wholly inside the span, in place
   if (c.T > 0 && (rc = xl_spec_launch_t(s, in, s->P, c.g_first, c.T, st)) != 0) return rc;
   // the transform that straddles P + n and starts inside the span: its start into the carry
   if (c.save_n > 0)
-    XL_SPEC_TRY(hipMemcpyAsync(s->d_carry, in + c.save_off * ssz, (size_t)(c.save_n * ssz), hipMemcpyDeviceToDevice, st));
+    XL_TRY_RET(hipMemcpyAsync(s->d_carry, in + c.save_off * ssz, (size_t)(c.save_n * ssz), hipMemcpyDeviceToDevice, st));
   s->P += n;
   // rows whose F-th transform is in: finish, and copy to the host ring
   const int64_t done = c.rows_done;
@@ -314,12 +314,12 @@ static int xl_spec_span(xlating_spectrum *s, const uint8_t *in, int64_t n, hipSt
     const int64_t slot = r % s->cap;
     const int64_t nr = std::min<int64_t>({done - r, (int64_t)s->cap - slot, 65535});
     if (s->wide)
-      XL_SPEC_TRY(xl_specw_finish(s->d_max, s->d_db, s->d_px, s->W, s->N1, s->N2, !s->blue, s->cap, r, (uint32_t)nr, st));
+      XL_TRY_RET(xl_specw_finish(s->d_max, s->d_db, s->d_px, s->W, s->N1, s->N2, !s->blue, s->cap, r, (uint32_t)nr, st));
     else
-      XL_SPEC_TRY(xl_spec_finish(s->d_max, s->d_db, s->d_px, s->W, s->cap, r, (uint32_t)nr, st));
+      XL_TRY_RET(xl_spec_finish(s->d_max, s->d_db, s->d_px, s->W, s->cap, r, (uint32_t)nr, st));
     const size_t o = (size_t)slot * W;
-    XL_SPEC_TRY(hipMemcpyAsync(s->h_db + o, s->d_db + o, sizeof(float) * W * nr, hipMemcpyDeviceToHost, st));
-    XL_SPEC_TRY(hipMemcpyAsync(s->h_px + o, s->d_px + o, (size_t)(W * nr), hipMemcpyDeviceToHost, st));
+    XL_TRY_RET(hipMemcpyAsync(s->h_db + o, s->d_db + o, sizeof(float) * W * nr, hipMemcpyDeviceToHost, st));
+    XL_TRY_RET(hipMemcpyAsync(s->h_px + o, s->d_px + o, (size_t)(W * nr), hipMemcpyDeviceToHost, st));
     r += nr;
   }
   s->rows_finished = std::max(s->rows_finished, done);
@@ -328,8 +328,8 @@ static int xl_spec_span(xlating_spectrum *s, const uint8_t *in, int64_t n, hipSt
 
 static int xl_spec_begin(xlating_spectrum *s, hipStream_t st) {
   if (s->broken) return -EIO;
-  XL_SPEC_TRY(hipSetDevice(s->device));
-  if (s->fed) XL_SPEC_TRY(hipStreamWaitEvent(st, s->last, 0));
+  XL_TRY_RET(hipSetDevice(s->device));
+  if (s->fed) XL_TRY_RET(hipStreamWaitEvent(st, s->last, 0));
   return 0;
 }
 
@@ -338,7 +338,7 @@ static int xl_spec_end(xlating_spectrum *s, hipStream_t st, int rc) {
     s->broken = true;
     return rc;
   }
-  XL_SPEC_TRY(hipEventRecord(s->last, st));
+  XL_TRY_RET(hipEventRecord(s->last, st));
   s->fed = true;
   return 0;
 }
@@ -462,8 +462,8 @@ extern "C" int xlating_spectrum_take_rows(xlating_spectrum *s, float *db, uint8_
   if (s == nullptr) return -EINVAL;
   if (s->broken) return -EIO;
   if (s->fed) {
-    XL_SPEC_TRY(hipSetDevice(s->device));
-    XL_SPEC_TRY(hipEventSynchronize(s->last));
+    XL_TRY_RET(hipSetDevice(s->device));
+    XL_TRY_RET(hipEventSynchronize(s->last));
   }
   const int64_t n = std::min<int64_t>((int64_t)std::min<size_t>(max_rows, 1u << 30), s->rows_finished - s->rows_taken);
   const size_t W = s->W;

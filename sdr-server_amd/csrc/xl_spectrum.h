@@ -79,15 +79,4 @@ struct XlSpecSetup {
 int xl_spec_setup_init(XlSpecSetup *u, int width, int max_width, int format, const char *who);
 void xl_spec_setup_free(XlSpecSetup *u);
 
-// (needs xl_common.h at the place of use)
-#define XL_SPEC_TRY(expr)                                                                                         \
-  do {                                                                                                            \
-    hipError_t xl_e_ = (hipError_t)(expr);                                                                        \
-    if (xl_e_ != hipSuccess) {                                                                                    \
-      xl_last_hip_error = xl_e_;                                                                                  \
-      XL_LOG_ERR("%s failed: %s (%s:%d)", #expr, hipGetErrorString(xl_e_), __FILE__, __LINE__);                   \
-      return xl_e_ == hipErrorOutOfMemory ? -ENOMEM : -EIO;                                                       \
-    }                                                                                                             \
-  } while (0)
-
 #endif

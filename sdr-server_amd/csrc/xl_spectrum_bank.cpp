@@ -8,8 +8,8 @@
 // One round = one table (runs of the ragged launch, carry operations, the list of completed rows) written into pinned memory and
 // uploaded by one copy, then: the carry appends, the ragged transform launch, the carry saves, and -- when the round completes rows --
 // the finishing launch and one pair of copies (dB, pixels) into a pinned batch.  Launches that have nothing to do are left out.
-// The pinned tables are multi-buffered behind events, so a feed does not wait for the previous one; every feed is ordered behind the
-// previous feed's work by an event, so the single device table, the carries and the staging buffers need no copies of their own.
+// The ring of pinned tables, the single device table and the growth of the per-stream arrays, with the rules of their lifetimes, are
+// xl_bank_host.h's (shared with the resampler banks); a feed does not wait for the previous one.
 // Rows: a batch's rows are moved into their streams' host stores once its event has completed (looked at, without waiting, at the
 // start of every feed; waited for by take_rows of a stream that has rows in flight).  The stores grow; rows are never lost.
 #include "../../include/xlating_spectrum.h"
@@ -24,13 +24,13 @@
 #include <utility>
 #include <vector>
 
+#include "xl_bank_host.h"
 #include "xl_common.h"
 #include "xl_device.h"
 #include "xl_spectrum.h"
 #include "xl_spectrum_bank.h"
 #include "xl_spectrum_cut.h"
 
-#define XL_BANK_TABLES 4
 #define XL_BANK_MAX_STREAMS 65536
 
 namespace {
@@ -56,13 +56,6 @@ struct XlBankBatch {
   std::vector<std::pair<uint32_t, uint32_t>> rows;  // (stream id, gen) of row i
 };
 
-struct XlBankTable {
-  void *h = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
-  bool used = false;
-};
-
 }  // namespace
 
 struct xlating_spectrum_bank : XlSpecSetup {
@@ -71,15 +64,12 @@ struct xlating_spectrum_bank : XlSpecSetup {
   hipEvent_t last = nullptr;  // behind the latest feed's work
   bool fed = false, broken = false;
   uint32_t cap_streams = 0;
-  uint8_t *d_carry = nullptr;  // [cap_streams][W] samples
-  uint32_t *d_max = nullptr;   // [cap_streams * slots][W]
+  void *d_carry = nullptr;  // [cap_streams][W] samples
+  void *d_max = nullptr;    // [cap_streams * slots][W] uint32_t
   std::vector<XlBankStream> streams;
   std::vector<int> free_ids;
   uint64_t feed_no = 0;
-  XlBankTable tab[XL_BANK_TABLES];
-  int tab_i = 0;
-  void *d_tab = nullptr;
-  size_t d_tab_cap = 0;
+  XlTableRing ring;  // the rounds' tables
   float *d_db = nullptr;  // staging of one round's rows
   uint8_t *d_px = nullptr;
   size_t d_rows_cap = 0;
@@ -112,14 +102,14 @@ static int xl_bank_drain(xlating_spectrum_bank *b, bool wait) {
   while (!b->flying.empty()) {
     XlBankBatch *t = b->flying.front();
     if (wait) {
-      XL_SPEC_TRY(hipEventSynchronize(t->ev));
+      XL_TRY_RET(hipEventSynchronize(t->ev));
     } else {
       const hipError_t e = hipEventQuery(t->ev);
       if (e == hipErrorNotReady) {
         (void)hipGetLastError();  // (not an error: keep it out of the next launch's hipGetLastError)
         break;
       }
-      XL_SPEC_TRY(e);
+      XL_TRY_RET(e);
     }
     for (size_t i = 0; i < t->rows.size(); ++i) {
       const uint32_t id = t->rows[i].first;
@@ -140,47 +130,10 @@ static int xl_bank_drain(xlating_spectrum_bank *b, bool wait) {
 // device state for `need` streams: the arrays are replaced by larger ones and the present streams' state moves over
 static int xl_bank_reserve_streams(xlating_spectrum_bank *b, uint32_t need) {
   if (need <= b->cap_streams) return 0;
-  uint32_t cap = b->cap_streams ? b->cap_streams * 2u : 64u;
-  while (cap < need) cap *= 2u;
-  const size_t cbytes = (size_t)b->W * b->ssz, mbytes = (size_t)b->slots * b->W * sizeof(uint32_t);
-  if (b->fed) XL_SPEC_TRY(hipEventSynchronize(b->last));
-  uint8_t *carry = nullptr;
-  uint32_t *mx = nullptr;
-  hipError_t e = hipMalloc(&carry, cbytes * cap);
-  if (e == hipSuccess) e = hipMalloc(&mx, mbytes * cap);
-  if (e == hipSuccess) e = hipMemsetAsync(mx, 0, mbytes * cap, b->own);
-  if (e == hipSuccess && b->cap_streams > 0) {
-    e = hipMemcpyAsync(carry, b->d_carry, cbytes * b->cap_streams, hipMemcpyDeviceToDevice, b->own);
-    if (e == hipSuccess) e = hipMemcpyAsync(mx, b->d_max, mbytes * b->cap_streams, hipMemcpyDeviceToDevice, b->own);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(b->own);
-  if (e != hipSuccess) {
-    xl_last_hip_error = e;
-    XL_LOG_ERR("spectrum bank: state of %u streams x %u bins: %s", cap, b->W, hipGetErrorString(e));
-    if (carry) (void)hipFree(carry);
-    if (mx) (void)hipFree(mx);
-    return e == hipErrorOutOfMemory ? -ENOMEM : -EIO;
-  }
-  if (b->d_carry) (void)hipFree(b->d_carry);
-  if (b->d_max) (void)hipFree(b->d_max);
-  b->d_carry = carry, b->d_max = mx, b->cap_streams = cap;
-  return 0;
-}
-
-// a pinned table of at least `bytes`, free for writing
-static int xl_bank_table(xlating_spectrum_bank *b, size_t bytes, XlBankTable **out) {
-  XlBankTable &t = b->tab[b->tab_i];
-  b->tab_i = (b->tab_i + 1) % XL_BANK_TABLES;
-  if (t.used) XL_SPEC_TRY(hipEventSynchronize(t.ev));
-  if (t.cap < bytes) {
-    if (t.h) (void)hipHostFree(t.h);
-    t.h = nullptr, t.cap = 0;
-    const size_t cap = std::max<size_t>(bytes * 2, 1u << 16);
-    XL_SPEC_TRY(hipHostMalloc(&t.h, cap, hipHostMallocDefault));
-    t.cap = cap;
-  }
-  *out = &t;
-  return 0;
+  if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
+  const XlStreamArray a[] = {{&b->d_carry, (size_t)b->W * b->ssz, false},  // (a carry is appended to from `have` on, saved from 0 on)
+                             {&b->d_max, (size_t)b->slots * b->W * sizeof(uint32_t), true}};
+  return xl_streams_grow(&b->cap_streams, need, a, b->own, "spectrum bank: state");
 }
 
 static int xl_bank_batch(xlating_spectrum_bank *b, size_t rows, XlBankBatch **out) {
@@ -203,7 +156,7 @@ static int xl_bank_batch(xlating_spectrum_bank *b, size_t rows, XlBankBatch **ou
     if (e == hipSuccess) e = hipHostMalloc(&t->h_px, cap * b->W, hipHostMallocDefault);
     if (e != hipSuccess) {
       xl_bank_batch_free(t);
-      XL_SPEC_TRY(e);
+      XL_TRY_RET(e);
     }
     t->cap = cap;
   }
@@ -237,7 +190,7 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
     XlBankRun r;
     r.F = s.F, r.sr = s.sr, r.slot0 = id * b->slots;
     if (cut.carry_done) {  // the completed straddling transform: one more run, read from the carry
-      r.src = b->d_carry + (size_t)id * W * b->ssz, r.base = cut.carry_t0, r.g0 = cut.carry_g, r.tsum = T;
+      r.src = static_cast<const uint8_t *>(b->d_carry) + (size_t)id * W * b->ssz, r.base = cut.carry_t0, r.g0 = cut.carry_g, r.tsum = T;
       b->runs.push_back(r);
       T += 1u;
     }
@@ -262,60 +215,56 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
   const size_t o_list = o_ops + xl_bank_align(b->ops.size() * sizeof(XlBankCarry));
   const size_t bytes = o_list + xl_bank_align(b->list.size() * sizeof(uint32_t));
   if (bytes == 0) return 0;
-  XlBankTable *t = nullptr;
-  int rc = xl_bank_table(b, bytes, &t);
-  if (rc != 0) return rc;
-  if (b->d_tab_cap < bytes) {
-    XL_SPEC_TRY(hipStreamSynchronize(st));  // (this feed's earlier rounds read the table that is replaced)
-    if (b->d_tab) (void)hipFree(b->d_tab);
-    b->d_tab = nullptr, b->d_tab_cap = 0;
-    XL_SPEC_TRY(hipMalloc(&b->d_tab, bytes * 2));
-    b->d_tab_cap = bytes * 2;
+  XlRingTable *t = nullptr;
+  XL_TRY_RET(xl_ring_acquire(&b->ring, bytes, &t));
+  if (b->ring.d_cap < bytes) {
+    XL_TRY_RET(hipStreamSynchronize(st));  // (this feed's earlier rounds read the table that is replaced)
+    XL_TRY_RET(xl_ring_dev_grow(&b->ring, bytes));
   }
   uint8_t *h = static_cast<uint8_t *>(t->h);
   if (!b->runs.empty()) memcpy(h, b->runs.data(), b->runs.size() * sizeof(XlBankRun));
   if (!b->ops.empty()) memcpy(h + o_ops, b->ops.data(), b->ops.size() * sizeof(XlBankCarry));
   if (!b->list.empty()) memcpy(h + o_list, b->list.data(), b->list.size() * sizeof(uint32_t));
-  XL_SPEC_TRY(hipMemcpyAsync(b->d_tab, h, bytes, hipMemcpyHostToDevice, st));
-  XL_SPEC_TRY(hipEventRecord(t->ev, st));
-  t->used = true;
+  XL_TRY_RET(xl_ring_upload(&b->ring, t, bytes, st));
   b->copies += 1;
-  uint8_t *d = static_cast<uint8_t *>(b->d_tab);
+  uint8_t *d = static_cast<uint8_t *>(b->ring.d_tab);
   const XlBankCarry *d_ops = reinterpret_cast<const XlBankCarry *>(d + o_ops);
+  uint32_t *const d_max = static_cast<uint32_t *>(b->d_max);
   if (any_app) {
-    XL_SPEC_TRY(xl_bank_carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, false, st));
+    XL_TRY_RET(xl_bank_carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, false, st));
     b->launches += 1;
   }
   if (T > 0) {
     XlBankArgs a;
     a.runs = reinterpret_cast<const XlBankRun *>(d), a.nruns = (uint32_t)b->runs.size(), a.T = T, a.W = b->W, a.slots = b->slots;
-    a.rowmax = b->d_max, a.tw = b->d_tw, a.chirp = b->d_chirp, a.bspec = b->d_bspec, a.norm = 1.0f / (float)b->W;
-    XL_SPEC_TRY(xl_bank_launch(a, b->N, b->blue, b->fmt, st));
+    a.rowmax = d_max, a.tw = b->d_tw, a.chirp = b->d_chirp, a.bspec = b->d_bspec, a.norm = 1.0f / (float)b->W;
+    XL_TRY_RET(xl_bank_launch(a, b->N, b->blue, b->fmt, st));
     b->launches += 1;
   }
   if (any_save) {
-    XL_SPEC_TRY(xl_bank_carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, true, st));
+    XL_TRY_RET(xl_bank_carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, true, st));
     b->launches += 1;
   }
   const size_t nrows = b->list.size();
   if (nrows > 0) {
     if (b->d_rows_cap < nrows) {
-      XL_SPEC_TRY(hipStreamSynchronize(st));  // (earlier rounds' copies read the staging that is replaced)
+      XL_TRY_RET(hipStreamSynchronize(st));  // (earlier rounds' copies read the staging that is replaced)
       if (b->d_db) (void)hipFree(b->d_db);
       if (b->d_px) (void)hipFree(b->d_px);
       b->d_db = nullptr, b->d_px = nullptr, b->d_rows_cap = 0;
       const size_t cap = std::max<size_t>(nrows * 2, 64);
-      XL_SPEC_TRY(hipMalloc(&b->d_db, cap * b->W * sizeof(float)));
-      XL_SPEC_TRY(hipMalloc(&b->d_px, cap * b->W));
+      XL_TRY_RET(hipMalloc(&b->d_db, cap * b->W * sizeof(float)));
+      XL_TRY_RET(hipMalloc(&b->d_px, cap * b->W));
       b->d_rows_cap = cap;
     }
-    if ((rc = xl_bank_batch(b, nrows, &batch)) != 0) return rc;
+    const int rc = xl_bank_batch(b, nrows, &batch);
+    if (rc != 0) return rc;
     batch->rows.swap(owners);
     b->flying.push_back(batch);
-    XL_SPEC_TRY(xl_bank_finish(reinterpret_cast<const uint32_t *>(d + o_list), (uint32_t)nrows, b->d_max, b->d_db, b->d_px, b->W, st));
-    XL_SPEC_TRY(hipMemcpyAsync(batch->h_db, b->d_db, nrows * b->W * sizeof(float), hipMemcpyDeviceToHost, st));
-    XL_SPEC_TRY(hipMemcpyAsync(batch->h_px, b->d_px, nrows * b->W, hipMemcpyDeviceToHost, st));
-    XL_SPEC_TRY(hipEventRecord(batch->ev, st));
+    XL_TRY_RET(xl_bank_finish(reinterpret_cast<const uint32_t *>(d + o_list), (uint32_t)nrows, d_max, b->d_db, b->d_px, b->W, st));
+    XL_TRY_RET(hipMemcpyAsync(batch->h_db, b->d_db, nrows * b->W * sizeof(float), hipMemcpyDeviceToHost, st));
+    XL_TRY_RET(hipMemcpyAsync(batch->h_px, b->d_px, nrows * b->W, hipMemcpyDeviceToHost, st));
+    XL_TRY_RET(hipEventRecord(batch->ev, st));
     b->launches += 1;
     b->copies += 2;
   }
@@ -335,7 +284,7 @@ static int xl_bank_feed(xlating_spectrum_bank *b, size_t n, const int *ids, cons
   }
   if (total_t > ((uint64_t)1 << 31)) return -EINVAL;  // (the ragged launch counts its transforms in 32 bits)
   b->launches = b->copies = 0;
-  XL_SPEC_TRY(hipSetDevice(b->device));
+  XL_TRY_RET(hipSetDevice(b->device));
   int rc = xl_bank_drain(b, false);
   if (rc != 0) return rc;
   b->rem.assign(counts, counts + n);
@@ -343,13 +292,13 @@ static int xl_bank_feed(xlating_spectrum_bank *b, size_t n, const int *ids, cons
   bool any = false;
   for (size_t i = 0; i < n; ++i) b->ptr[i] = static_cast<const uint8_t *>(dev_samples[i]), any |= counts[i] > 0;
   if (!any) return 0;
-  if (b->fed) XL_SPEC_TRY(hipStreamWaitEvent(st, b->last, 0));
+  if (b->fed) XL_TRY_RET(hipStreamWaitEvent(st, b->last, 0));
   while (any) {
     if ((rc = xl_bank_round(b, n, ids, st)) != 0) return rc;
     any = false;
     for (size_t i = 0; i < n; ++i) any |= b->rem[i] > 0;
   }
-  XL_SPEC_TRY(hipEventRecord(b->last, st));
+  XL_TRY_RET(hipEventRecord(b->last, st));
   b->fed = true;
   return 0;
 }
@@ -375,7 +324,7 @@ extern "C" int xlating_spectrum_bank_create(int width, int format, xlating_spect
   }
   hipError_t e = hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->last, hipEventDisableTiming);
-  for (int i = 0; i < XL_BANK_TABLES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->tab[i].ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = xl_ring_init(&b->ring);
   if (e != hipSuccess) {
     xl_last_hip_error = e;
     XL_LOG_ERR("xlating_spectrum_bank_create: %s", hipGetErrorString(e));
@@ -394,7 +343,7 @@ extern "C" int xlating_spectrum_bank_add(xlating_spectrum_bank *b, uint32_t samp
     const bool reuse = !b->free_ids.empty();
     const size_t id = reuse ? (size_t)b->free_ids.back() : b->streams.size();
     if (id >= XL_BANK_MAX_STREAMS) return -ENOMEM;
-    XL_SPEC_TRY(hipSetDevice(b->device));
+    XL_TRY_RET(hipSetDevice(b->device));
     const int rc = xl_bank_reserve_streams(b, (uint32_t)id + 1u);
     if (rc != 0) return rc;
     if (reuse)
@@ -414,11 +363,11 @@ extern "C" int xlating_spectrum_bank_remove(xlating_spectrum_bank *b, int stream
   if (!xl_bank_live(b, stream_id)) return -EINVAL;
   XlBankStream &s = b->streams[(size_t)stream_id];
   if (s.P > 0 && !b->broken) {  // a row in progress leaves maxima behind: clear the id's slots for its next use
-    XL_SPEC_TRY(hipSetDevice(b->device));
-    if (b->fed) XL_SPEC_TRY(hipEventSynchronize(b->last));
+    XL_TRY_RET(hipSetDevice(b->device));
+    if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
     const size_t mbytes = (size_t)b->slots * b->W * sizeof(uint32_t);
-    XL_SPEC_TRY(hipMemsetAsync(b->d_max + (size_t)stream_id * b->slots * b->W, 0, mbytes, b->own));
-    XL_SPEC_TRY(hipStreamSynchronize(b->own));
+    XL_TRY_RET(hipMemsetAsync(static_cast<uint8_t *>(b->d_max) + (size_t)stream_id * mbytes, 0, mbytes, b->own));
+    XL_TRY_RET(hipStreamSynchronize(b->own));
   }
   s.live = false;
   s.gen++;
@@ -456,7 +405,7 @@ extern "C" int xlating_spectrum_bank_take_rows(xlating_spectrum_bank *b, int str
   if (b->broken) return -EIO;
   XlBankStream &s = b->streams[(size_t)stream_id];
   if (s.in_flight > 0) {
-    XL_SPEC_TRY(hipSetDevice(b->device));
+    XL_TRY_RET(hipSetDevice(b->device));
     int rc;
     try {
       rc = xl_bank_drain(b, true);
@@ -497,11 +446,7 @@ extern "C" void xlating_spectrum_bank_destroy(xlating_spectrum_bank *b) {
   if (b->own) (void)hipStreamSynchronize(b->own);
   for (XlBankBatch *t : b->flying) xl_bank_batch_free(t);
   for (XlBankBatch *t : b->idle) xl_bank_batch_free(t);
-  for (XlBankTable &t : b->tab) {
-    if (t.h) (void)hipHostFree(t.h);
-    if (t.ev) (void)hipEventDestroy(t.ev);
-  }
-  if (b->d_tab) (void)hipFree(b->d_tab);
+  xl_ring_destroy(&b->ring);
   if (b->d_db) (void)hipFree(b->d_db);
   if (b->d_px) (void)hipFree(b->d_px);
   if (b->d_carry) (void)hipFree(b->d_carry);

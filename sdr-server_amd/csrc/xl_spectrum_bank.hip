@@ -10,6 +10,7 @@
 // a slot belongs to one stream and, within a launch, to one row: stream or row changes are slot changes.
 // SCALAR FP32 ONLY, no matrix instructions (Makefile: SPEC_FLAGS), as xl_spectrum.hip: these launches run behind and beside the
 // engine's matrix-core launches.
+#include "xl_ragged.h"
 #include "xl_spectrum_bank.h"
 #include "xl_spectrum_dev.h"
 
@@ -28,12 +29,7 @@ __global__ void __launch_bounds__(xl_spec_nt(N)) xl_bank_kernel(const XlBankArgs
   for (uint32_t b = tid; b < B; b += NT) {
     const uint64_t t = first + b;
     if (t < a.T) {
-      uint32_t lo = 0u, hi = a.nruns;  // the last run with tsum <= t (runs[0].tsum == 0)
-      while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) / 2u;
-        if (a.runs[mid].tsum <= (uint32_t)t) lo = mid; else hi = mid;
-      }
-      const XlBankRun r = a.runs[lo];
+      const XlBankRun r = a.runs[xl_ragged_find(a.runs, a.nruns, (uint32_t)t, [](const XlBankRun &x) { return x.tsum; })];
       const int64_t g = r.g0 + (int64_t)((uint32_t)t - r.tsum);
       const int64_t row = g / r.F, k = g - row * r.F;
       src[b] = r.src;

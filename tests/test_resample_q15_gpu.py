@@ -347,6 +347,86 @@ def test_a_feed_of_single_tap_streams_is_one_launch():
     bank.close()
 
 
+# ------------------------------------------------------------------------------------------------------------ the tables' and carries' lifetimes
+def alone(bank, L, M, taps, addr, pieces):
+    """the oracle of the three tests below: the stream by itself in `bank` (which holds nothing else), fed the same pieces with a
+    fetch behind every feed -> its outputs per piece"""
+    sid = bank.add(L, M, taps)
+    outs, pos = [], 0
+    for c in pieces:
+        bank.feed([sid], [addr + 4 * pos], [c], stream())
+        bank.fetch()
+        outs.append(bank.output(sid))
+        pos += c
+    bank.remove(sid)
+    return outs
+
+
+def test_carry_array_grows_under_live_carries():
+    """64 streams hold a carry (Q = 21) from a feed that nothing has waited for when the 65th is added: the array of carry slots is
+    replaced by one of 128 and the carries move over"""
+    _, _, L, M, taps = admission(10000000, 48000)
+    assert (L, M) == (3, 5) and -(-taps.size // L) == 21
+    first, second = [300 + i for i in range(65)], [200 + 2 * i for i in range(65)]
+    dev = [to_device(full_range(first[i] + second[i], 7000 + i)) for i in range(65)]
+    bank, ref = xl.ResamplerBankQ15(), xl.ResamplerBankQ15()
+    sids = [bank.add(L, M, taps) for _ in range(64)]
+    bank.feed(sids, [d[1] for d in dev[:64]], first[:64], stream())
+    sids.append(bank.add(L, M, taps))
+    assert sids == list(range(65))
+    bank.feed(sids, [d[1] + 4 * c for d, c in zip(dev[:64], first)] + [dev[64][1]], second[:64] + [first[64] + second[64]], stream())
+    bank.fetch()
+    for i, sid in enumerate(sids):
+        want = alone(ref, L, M, taps, dev[i][1], [first[i], second[i]])
+        assert np.array_equal(bank.output(sid), want[1] if i < 64 else np.concatenate(want)), i
+    bank.close()
+    ref.close()
+
+
+def test_six_feeds_in_a_row_reuse_the_pinned_tables():
+    """the ring holds four pinned tables: the fifth and the sixth feed write tables that earlier feeds were uploaded from, and nothing
+    on the host waits in between"""
+    _, _, L, M, taps = admission(10000000, 48000)
+    pieces = [300, 200, 257, 100, 333, 150]
+    keep, addr = to_device(full_range(sum(pieces), 41))
+    bank, ref = xl.ResamplerBankQ15(), xl.ResamplerBankQ15()
+    sid = bank.add(L, M, taps)
+    pos = 0
+    for c in pieces:
+        bank.feed([sid], [addr + 4 * pos], [c], stream())
+        assert bank.last_feed_ops() == (2, 1)
+        pos += c
+    bank.fetch()
+    assert bank.produced(sid) == RR.counts(L, M, pos)
+    got, want = bank.output(sid), alone(ref, L, M, taps, addr, pieces)[-1]  # (which every earlier feed's carry has gone into)
+    assert got.shape == want.shape and want.shape[0] > 0 and np.array_equal(got, want)
+    bank.close()
+    ref.close()
+
+
+def test_device_table_grows_between_feeds():
+    """a feed of 2 streams, then one that names 5 -- more than twice the table the first allocated -- while nothing has waited for
+    the first, then a third"""
+    _, _, L, M, taps = admission(10000000, 48000)
+    counts = [[300, 310, 0, 0, 0], [200, 210, 220, 230, 240], [150, 160, 170, 180, 190]]
+    dev = [to_device(full_range(sum(c[i] for c in counts), 43 + i)) for i in range(5)]
+    bank, ref = xl.ResamplerBankQ15(), xl.ResamplerBankQ15()
+    sids = [bank.add(L, M, taps) for _ in range(5)]
+    want = [alone(ref, L, M, taps, dev[i][1], [c[i] for c in counts]) for i in range(5)]
+    pos = [0] * 5
+    for f, c in enumerate(counts):
+        named = [i for i in range(5) if c[i] > 0]
+        bank.feed([sids[i] for i in named], [dev[i][1] + 4 * pos[i] for i in named], [c[i] for i in named], stream())
+        pos = [p + v for p, v in zip(pos, c)]
+        if f > 0:
+            bank.fetch()
+            for i in named:
+                got = bank.output(sids[i])
+                assert got.shape == want[i][f].shape and got.shape[0] > 0 and np.array_equal(got, want[i][f]), (f, i)
+    bank.close()
+    ref.close()
+
+
 # ------------------------------------------------------------------------------------------------------------ housekeeping
 def test_equal_definitions_share_one_table():
     _, _, L, M, taps = admission(2016000, 44100)

@@ -139,6 +139,30 @@ def test_rounds_give_the_same_rows(monkeypatch):
     _BANK_RUNS.clear()
 
 
+def test_six_feeds_in_a_row_reuse_the_pinned_tables():
+    """the ring holds four pinned tables: the fifth and the sixth feed write tables that earlier feeds were uploaded from, and nothing
+    on the host waits in between (the per-stream arrays growing under rows in progress and the device table growing between feeds:
+    test_membership)"""
+    import torch
+
+    W, sr, fmt = 64, 64 * 3 + 33, "cf32"
+    counts = [300, 200, 257, 150, 333, 150]  # every feed completes a row and leaves a straddling transform
+    raw = signal(fmt, sum(counts), W, seed=61)
+    d = torch.from_numpy(raw).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    bank = xl.SpectrumBank(W, fmt)
+    sid = bank.add(sr)
+    pos = 0
+    for c in counts:
+        assert pos // sr < (pos + c) // sr and (pos + c) % sr % W != 0
+        bank.feed([sid], [d.data_ptr() + 8 * pos], [c], st)
+        pos += c
+    rows = bank.take_rows(sid)
+    assert rows[0].shape[0] == pos // sr == 6
+    assert_same_rows(rows, single(raw, fmt, sr, W), "six feeds")
+    bank.close()
+
+
 # ------------------------------------------------------------------------------------------------------------ (3) membership
 def test_membership():
     import torch
