@@ -69,8 +69,26 @@ void xlating_spectrum_destroy(xlating_spectrum *s);
  */
 typedef struct xlating_spectrum_bank xlating_spectrum_bank;
 
-/* width (1 .. XLATING_SPECTRUM_MAX_WIDTH: the bank has no wide entry) and format as xlating_spectrum_create.  0, -EINVAL, -ENODEV (with a "<3>" line on stderr), -ENOMEM. */
+/* width (1 .. XLATING_SPECTRUM_MAX_WIDTH; wider: xlating_spectrum_bank_create_wide) and format as xlating_spectrum_create.  0, -EINVAL, -ENODEV (with a "<3>" line on stderr), -ENOMEM. */
 int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out);
+
+/* The same with the cap at XLATING_SPECTRUM_MAX_WIDE_WIDTH: the same checks in the same order with the same return values, every
+ * -EINVAL decided before the device is touched (*out is then left alone).  The bank is added to, fed, read and destroyed with the
+ * functions below.  Up to XLATING_SPECTRUM_MAX_WIDTH it is the very bank xlating_spectrum_bank_create builds (same kernels,
+ * bit-identical rows).  A wider one runs each transform in two levels across workgroups, the transforms of ALL streams of a feed in
+ * one ragged list that goes through a scratch buffer in device memory a chunk at a time; per stream its rows are, bit for bit, those
+ * of an xlating_spectrum_create_wide object of the same (sampling_rate, width, format) from the same samples -- under any split into
+ * feeds, in any company of other streams, with streams added and removed between feeds.
+ * Memory of a bank of `width` W (s: bytes per complex sample, 2 / 4 / 8):
+ *   per stream, device: W * s of carry and two row slots of W * 4 -- W * (s + 8) bytes: 768 KB for cf32 at W = 48000, 16 MiB at
+ *     W = 1048576.  The arrays grow by doubling as streams are added, from as many streams as 64 MiB hold (at most 64);
+ *   per stream, host: its completed rows that have not been taken, W * 5 bytes each;
+ *   per bank, device: the scratch (64 MiB), the tables (8 .. 40 bytes per bin), and a staging for completed rows of at most 32 MiB (or
+ *     one row), allocated when the first row completes;
+ *   per bank, pinned host: one batch of at most the staging's size EACH per round whose rows are on their way, kept for reuse: a
+ *     feed that the staging cuts into k rounds holds k of them (not bounded in total).
+ * An empty bank of width 1048576 holds about 72 MiB of device memory and no pinned row memory. */
+int xlating_spectrum_bank_create_wide(int width, int format, xlating_spectrum_bank **out);
 
 /* A new stream whose sample 0 is the first sample it is fed.  Returns its stream id >= 0 (ids of removed streams are reused), -EINVAL
  * (sampling_rate == 0 or < width) or -ENOMEM.  Streams may be added and removed between any two feeds; the per-stream device state
@@ -97,7 +115,12 @@ int xlating_spectrum_bank_rows_pending(const xlating_spectrum_bank *b, int strea
 /* What the latest feed issued: kernel launches and memory copies (for tests, logs and benchmarks).  A feed is a few launches (carry
  * appends, one ragged transform launch, carry saves, one finishing launch when rows complete) and one to three copies, times the
  * number of rounds: a feed that takes a stream through more rows than the bank keeps row slots per stream (2 .. 16 by width) is cut
- * into rounds. */
+ * into rounds.
+ * A width above XLATING_SPECTRUM_MAX_WIDTH: the transform launch becomes two launches (a power-of-two width) or three (any other) per
+ * CHUNK of the round's transforms, a chunk being as many transforms as the scratch holds (64 MiB / (8 N) with N the transform length:
+ * the width if a power of two, else the power of two >= 2 width - 1); and a round also ends when the rows it completes would exceed
+ * the staging.  So the launch count of a feed depends on how many transforms it runs, how many rows it completes and how many
+ * transforms the scratch holds -- not on how the transforms are spread over streams. */
 int xlating_spectrum_bank_last_feed_ops(const xlating_spectrum_bank *b, unsigned *launches, unsigned *copies);
 
 void xlating_spectrum_bank_destroy(xlating_spectrum_bank *b);

@@ -766,7 +766,7 @@ SPECTRUM_SYMBOLS = ["xlating_spectrum_create", "xlating_spectrum_feed_host", "xl
                     "xlating_spectrum_create_wide", "spectrogram_main_wide",
                     "xlating_spectrum_bank_create", "xlating_spectrum_bank_add", "xlating_spectrum_bank_remove",
                     "xlating_spectrum_bank_feed_device", "xlating_spectrum_bank_take_rows", "xlating_spectrum_bank_rows_pending",
-                    "xlating_spectrum_bank_last_feed_ops", "xlating_spectrum_bank_destroy"]
+                    "xlating_spectrum_bank_last_feed_ops", "xlating_spectrum_bank_destroy", "xlating_spectrum_bank_create_wide"]
 SPECTRUM_FMT = {"cu8": 0, "cs16": 2, "cf32": 3}
 _SPEC_NP = {"cu8": np.uint8, "cs16": np.int16, "cf32": np.float32}
 _slib = None
@@ -804,6 +804,8 @@ def spectrum_lib():
     S.spectrogram_main_wide.restype = C.c_int
     S.xlating_spectrum_bank_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     S.xlating_spectrum_bank_create.restype = C.c_int
+    S.xlating_spectrum_bank_create_wide.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    S.xlating_spectrum_bank_create_wide.restype = C.c_int
     S.xlating_spectrum_bank_add.argtypes = [C.c_void_p, C.c_uint32]
     S.xlating_spectrum_bank_add.restype = C.c_int
     S.xlating_spectrum_bank_remove.argtypes = [C.c_void_p, C.c_int]
@@ -879,16 +881,18 @@ class Spectrum:
 
 class SpectrumBank:
     """One `xlating_spectrum_bank *` (include/xlating_spectrum.h): many streams of one width and format, each with its own
-    sampling_rate, advanced together by one feed of device buffers; rows are taken per stream."""
+    sampling_rate, advanced together by one feed of device buffers; rows are taken per stream.
+    wide=True creates it with xlating_spectrum_bank_create_wide: widths up to 1048576 instead of 8192."""
 
-    def __init__(self, width, fmt="cf32"):
+    def __init__(self, width, fmt="cf32", wide=False):
         S = spectrum_lib()
+        name = "xlating_spectrum_bank_create_wide" if wide else "xlating_spectrum_bank_create"
         if fmt not in SPECTRUM_FMT:
-            raise XlatingError("xlating_spectrum_bank_create", -22)
+            raise XlatingError(name, -22)
         h = C.c_void_p()
-        code = S.xlating_spectrum_bank_create(width, SPECTRUM_FMT[fmt], C.byref(h))
+        code = getattr(S, name)(width, SPECTRUM_FMT[fmt], C.byref(h))
         if code != 0:
-            raise XlatingError("xlating_spectrum_bank_create", code)
+            raise XlatingError(name, code)
         self.h, self.W, self.fmt = h, width, fmt
 
     def add(self, sampling_rate):

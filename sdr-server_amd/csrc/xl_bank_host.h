@@ -92,11 +92,13 @@ struct XlStreamArray {
   bool zero;      // a new array starts zeroed (one that does not is written before it is read)
 };
 
-// room for `need` streams in every array of a[]: the capacity doubles from 64 until it fits.  The caller has found need > *cap and
-// has waited for `last`.  what: names the bank and the arrays in the error line.
+// room for `need` streams in every array of a[]: the capacity doubles from `first` (64; fewer where a stream's state is large: the wide
+// spectrum bank) until it fits.  The caller has found need > *cap and has waited for `last`.  what: names the bank and the arrays in the
+// error line.
 template <size_t N>
-static inline int xl_streams_grow(uint32_t *cap, uint32_t need, const XlStreamArray (&a)[N], hipStream_t own, const char *what) {
-  uint32_t ncap = *cap ? *cap * 2u : 64u;
+static inline int xl_streams_grow(uint32_t *cap, uint32_t need, const XlStreamArray (&a)[N], hipStream_t own, const char *what,
+                                  uint32_t first = 64u) {
+  uint32_t ncap = *cap ? *cap * 2u : first;
   while (ncap < need) ncap *= 2u;
   void *fresh[N] = {};
   hipError_t e = hipSuccess;

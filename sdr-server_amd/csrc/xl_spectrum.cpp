@@ -214,6 +214,15 @@ void xl_spec_setup_free(XlSpecSetup *u) {
   u->d_tw = u->d_chirp = u->d_bspec = u->d_tw1 = u->d_tw2 = nullptr;
 }
 
+uint64_t xl_specw_scratch_bytes(void) {
+  uint64_t scratch = XL_SPECW_SCRATCH_DEFAULT;
+  if (const char *v = xl_exp_getenv("XL_EXP_SPEC_SCRATCH")) {  // test knob: the scratch buffer's size in bytes
+    const long long b = strtoll(v, nullptr, 10);
+    if (b > 0) scratch = (uint64_t)std::min<long long>(b, 1ll << 30);
+  }
+  return scratch;
+}
+
 // ---------------------------------------------------------------------------------------------------------- row ring
 static void xl_spec_free_rows(uint32_t *d_max, float *d_db, uint8_t *d_px, float *h_db, uint8_t *h_px) {
   if (d_max) (void)hipFree(d_max);
@@ -372,13 +381,8 @@ static int xl_spectrum_create_cap(uint32_t sampling_rate, int width, int max_wid
   }
   if (e == hipSuccess) e = hipMalloc(&s->d_carry, (size_t)s->W * s->ssz);
   if (s->W > XL_SPEC_MAX_W) {
-    uint64_t scratch = XL_SPECW_SCRATCH_DEFAULT;
-    if (const char *v = xl_exp_getenv("XL_EXP_SPEC_SCRATCH")) {  // test knob: the scratch buffer's size in bytes
-      const long long b = strtoll(v, nullptr, 10);
-      if (b > 0) scratch = (uint64_t)std::min<long long>(b, 1ll << 30);
-    }
     s->wide = true;
-    s->scratch_T = (uint32_t)xl_specw_chunk(scratch, s->N);
+    s->scratch_T = (uint32_t)xl_specw_chunk(xl_specw_scratch_bytes(), s->N);
     if (e == hipSuccess) e = hipMalloc(&s->d_scratch, sizeof(float2) * (size_t)s->N * s->scratch_T);
   }
   if (e != hipSuccess) {

@@ -54,7 +54,7 @@ struct XlSpecWideArgs {
 };
 int xl_specw_launch(const XlSpecWideArgs &w, bool bluestein, int fmt, hipStream_t st);
 // xl_spec_finish for a wide object's rows: permuted (a plain width): column j reads its bin (the half swap first) from the row pass's
-// position; the dB is 10 * the correctly rounded log10f (xl_spectrum_wide.hip: xl_specw_db)
+// position; the dB is 10 * the correctly rounded log10f (xl_spectrum_wide_dev.h: xl_specw_db)
 int xl_specw_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t N1, uint32_t N2, bool permuted, uint32_t cap, int64_t r0,
                     uint32_t nrows, hipStream_t st);
 
@@ -67,16 +67,21 @@ struct XlSpecSetup {
   bool blue = false;
   int device = 0;
   float2 *d_tw = nullptr, *d_chirp = nullptr, *d_bspec = nullptr;
-  // a width above XL_SPEC_MAX_W (the single object's wide entry only): the split, the two levels' twiddles; d_bspec is in [k1][k2] order
+  // a width above XL_SPEC_MAX_W (the wide entries of the single object and of the bank): the split, the two levels' twiddles; d_bspec is
+  // in [k1][k2] order
   uint32_t N1 = 0, N2 = 0;
   float2 *d_tw1 = nullptr, *d_tw2 = nullptr;
 };
 
 // In this order: -EINVAL for a width outside 1 .. max_width (XLATING_SPECTRUM_MAX_WIDTH, or XLATING_SPECTRUM_MAX_WIDE_WIDTH from
-// xlating_spectrum_create_wide; the bank passes the former) or an unknown format, before the device is touched; the
+// xlating_spectrum_create_wide and xlating_spectrum_bank_create_wide) or an unknown format, before the device is touched; the
 // device, -ENODEV with a "<3>" line that names `who` (the calling function) when there is none; N; the tables (-ENOMEM, -EIO).  The
 // device is left current.  A failed init leaves nothing to free.
 int xl_spec_setup_init(XlSpecSetup *u, int width, int max_width, int format, const char *who);
 void xl_spec_setup_free(XlSpecSetup *u);
+
+// Bytes of the two-level transform's scratch buffer, for the single wide object and the wide bank alike: XL_SPECW_SCRATCH_DEFAULT, or
+// what the test knob beside XL_TESTING=1 says (xl_spectrum.cpp; at most 1 GiB).  xl_specw_chunk turns it into transforms.
+uint64_t xl_specw_scratch_bytes(void);
 
 #endif

@@ -10,6 +10,11 @@
 // the finishing launch and one pair of copies (dB, pixels) into a pinned batch.  Launches that have nothing to do are left out.
 // The ring of pinned tables, the single device table and the growth of the per-stream arrays, with the rules of their lifetimes, are
 // xl_bank_host.h's (shared with the resampler banks); a feed does not wait for the previous one.
+// A bank of xlating_spectrum_bank_create_wide with a width above 8192 differs in four places: the ragged transform launch becomes the
+// two-level transform's passes (xl_spectrum_bank_wide.hip), a chunk of the round's transform list at a time through one scratch buffer
+// (stream order keeps one chunk's passes and the next chunk's apart); the carries are copied on a grid over pieces; the finishing launch
+// is that file's; and the staging and the pinned batches are bounded in BYTES, which is one more reason for a round to end
+// (xl_spectrum_bank_plan.h: a round's row budget).  The cut, the runs, the tables and the row stores are the same.
 // Rows: a batch's rows are moved into their streams' host stores once its event has completed (looked at, without waiting, at the
 // start of every feed; waited for by take_rows of a stream that has rows in flight).  The stores grow; rows are never lost.
 #include "../../include/xlating_spectrum.h"
@@ -29,7 +34,9 @@
 #include "xl_device.h"
 #include "xl_spectrum.h"
 #include "xl_spectrum_bank.h"
+#include "xl_spectrum_bank_plan.h"
 #include "xl_spectrum_cut.h"
+#include "xl_spectrum_wide_plan.h"
 
 #define XL_BANK_MAX_STREAMS 65536
 
@@ -82,6 +89,12 @@ struct xlating_spectrum_bank : XlSpecSetup {
   std::vector<uint32_t> list;
   std::vector<size_t> rem;
   std::vector<const uint8_t *> ptr;
+  // a width above XL_SPEC_MAX_W: the two-level transform's scratch ([transform][k1][j2]), how many transforms it holds, and how many rows
+  // the staging (and a pinned batch) may hold
+  bool wide = false;
+  float2 *d_scratch = nullptr;
+  uint32_t scratch_T = 0;
+  size_t stage_rows = 0;
 };
 
 static bool xl_bank_live(const xlating_spectrum_bank *b, int id) {
@@ -133,7 +146,15 @@ static int xl_bank_reserve_streams(xlating_spectrum_bank *b, uint32_t need) {
   if (b->fed) XL_TRY_RET(hipEventSynchronize(b->last));
   const XlStreamArray a[] = {{&b->d_carry, (size_t)b->W * b->ssz, false},  // (a carry is appended to from `have` on, saved from 0 on)
                              {&b->d_max, (size_t)b->slots * b->W * sizeof(uint32_t), true}};
-  return xl_streams_grow(&b->cap_streams, need, a, b->own, "spectrum bank: state");
+  const uint32_t first = b->wide ? xl_bankw_first_streams(a[0].stride + a[1].stride) : 64u;
+  return xl_streams_grow(&b->cap_streams, need, a, b->own, "spectrum bank: state", first);
+}
+
+// rows to allocate for a staging or a batch that must hold `rows`: twice that and 64 at least; a wide bank's are bounded in bytes
+// (stage_rows >= rows: the round's budget)
+static size_t xl_bank_rows_cap(const xlating_spectrum_bank *b, size_t rows) {
+  const size_t cap = std::max<size_t>(rows * 2, 64);
+  return b->wide ? std::max(rows, std::min(cap, b->stage_rows)) : cap;
 }
 
 static int xl_bank_batch(xlating_spectrum_bank *b, size_t rows, XlBankBatch **out) {
@@ -150,7 +171,7 @@ static int xl_bank_batch(xlating_spectrum_bank *b, size_t rows, XlBankBatch **ou
       b->idle.pop_back();
     }
     t = new XlBankBatch();
-    const size_t cap = std::max<size_t>(rows * 2, 64);
+    const size_t cap = xl_bank_rows_cap(b, rows);
     hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipHostMalloc(&t->h_db, cap * b->W * sizeof(float), hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc(&t->h_px, cap * b->W, hipHostMallocDefault);
@@ -174,11 +195,14 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
   std::vector<std::pair<uint32_t, uint32_t>> owners;
   uint32_t T = 0;
   bool any_app = false, any_save = false;
+  int64_t budget = (int64_t)b->stage_rows;  // (wide) rows this round may still complete
   for (size_t i = 0; i < n; ++i) {
     if (b->rem[i] == 0) continue;
     const uint32_t id = (uint32_t)ids[i];
     XlBankStream &s = b->streams[id];
-    const int64_t c = std::min<int64_t>((int64_t)b->rem[i], xl_spec_round_limit(s.sr, s.P, b->slots));
+    const int64_t lim = b->wide ? xl_bankw_round_limit(s.sr, W, s.P, b->slots, budget) : xl_spec_round_limit(s.sr, s.P, b->slots);
+    if (lim == 0) continue;  // (wide: the staging is full; the stream goes on in the next round)
+    const int64_t c = std::min<int64_t>((int64_t)b->rem[i], lim);
     const XlSpecCut cut = xl_spec_cut(s.sr, W, s.P, c);
     if (cut.carry_app > 0 || cut.save_n > 0) {
       XlBankCarry op;
@@ -204,6 +228,7 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
       owners.emplace_back(id, s.gen);
     }
     const int done = (int)std::max<int64_t>(cut.rows_done - s.rows_done, 0);
+    budget -= done;
     s.pending += done, s.in_flight += done;
     s.rows_done = std::max(s.rows_done, cut.rows_done);
     s.P += c;
@@ -230,19 +255,31 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
   uint8_t *d = static_cast<uint8_t *>(b->ring.d_tab);
   const XlBankCarry *d_ops = reinterpret_cast<const XlBankCarry *>(d + o_ops);
   uint32_t *const d_max = static_cast<uint32_t *>(b->d_max);
+  const auto carry = b->wide ? xl_bankw_carry : xl_bank_carry;
   if (any_app) {
-    XL_TRY_RET(xl_bank_carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, false, st));
+    XL_TRY_RET(carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, false, st));
     b->launches += 1;
   }
   if (T > 0) {
     XlBankArgs a;
     a.runs = reinterpret_cast<const XlBankRun *>(d), a.nruns = (uint32_t)b->runs.size(), a.T = T, a.W = b->W, a.slots = b->slots;
     a.rowmax = d_max, a.tw = b->d_tw, a.chirp = b->d_chirp, a.bspec = b->d_bspec, a.norm = 1.0f / (float)b->W;
-    XL_TRY_RET(xl_bank_launch(a, b->N, b->blue, b->fmt, st));
-    b->launches += 1;
+    if (!b->wide) {
+      XL_TRY_RET(xl_bank_launch(a, b->N, b->blue, b->fmt, st));
+      b->launches += 1;
+    } else {
+      XlBankWideArgs w;
+      w.a = a, w.scratch = b->d_scratch, w.tw1 = b->d_tw1, w.tw2 = b->d_tw2, w.N = b->N, w.N1 = b->N1, w.N2 = b->N2;
+      const uint64_t chunks = xl_bankw_chunks(T, b->scratch_T);
+      for (uint64_t i = 0; i < chunks; ++i) {
+        w.t0 = (uint32_t)(i * b->scratch_T), w.Tc = (uint32_t)xl_bankw_chunk_len(T, b->scratch_T, i);
+        XL_TRY_RET(xl_bankw_launch(w, b->blue, b->fmt, st));
+        b->launches += xl_bankw_passes(b->blue);
+      }
+    }
   }
   if (any_save) {
-    XL_TRY_RET(xl_bank_carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, true, st));
+    XL_TRY_RET(carry(d_ops, (uint32_t)b->ops.size(), b->d_carry, b->W, b->ssz, true, st));
     b->launches += 1;
   }
   const size_t nrows = b->list.size();
@@ -252,7 +289,7 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
       if (b->d_db) (void)hipFree(b->d_db);
       if (b->d_px) (void)hipFree(b->d_px);
       b->d_db = nullptr, b->d_px = nullptr, b->d_rows_cap = 0;
-      const size_t cap = std::max<size_t>(nrows * 2, 64);
+      const size_t cap = xl_bank_rows_cap(b, nrows);
       XL_TRY_RET(hipMalloc(&b->d_db, cap * b->W * sizeof(float)));
       XL_TRY_RET(hipMalloc(&b->d_px, cap * b->W));
       b->d_rows_cap = cap;
@@ -261,7 +298,11 @@ static int xl_bank_round(xlating_spectrum_bank *b, size_t n, const int *ids, hip
     if (rc != 0) return rc;
     batch->rows.swap(owners);
     b->flying.push_back(batch);
-    XL_TRY_RET(xl_bank_finish(reinterpret_cast<const uint32_t *>(d + o_list), (uint32_t)nrows, d_max, b->d_db, b->d_px, b->W, st));
+    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(d + o_list);
+    if (b->wide)
+      XL_TRY_RET(xl_bankw_finish(d_list, (uint32_t)nrows, d_max, b->d_db, b->d_px, b->W, b->N1, b->N2, !b->blue, st));
+    else
+      XL_TRY_RET(xl_bank_finish(d_list, (uint32_t)nrows, d_max, b->d_db, b->d_px, b->W, st));
     XL_TRY_RET(hipMemcpyAsync(batch->h_db, b->d_db, nrows * b->W * sizeof(float), hipMemcpyDeviceToHost, st));
     XL_TRY_RET(hipMemcpyAsync(batch->h_px, b->d_px, nrows * b->W, hipMemcpyDeviceToHost, st));
     XL_TRY_RET(hipEventRecord(batch->ev, st));
@@ -304,10 +345,10 @@ static int xl_bank_feed(xlating_spectrum_bank *b, size_t n, const int *ids, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------- C API
-extern "C" int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out) {
+static int xl_bank_create_cap(int width, int max_width, int format, xlating_spectrum_bank **out, const char *who) {
   if (out == nullptr) return -EINVAL;
   XlSpecSetup u;
-  int rc = xl_spec_setup_init(&u, width, XLATING_SPECTRUM_MAX_WIDTH, format, "xlating_spectrum_bank_create");
+  int rc = xl_spec_setup_init(&u, width, max_width, format, who);
   if (rc == -EINVAL) return rc;  // (as the refusal above: *out is left alone)
   *out = nullptr;
   if (rc != 0) return rc;
@@ -325,15 +366,34 @@ extern "C" int xlating_spectrum_bank_create(int width, int format, xlating_spect
   hipError_t e = hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&b->last, hipEventDisableTiming);
   if (e == hipSuccess) e = xl_ring_init(&b->ring);
+  if (e == hipSuccess && b->W > XL_SPEC_MAX_W) {
+    uint64_t stage = XL_BANKW_STAGE_DEFAULT;
+    if (const char *v = xl_exp_getenv("XL_EXP_SPEC_BANK_STAGE")) {  // test knob: the staging's size in bytes (rows per round)
+      const long long sb = strtoll(v, nullptr, 10);
+      if (sb > 0) stage = (uint64_t)std::min<long long>(sb, 1ll << 30);
+    }
+    b->wide = true;
+    b->stage_rows = (size_t)xl_bankw_stage_rows(stage, b->W);
+    b->scratch_T = (uint32_t)xl_specw_chunk(xl_specw_scratch_bytes(), b->N);
+    e = hipMalloc(&b->d_scratch, sizeof(float2) * (size_t)b->N * b->scratch_T);
+  }
   if (e != hipSuccess) {
     xl_last_hip_error = e;
-    XL_LOG_ERR("xlating_spectrum_bank_create: %s", hipGetErrorString(e));
+    XL_LOG_ERR("%s: %s", who, hipGetErrorString(e));
     rc = xl_errno_of_last_hip_error();
     xlating_spectrum_bank_destroy(b);
     return rc;
   }
   *out = b;
   return 0;
+}
+
+extern "C" int xlating_spectrum_bank_create(int width, int format, xlating_spectrum_bank **out) {
+  return xl_bank_create_cap(width, XLATING_SPECTRUM_MAX_WIDTH, format, out, "xlating_spectrum_bank_create");
+}
+
+extern "C" int xlating_spectrum_bank_create_wide(int width, int format, xlating_spectrum_bank **out) {
+  return xl_bank_create_cap(width, XLATING_SPECTRUM_MAX_WIDE_WIDTH, format, out, "xlating_spectrum_bank_create_wide");
 }
 
 extern "C" int xlating_spectrum_bank_add(xlating_spectrum_bank *b, uint32_t sampling_rate) {
@@ -451,6 +511,7 @@ extern "C" void xlating_spectrum_bank_destroy(xlating_spectrum_bank *b) {
   if (b->d_px) (void)hipFree(b->d_px);
   if (b->d_carry) (void)hipFree(b->d_carry);
   if (b->d_max) (void)hipFree(b->d_max);
+  if (b->d_scratch) (void)hipFree(b->d_scratch);
   xl_spec_setup_free(b);
   if (b->last) (void)hipEventDestroy(b->last);
   if (b->own) (void)hipStreamDestroy(b->own);

@@ -53,4 +53,26 @@ int xl_bank_carry(const XlBankCarry *ops, uint32_t n, void *carry, uint32_t W, u
 // Rows list[0 .. nrows) (global row slots, device): 10 log10f, half swap, pixel of row i to db[i * W ..] / px[i * W ..]; clears the maxima.
 int xl_bank_finish(const uint32_t *list, uint32_t nrows, uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, hipStream_t st);
 
+// ---- widths above XL_SPEC_MAX_W (xl_spectrum_bank_wide.hip; the rules are xl_spectrum_wide_plan.h's and xl_spectrum_bank_plan.h's)
+// One chunk of a round's ragged transform list through the two-level transform: transforms t0 .. t0 + Tc - 1 of the round's a.T, transform
+// t0 + t in slot t of `scratch` ([transform][k1][j2], N float2 each; Tc at most what it holds).  Two launches (plain) or three
+// (Bluestein), stream-ordered.  Bins are left as XlSpecWideArgs says: a plain width's bin k1 + N1 k2 at position k1 * N2 + k2 of its row slot.
+struct XlBankWideArgs {
+  XlBankArgs a;        // tw: the N-point table (the twiddles between the two levels); bspec: Bluestein, in [k1][k2] order
+  float2 *scratch;
+  const float2 *tw1;   // N1-point twiddles
+  const float2 *tw2;   // N2-point twiddles
+  uint32_t N, N1, N2;
+  uint32_t t0, Tc;
+};
+int xl_bankw_launch(const XlBankWideArgs &w, bool bluestein, int fmt, hipStream_t st);
+static inline unsigned xl_bankw_passes(bool bluestein) { return bluestein ? 3u : 2u; }  // launches of one xl_bankw_launch
+
+// xl_bank_carry on a grid over (stream, piece of XL_BANKW_CARRY_PIECE samples of the carry)
+int xl_bankw_carry(const XlBankCarry *ops, uint32_t n, void *carry, uint32_t W, uint32_t ssz, bool save, hipStream_t st);
+
+// xl_bank_finish with the wide object's arithmetic (xl_specw_finish's: permuted for a plain width, the correctly rounded log10f)
+int xl_bankw_finish(const uint32_t *list, uint32_t nrows, uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t N1, uint32_t N2,
+                    bool permuted, hipStream_t st);
+
 #endif

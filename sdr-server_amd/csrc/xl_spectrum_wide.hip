@@ -16,19 +16,15 @@
 // FFT_N2, conj(. Bs) (Bs stored in [k1][k2] order), FFT_N2, times w_N^(k1 m2) without leaving LDS and writes its row back in place; a last
 // column pass does the N1-point transforms, X[m] = c[m] conj(conv'[m]), the power of bins m < W and the row maximum, in natural bin
 // order and in runs of `pack`.  Three launches.
-// Every piece of the transforms' arithmetic is xl_spectrum_dev.h's (xl_fft_lds, xl_sample via xl_spec_point, xl_spec_blue_mid,
+// What a workgroup does in each pass is xl_spectrum_wide_dev.h's (shared with the bank's ragged kernels, xl_spectrum_bank_wide.hip); every
+// piece of its arithmetic is xl_spectrum_dev.h's (xl_fft_lds, xl_sample via xl_spec_point, xl_spec_blue_mid,
 // xl_spec_power, the atomicMax on the float's bits); tables are made on the host in double.  The transforms are SCALAR FP32 ONLY, no
 // matrix instruction, no sin / cos: the file is compiled with SPEC_FLAGS and -ffp-contract=off like xl_spectrum.hip.  The finishing pass
 // alone takes one double log10 per bin and row (xl_specw_db).
 #include "xl_spectrum.h"
-#include "xl_spectrum_dev.h"
-#include "xl_spectrum_wide_plan.h"
+#include "xl_spectrum_wide_dev.h"
 
 namespace {
-
-constexpr uint32_t PACK_POINTS = XL_SPECW_PACK_POINTS;
-constexpr uint32_t COL_NT = 256;  // xl_spec_nt of a 4096-point pack
-constexpr uint32_t xl_specw_row_points(uint32_t N2) { return xl_spec_b(N2) * N2; }
 
 // the launch's transform t: its first sample relative to a.in, and its row's ring slot
 XL_DEV void xl_specw_where(const XlSpecArgs &a, const uint32_t t, uint32_t &off, uint32_t &slot) {
@@ -38,103 +34,40 @@ XL_DEV void xl_specw_where(const XlSpecArgs &a, const uint32_t t, uint32_t &off,
   slot = (uint32_t)(row % a.cap);
 }
 
-// ------------------------------------------------------------------------------------------------------------ column pass, input side
+// The three passes: the single object's prologue (transform t of the launch is transform g0 + t of the one stream, in slot t of the
+// scratch) and xl_spectrum_wide_dev.h's body.
 template <uint32_t N1, uint32_t N2, int FMT, bool BLUE>
-__global__ void __launch_bounds__(COL_NT) xl_specw_col_in_kernel(const XlSpecWideArgs w) {
-  constexpr uint32_t B = PACK_POINTS / N1, N = N1 * N2, PB = N2 / B;  // PB: packs per transform
-  static_assert(xl_spec_b(N1) == B && xl_spec_nt(N1) == COL_NT, "a column pack is an xl_fft_lds pack");
-  __shared__ v2f buf[PACK_POINTS];
-  const uint32_t tid = threadIdx.x;
+__global__ void __launch_bounds__(XL_SPECW_COL_NT) xl_specw_col_in_kernel(const XlSpecWideArgs w) {
+  constexpr uint32_t B = xl_specw_pack(N1), N = N1 * N2, PB = N2 / B;  // PB: packs per transform
+  __shared__ v2f buf[XL_SPECW_PACK_POINTS];
   const uint32_t t = blockIdx.x / PB, j0 = (blockIdx.x % PB) * B;
   uint32_t off, slot;
   xl_specw_where(w.a, t, off, slot);
-  for (uint32_t q = tid; q < PACK_POINTS; q += COL_NT) {
-    const uint32_t c = q % B, n1 = q / B, n = n1 * N2 + j0 + c;
-    v2f v = (v2f){0.0f, 0.0f};
-    if (n < w.a.W) v = xl_spec_point<FMT, BLUE>(w.a.in, off, n, w.a.chirp);
-    buf[c * N1 + n1] = v;
-  }
-  __syncthreads();
-  xl_fft_lds<N1, B, COL_NT>(buf, w.tw1, tid);
-  float2 *out = w.scratch + (size_t)t * N;
-  for (uint32_t q = tid; q < PACK_POINTS; q += COL_NT) {
-    const uint32_t c = q % B, k1 = q / B, j2 = j0 + c;
-    const float2 tw = w.a.tw[j2 * k1];
-    const v2f v = cmul(buf[c * N1 + k1], (v2f){tw.x, tw.y});
-    out[k1 * N2 + j2] = make_float2(v.x, v.y);
-  }
+  xl_specw_col_in<N1, N2, FMT, BLUE>(buf, w.a.in, off, j0, w.scratch + (size_t)t * N, w.a.W, w.a.chirp, w.tw1, w.a.tw);
 }
 
-// ------------------------------------------------------------------------------------------------------------ row pass
 template <uint32_t N1, uint32_t N2, bool BLUE>
 __global__ void __launch_bounds__(xl_spec_nt(N2)) xl_specw_row_kernel(const XlSpecWideArgs w) {
-  constexpr uint32_t B = xl_spec_b(N2), NT = xl_spec_nt(N2), P = B * N2, N = N1 * N2;
-  static_assert(N1 % B == 0, "a pack of rows stays inside one transform");
-  __shared__ v2f buf[P];
-  const uint32_t tid = threadIdx.x;
+  constexpr uint32_t B = xl_spec_b(N2), N = N1 * N2;
+  __shared__ v2f buf[B * N2];
   const uint32_t r0 = blockIdx.x * B;  // first row of the pack among the launch's T * N1 rows
   const uint32_t t = r0 / N1, k10 = r0 % N1;
-  float2 *row = w.scratch + (size_t)t * N + (size_t)k10 * N2;  // B rows, contiguous
-  for (uint32_t q = tid; q < P; q += NT) {
-    const float2 v = row[q];
-    buf[q] = (v2f){v.x, v.y};
-  }
-  __syncthreads();
-  xl_fft_lds<N2, B, NT>(buf, w.tw2, tid);
-  if constexpr (BLUE) {
-    const float2 *bs = w.a.bspec + (size_t)k10 * N2;
-    for (uint32_t q = tid; q < P; q += NT) buf[q] = xl_spec_blue_mid(buf[q], bs[q]);
-    __syncthreads();
-    xl_fft_lds<N2, B, NT>(buf, w.tw2, tid);
-    for (uint32_t q = tid; q < P; q += NT) {
-      const uint32_t k1 = k10 + q / N2, m2 = q % N2;
-      const float2 tw = w.a.tw[k1 * m2];
-      const v2f v = cmul(buf[q], (v2f){tw.x, tw.y});
-      row[q] = make_float2(v.x, v.y);
-    }
-  } else {
+  xl_specw_row<N1, N2, BLUE>(buf, w.scratch + (size_t)t * N + (size_t)k10 * N2, k10, w.a.bspec, w.tw2, w.a.tw, w.a.norm, [&]() {
     uint32_t off, slot;
     xl_specw_where(w.a, t, off, slot);
-    uint32_t *mx = w.a.rowmax + (size_t)slot * w.a.W + (size_t)k10 * N2;  // (plain: W = N)
-    for (uint32_t q = tid; q < P; q += NT) {
-      const float pw = xl_spec_power<false>(buf[q], (v2f){1.0f, 0.0f}, w.a.norm);
-      atomicMax(mx + q, __float_as_uint(pw));
-    }
-  }
+    return w.a.rowmax + (size_t)slot * w.a.W + (size_t)k10 * N2;  // (plain: W = N)
+  });
 }
 
-// ------------------------------------------------------------------------------------------------------------ column pass, output side
 template <uint32_t N1, uint32_t N2>
-__global__ void __launch_bounds__(COL_NT) xl_specw_col_out_kernel(const XlSpecWideArgs w) {
-  constexpr uint32_t B = PACK_POINTS / N1, N = N1 * N2, PB = N2 / B;
-  __shared__ v2f buf[PACK_POINTS];
-  const uint32_t tid = threadIdx.x;
+__global__ void __launch_bounds__(XL_SPECW_COL_NT) xl_specw_col_out_kernel(const XlSpecWideArgs w) {
+  constexpr uint32_t B = xl_specw_pack(N1), N = N1 * N2, PB = N2 / B;
+  __shared__ v2f buf[XL_SPECW_PACK_POINTS];
   const uint32_t t = blockIdx.x / PB, m0 = (blockIdx.x % PB) * B;
   uint32_t off, slot;
   xl_specw_where(w.a, t, off, slot);
-  const float2 *in = w.scratch + (size_t)t * N;
-  for (uint32_t q = tid; q < PACK_POINTS; q += COL_NT) {
-    const uint32_t c = q % B, k1 = q / B;
-    const float2 v = in[k1 * N2 + m0 + c];
-    buf[c * N1 + k1] = (v2f){v.x, v.y};
-  }
-  __syncthreads();
-  xl_fft_lds<N1, B, COL_NT>(buf, w.tw1, tid);
-  uint32_t *mx = w.a.rowmax + (size_t)slot * w.a.W;
-  for (uint32_t q = tid; q < PACK_POINTS; q += COL_NT) {
-    const uint32_t c = q % B, m1 = q / B, m = m1 * N2 + m0 + c;
-    if (m < w.a.W) {
-      const float2 cj = w.a.chirp[m];
-      const float pw = xl_spec_power<true>(buf[c * N1 + m1], (v2f){cj.x, cj.y}, w.a.norm);
-      atomicMax(mx + m, __float_as_uint(pw));
-    }
-  }
+  xl_specw_col_out<N1, N2>(buf, w.scratch + (size_t)t * N, m0, w.a.rowmax + (size_t)slot * w.a.W, w.a.W, w.a.chirp, w.tw1, w.a.norm);
 }
-
-// spectrogram.c:150: 10 * log10f(v) with the log10f the reference gets from its libm, the correctly rounded one.  The device's log10f is
-// an ulp off here and there -- at v = 1e-20f, the floor every bin of a silent input sits on, it gives -20.000002 and so pixel 54 where
-// the reference writes 55 -- so this one value per bin and row is taken in double and rounded once; the product is the float one.
-XL_DEV float xl_specw_db(const float v) { return 10.0f * (float)log10((double)v); }
 
 // the finishing pass of a wide object's rows: xl_spec_finish_kernel's, with the row pass's bin order for a plain width (permuted) and
 // xl_specw_db
@@ -143,29 +76,24 @@ __global__ void __launch_bounds__(256) xl_specw_finish_kernel(uint32_t *rowmax, 
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= W) return;
   const size_t s = (size_t)((r0 + (int64_t)blockIdx.y) % cap) * W;
-  const uint32_t from = permuted ? xl_specw_col_pos(N1, N2, W, j) : xl_spec_shift_src(j, W);
-  const float v = __uint_as_float(rowmax[s + from]);
-  rowmax[s + from] = 0u;  // (either order is a permutation of the slot: every bin is read and cleared by exactly one thread)
-  const float d = xl_specw_db(v);
-  db[s + j] = d;
-  px[s + j] = xl_spec_pixel(d);
+  xl_specw_finish_col(rowmax, db, px, s, permuted ? xl_specw_col_pos(N1, N2, W, j) : xl_spec_shift_src(j, W), s, j);
 }
 
 // ------------------------------------------------------------------------------------------------------------ launches
 template <uint32_t N, bool BLUE>
 int xl_specw_launch_n(const XlSpecWideArgs &w, const int fmt, hipStream_t st) {
-  constexpr uint32_t N2 = XL_SPECW_N2(N), N1 = N / N2, B = PACK_POINTS / N1;
+  constexpr uint32_t N2 = XL_SPECW_N2(N), N1 = N / N2, B = xl_specw_pack(N1);
   static_assert(B >= 16 && N2 % B == 0 && N1 * N2 == N, "the split");
   if (w.N1 != N1 || w.N2 != N2) return (int)hipErrorInvalidValue;  // (the plan and the kernels disagree)
-  const dim3 col_grid(w.a.T * (N2 / B)), row_grid(w.a.T * (N1 / xl_spec_b(N2)));
+  const dim3 col_grid(w.a.T * (N2 / B)), row_grid(w.a.T * (N1 / xl_spec_b(N2))), col_nt(XL_SPECW_COL_NT);
   if (fmt == XLF_CU8)
-    hipLaunchKernelGGL((xl_specw_col_in_kernel<N1, N2, XLF_CU8, BLUE>), col_grid, dim3(COL_NT), 0, st, w);
+    hipLaunchKernelGGL((xl_specw_col_in_kernel<N1, N2, XLF_CU8, BLUE>), col_grid, col_nt, 0, st, w);
   else if (fmt == XLF_CS16)
-    hipLaunchKernelGGL((xl_specw_col_in_kernel<N1, N2, XLF_CS16, BLUE>), col_grid, dim3(COL_NT), 0, st, w);
+    hipLaunchKernelGGL((xl_specw_col_in_kernel<N1, N2, XLF_CS16, BLUE>), col_grid, col_nt, 0, st, w);
   else
-    hipLaunchKernelGGL((xl_specw_col_in_kernel<N1, N2, XLF_CF32, BLUE>), col_grid, dim3(COL_NT), 0, st, w);
+    hipLaunchKernelGGL((xl_specw_col_in_kernel<N1, N2, XLF_CF32, BLUE>), col_grid, col_nt, 0, st, w);
   hipLaunchKernelGGL((xl_specw_row_kernel<N1, N2, BLUE>), row_grid, dim3(xl_spec_nt(N2)), 0, st, w);
-  if constexpr (BLUE) hipLaunchKernelGGL((xl_specw_col_out_kernel<N1, N2>), col_grid, dim3(COL_NT), 0, st, w);
+  if constexpr (BLUE) hipLaunchKernelGGL((xl_specw_col_out_kernel<N1, N2>), col_grid, col_nt, 0, st, w);
   return (int)hipGetLastError();
 }
 
@@ -173,28 +101,7 @@ int xl_specw_launch_n(const XlSpecWideArgs &w, const int fmt, hipStream_t st) {
 
 int xl_specw_launch(const XlSpecWideArgs &w, bool bluestein, int fmt, hipStream_t st) {
   if (w.a.T == 0) return 0;
-  if (bluestein) {
-    switch (w.N) {
-      case 1u << 15: return xl_specw_launch_n<1u << 15, true>(w, fmt, st);
-      case 1u << 16: return xl_specw_launch_n<1u << 16, true>(w, fmt, st);
-      case 1u << 17: return xl_specw_launch_n<1u << 17, true>(w, fmt, st);
-      case 1u << 18: return xl_specw_launch_n<1u << 18, true>(w, fmt, st);
-      case 1u << 19: return xl_specw_launch_n<1u << 19, true>(w, fmt, st);
-      case 1u << 20: return xl_specw_launch_n<1u << 20, true>(w, fmt, st);
-      case 1u << 21: return xl_specw_launch_n<1u << 21, true>(w, fmt, st);
-    }
-    return (int)hipErrorInvalidValue;
-  }
-  switch (w.N) {
-    case 1u << 14: return xl_specw_launch_n<1u << 14, false>(w, fmt, st);
-    case 1u << 15: return xl_specw_launch_n<1u << 15, false>(w, fmt, st);
-    case 1u << 16: return xl_specw_launch_n<1u << 16, false>(w, fmt, st);
-    case 1u << 17: return xl_specw_launch_n<1u << 17, false>(w, fmt, st);
-    case 1u << 18: return xl_specw_launch_n<1u << 18, false>(w, fmt, st);
-    case 1u << 19: return xl_specw_launch_n<1u << 19, false>(w, fmt, st);
-    case 1u << 20: return xl_specw_launch_n<1u << 20, false>(w, fmt, st);
-  }
-  return (int)hipErrorInvalidValue;
+  return xl_specw_dispatch(w.N, bluestein, [&](auto n, auto blue) { return xl_specw_launch_n<n, blue>(w, fmt, st); });
 }
 
 int xl_specw_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t N1, uint32_t N2, bool permuted, uint32_t cap, int64_t r0,

@@ -7,13 +7,13 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-$ROOT/profiles/r05_kernel_resources.txt}
 W=$(mktemp -d /tmp/xl_kres.XXXX)
 LLVM=/opt/rocm/lib/llvm/bin
-FILES="xl_kernels xl_polyphase xl_mixf32 xl_mixh xl_mixh2 xl_inv8 xl_inv32 xl_spectrum xl_spectrum_bank xl_spectrum_wide xl_resample xl_resample_q15"
+FILES="xl_kernels xl_polyphase xl_mixf32 xl_mixh xl_mixh2 xl_inv8 xl_inv32 xl_spectrum xl_spectrum_bank xl_spectrum_wide xl_spectrum_bank_wide xl_resample xl_resample_q15"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt"
 {
 echo "# kernel resources of sdr-server_amd/csrc/*.hip for gfx950 (hipcc $FLAGS), from llvm-readelf --notes of the code objects"
 echo "# columns: vgpr agpr sgpr sgpr_spill vgpr_spill lds_bytes scratch_bytes  kernel"
 for f in $FILES; do
-  case $f in xl_mixh|xl_mixh2|xl_mixf32|xl_spectrum|xl_spectrum_bank|xl_spectrum_wide|xl_resample|xl_resample_q15) X="-fno-slp-vectorize";; *) X="";; esac   # (csrc/Makefile: MIX_FLAGS, SPEC_FLAGS, RESAMPLE_FLAGS, RESAMPLE_Q15_FLAGS)
+  case $f in xl_mixh|xl_mixh2|xl_mixf32|xl_spectrum|xl_spectrum_bank|xl_spectrum_wide|xl_spectrum_bank_wide|xl_resample|xl_resample_q15) X="-fno-slp-vectorize";; *) X="";; esac   # (csrc/Makefile: MIX_FLAGS, SPEC_FLAGS, RESAMPLE_FLAGS, RESAMPLE_Q15_FLAGS)
   hipcc $FLAGS $X --cuda-device-only -c $ROOT/sdr-server_amd/csrc/$f.hip -o $W/$f.co
   $LLVM/clang-offload-bundler --unbundle --type=o --input=$W/$f.co --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$W/$f.elf
   echo "## $f.hip"

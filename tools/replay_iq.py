@@ -11,7 +11,8 @@ src/sdr/*_device.c, src/tcp_server.c:257-271).
 Every --client CENTER_HZ:RATE_HZ goes through the 15-byte wire request, the admission rules and
 xlating_wire_add_client, and ends up as <out>/<id>.cf32[.gz].  With --waterfall-width W every admitted client also gets a stream of a
 spectrum bank (include/xlating_spectrum.h) at its own rate, fed from the engine's device rows after every block, and <out>/<id>.png:
-the 8-bit gray waterfall sdr_spectrogram makes from that client's .cf32 (-w W -s RATE -d cf32).
+the 8-bit gray waterfall sdr_spectrogram makes from that client's .cf32 (-w W -s RATE -d cf32; W above 8192: the bank's wide form, and
+sdr_spectrogram -W).  A client slower than W gets no waterfall.
 With --any-rate a client whose RATE_HZ does not divide the band rate is admitted too (xlating_wire_admit_any_rate): the engine takes it
 to band_rate / D, one resampler bank (include/xlating_resample.h) from there to RATE_HZ by L / M, and its .cf32 and waterfall are at
 RATE_HZ like everybody's.
@@ -59,7 +60,8 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
     if q15 and gzip:
         raise ValueError("gzip is the sinks library's, which writes the cf32 family: not with variant q15")
     os.makedirs(out_dir, exist_ok=True)
-    bank = xl.SpectrumBank(waterfall_width, "cs16" if q15 else "cf32") if waterfall_width else None
+    # (a width above 8192 is the bank's wide form: xlating_spectrum_bank_create_wide)
+    bank = xl.SpectrumBank(waterfall_width, "cs16" if q15 else "cf32", wide=waterfall_width > 8192) if waterfall_width else None
     streams, rows, samples = {}, {}, {}  # client id -> bank stream, its rows so far, its output samples so far
     eng = xl.BatchEngine(band_rate, fmt, buffer_size)
     if q15:

@@ -13,7 +13,14 @@
              for before the next call, which reuses the device rows), alternating in one process; the feed's device time and the
              host time of the Python gather of the 1024 output pointers are reported beside them.
 
-usage: python tools/spectrum_bank_bench.py [--reps N] [--skip-engine] [--skip-loop] [--out FILE]
+  --wide     (alone) the wide bank: 1024 streams x 48 000 Hz at W = 48 000 (1 Hz per bin; Bluestein at N = 131072, F = 1), fed the
+             headline call's 24 966 samples per stream, against a loop over 1024 xlating_spectrum_create_wide objects in the same
+             process.  Every other feed completes no transform (the samples go to the carries); the others run 1024 transforms and
+             complete 1024 rows: the two kinds are reported apart, each with the bank's launches and copies per feed.  (The loop's
+             objects are created with a scratch of one transform, XL_EXP_SPEC_SCRATCH = 1 MiB -- a feed of theirs never runs more --
+             instead of 64 MiB each; the bank keeps its default scratch and staging.)
+
+usage: python tools/spectrum_bank_bench.py [--reps N] [--skip-engine] [--skip-loop] [--wide] [--out FILE]
 """
 import argparse
 import json
@@ -95,6 +102,77 @@ def feeds_bench(name, W, rates, counts, reps, warm=3, with_loop=True):
     return out
 
 
+def wide_bench(reps, warm=2, n=1024, W=48000, rate=48000, count=24966, with_loop=True):
+    """-> the --wide case: per kind of feed ("quiet": no transform completes, "rows": every stream completes a row) host and device
+    time of the bank's feed and of the loop over single wide objects, and the bank's (launches, copies)"""
+    import torch
+
+    d = torch.randn(2 * n * count, device="cuda", dtype=torch.float32) * 0.3
+    ptrs = [d.data_ptr() + 8 * i * count for i in range(n)]
+    counts = [count] * n
+    st = torch.cuda.current_stream()
+    bank = xl.SpectrumBank(W, "cf32", wide=True)
+    ids = [bank.add(rate) for _ in range(n)]
+    objs = []
+    if with_loop:
+        N = 1
+        while N < 2 * W - 1:
+            N *= 2
+        os.environ["XL_EXP_SPEC_CHUNK"] = "65536"
+        os.environ["XL_EXP_SPEC_SCRATCH"] = str(8 * N)
+        objs = [xl.Spectrum(rate, W, "cf32", wide=True) for _ in range(n)]
+        os.environ.pop("XL_EXP_SPEC_CHUNK")
+        os.environ.pop("XL_EXP_SPEC_SCRATCH")
+    S = xl.spectrum_lib()
+    res = {k: {w: {"host_s": [], "device_s": []} for w in ("bank", "loop")} for k in ("quiet", "rows")}
+    ops = {}
+    for k in range(2 * (reps + warm)):
+        kind, first = None, {}  # this repetition's kind of feed (decided by the bank's feed, which runs first) and first stream's rows
+        for which in ("bank", "loop") if with_loop else ("bank",):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(st)
+            t0 = time.perf_counter()
+            if which == "bank":
+                bank.feed(ids, ptrs, counts, st.cuda_stream)
+            else:
+                assert kind is not None
+                for o, p in zip(objs, ptrs):
+                    S.xlating_spectrum_feed_device(o.h, p, count, st.cuda_stream)
+            t1 = time.perf_counter()
+            b.record(st)
+            b.synchronize()
+            if which == "bank":
+                rows = sum(bank.rows_pending(i) for i in ids)
+                assert rows in (0, n)
+                kind = "rows" if rows else "quiet"
+                ops[kind] = bank.last_feed_ops()
+                first[which] = bank.take_rows(ids[0])
+                for i in ids[1:] if rows else []:
+                    bank.take_rows(i)
+            else:  # (the loop's feed of the same samples: the same kind, and the same first row)
+                first[which] = objs[0].take_rows()
+                assert first[which][0].shape[0] == (1 if kind == "rows" else 0)
+                for o in objs[1:] if kind == "rows" else []:
+                    o.take_rows(1)
+                assert all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(first["bank"], first["loop"]))
+            if k >= 2 * warm:
+                res[kind][which]["host_s"].append(t1 - t0)
+                res[kind][which]["device_s"].append(a.elapsed_time(b) * 1e-3)
+    bank.close()
+    for o in objs:
+        o.close()
+    out = {"case": f"wide: {n} x {rate} Hz, W {W}", "streams": n, "W": W, "samples_per_feed": n * count, "transform": "two-level bluestein"}
+    for kind in res:
+        out[kind] = {"bank_last_feed_ops": ops.get(kind)}
+        for which in res[kind]:
+            if res[kind][which]["host_s"]:
+                out[kind][which] = {m: stats(v) for m, v in res[kind][which].items()}
+        if with_loop:
+            out[kind]["host_speedup"] = out[kind]["loop"]["host_s"]["median"] / out[kind]["bank"]["host_s"]["median"]
+            out[kind]["device_speedup"] = out[kind]["loop"]["device_s"]["median"] / out[kind]["bank"]["device_s"]["median"]
+    return out
+
+
 def engine_bench(reps, W=256, warm=4):
     import torch
 
@@ -152,10 +230,18 @@ def main():
     ap.add_argument("--reps", type=int, default=12)
     ap.add_argument("--skip-engine", action="store_true")
     ap.add_argument("--skip-loop", action="store_true")
+    ap.add_argument("--wide", action="store_true", help="the wide bank's case alone: 1024 streams of 48 000 Hz at W = 48 000")
     ap.add_argument("--out")
     a = ap.parse_args()
     if "no usable device" in xl.device_info():
         raise SystemExit("spectrum_bank_bench needs a HIP device: " + xl.device_info())
+    if a.wide:
+        line = json.dumps({"device": xl.device_info(), "wide": wide_bench(a.reps, with_loop=not a.skip_loop)})
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     res = {"device": xl.device_info(), "feeds": []}
     cases = [("1024 x 48 kHz, W 256", 256, [48000] * 1024, [24966] * 1024),
              ("64 of two rates, W 256", 256, [48000, 96000] * 32, [24966, 49932] * 32),
