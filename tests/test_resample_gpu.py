@@ -2,7 +2,9 @@
 restatement (tests/resample_ref.py: |y32 - y64| <= gamma_Q S + Q 2^-126 per component, no measured tolerance), the output count per
 feed, bit-identity under any split of the input and in any company of streams, table sharing, membership, the output rows, the
 tables and the carries when their arrays grow and when the ring of pinned tables wraps, the bank behind the batch engine at the rates
-the admission rule picks, a spectrum bank fed from its device rows, and tools/replay_iq.py --any-rate."""
+the admission rule picks, a spectrum bank fed from its device rows, and tools/replay_iq.py --any-rate.
+The streams here have M / L <= 3: every tile's window is staged in LDS.  The windows read in place, the span limit itself and the
+splits that move a tile across it are tests/test_resample_edges_gpu.py's (streams from tests/resample_edges.py)."""
 import errno
 import importlib.util
 import math

@@ -3,7 +3,10 @@ np.array_equal against the integer restatement (tests/resample_q15_ref.py): no t
 filters and the edges of the tiling (256-output tiles, a 4096-sample LDS span, 1024-sample carry slots, a 4096-entry LDS tap table)
 under two splits of the input, saturation, the boundary between the 32-bit and the 64-bit sums, many streams in one feed, the bank's
 housekeeping, the bank behind the batch engine's XL_MODE_Q15 rows, a cs16 spectrum bank fed from its device rows, and
-tools/replay_iq.py --variant q15 --any-rate."""
+tools/replay_iq.py --variant q15 --any-rate.
+One stream here ("1/40", L = 1) reads its window in place.  The span limit itself, M % L != 0 in place, a tap table and a window both
+in place, 64-bit sums over an in-place window and M = 2^31 - 1 are tests/test_resample_edges_gpu.py's (streams from
+tests/resample_edges.py)."""
 import errno
 import functools
 import importlib.util
