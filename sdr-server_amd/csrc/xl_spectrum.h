@@ -17,7 +17,8 @@
 // (g / F) * sr + (g % F) * W).  `in` holds stream samples base .. : every transform of the launch lies inside it, so that the relative
 // offsets fit 32 bits (the core cuts spans to XL_SPEC_SPAN_MAX samples).  Per bin, the power's maximum over a row's transforms goes
 // to rowmax[(row % cap) * W + bin] by an unsigned atomicMax on the float's bits (every power is positive, so the bit order is the
-// value order, and max is exact: the result does not depend on the work split or on arrival order).
+// value order, and max is exact: the result does not depend on the work split or on arrival order; a NaN power enters as 0u and so
+// loses, as against the reference's fmaxf: xl_spec_max_bits).
 struct XlSpecArgs {
   const void *in;
   int64_t base;
@@ -54,7 +55,7 @@ struct XlSpecWideArgs {
 };
 int xl_specw_launch(const XlSpecWideArgs &w, bool bluestein, int fmt, hipStream_t st);
 // xl_spec_finish for a wide object's rows: permuted (a plain width): column j reads its bin (the half swap first) from the row pass's
-// position; the dB is 10 * the correctly rounded log10f (xl_spectrum_wide_dev.h: xl_specw_db)
+// position; the dB is xl_spec_db, as in xl_spec_finish
 int xl_specw_finish(uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t N1, uint32_t N2, bool permuted, uint32_t cap, int64_t r0,
                     uint32_t nrows, hipStream_t st);
 

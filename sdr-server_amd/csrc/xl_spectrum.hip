@@ -10,7 +10,8 @@
 // Packing: a workgroup holds B = min(256, max(1, 4096 / N)) transforms (P = B N points, P / 16 threads: every thread does 4 radix-4 or
 // 8 radix-2 butterflies per pass), so a 64-point transform is not a workgroup on its own.
 // Row maximum: per bin, one thread walks the workgroup's transforms in order and keeps a running maximum per row, flushed by an
-// unsigned atomicMax on the float's bits whenever the row changes and at the end (powers are positive: bit order = value order).
+// unsigned atomicMax on the float's bits whenever the row changes and at the end (powers are positive: bit order = value order;
+// a NaN power enters as 0u and so loses, as against the reference's fmaxf: xl_spec_max_bits).
 // SCALAR FP32 ONLY: compiled without the SLP vectoriser (Makefile: SPEC_FLAGS) -- these launches may share a chip, and a process,
 // with the engine's matrix-core launches, beside which packed FP32 loses lanes (xl_mixh.hip).  No matrix instructions.
 #include "xl_spectrum.h"

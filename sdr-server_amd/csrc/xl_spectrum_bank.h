@@ -71,7 +71,7 @@ static inline unsigned xl_bankw_passes(bool bluestein) { return bluestein ? 3u :
 // xl_bank_carry on a grid over (stream, piece of XL_BANKW_CARRY_PIECE samples of the carry)
 int xl_bankw_carry(const XlBankCarry *ops, uint32_t n, void *carry, uint32_t W, uint32_t ssz, bool save, hipStream_t st);
 
-// xl_bank_finish with the wide object's arithmetic (xl_specw_finish's: permuted for a plain width, the correctly rounded log10f)
+// xl_bank_finish with the wide object's arithmetic (xl_specw_finish's: permuted for a plain width)
 int xl_bankw_finish(const uint32_t *list, uint32_t nrows, uint32_t *rowmax, float *db, uint8_t *px, uint32_t W, uint32_t N1, uint32_t N2,
                     bool permuted, hipStream_t st);
 

@@ -8,7 +8,8 @@
 // xl_ragged_find as in xl_bank_kernel, and the run gives the source pointer, the sample offset and the row slot.  It uses slot t of the
 // scratch.  A chunk may end inside a run or between two streams' runs: a transform's place in the scratch depends on t alone.
 // SCALAR FP32 ONLY, no matrix instructions (Makefile: SPEC_FLAGS), as xl_spectrum_bank.hip: these launches run behind and beside the
-// engine's matrix-core launches.  The finishing pass takes one double log10 per bin and row (xl_specw_db), as the single object's.
+// engine's matrix-core launches.  The finishing pass takes one double log10 per bin and row (xl_spec_db), as every finishing pass of
+// the family.
 #include "xl_ragged.h"
 #include "xl_spectrum_bank.h"
 #include "xl_spectrum_bank_plan.h"
@@ -79,7 +80,7 @@ __global__ void __launch_bounds__(256) xl_bankw_carry_kernel(const XlBankCarry *
 }
 
 // xl_bank_finish_kernel's walk over a list of row slots with the wide object's arithmetic: a plain width's bins through the row pass's
-// order (xl_specw_col_pos), xl_specw_db; row i of the list goes to row i of the staging buffers
+// order (xl_specw_col_pos); row i of the list goes to row i of the staging buffers
 __global__ void __launch_bounds__(256) xl_bankw_finish_kernel(const uint32_t *__restrict__ list, uint32_t *rowmax, float *db, uint8_t *px,
                                                               const uint32_t W, const uint32_t N1, const uint32_t N2, const bool permuted) {
   const uint32_t j = blockIdx.y * 256u + threadIdx.x;

@@ -107,11 +107,16 @@ XL_DEV float xl_spec_power(v2f X, const v2f cj, const float norm) {
   return re * re + im * im + 1e-20f;
 }
 
+// The bits of a power as they enter a row maximum (spectrogram.c:148: fmaxf(temp[j], power), which a NaN power loses against any number):
+// 0u for a NaN, whose own bits (0x7FC.., 0xFFC..) would beat every power in the unsigned order; the float's bits otherwise.  A row
+// whose every transform holds a NaN keeps the cleared maximum 0u: dB -Inf, pixel 0.
+XL_DEV uint32_t xl_spec_max_bits(const float pw) { return pw != pw ? 0u : __float_as_uint(pw); }
+
 // A workgroup's pack of B = xl_spec_b(N) transforms, after the kernel's prologue has written for each: off[b], its first sample as an
 // element index into src(b), and slot[b], the row slot its maxima go to (~0u from the first b past the launch's transforms).  Load,
 // transform, power; then per bin one thread walks the pack in order with a running maximum, flushed by an unsigned atomicMax on the
-// float's bits whenever the slot changes and at the end.  A slot change is a row or stream change: along a pack the transforms of one
-// row of one stream are consecutive.  a: XlSpecArgs or XlBankArgs (W, rowmax, tw, chirp, bspec, norm).
+// power's bits (xl_spec_max_bits) whenever the slot changes and at the end.  A slot change is a row or stream change: along a pack the
+// transforms of one row of one stream are consecutive.  a: XlSpecArgs or XlBankArgs (W, rowmax, tw, chirp, bspec, norm).
 template <uint32_t N, int FMT, bool BLUE, class Args, class Src>
 XL_DEV void xl_spec_pack(v2f *buf, const uint32_t *off, const uint32_t *slot, const Args &a, const Src src) {
   constexpr uint32_t B = xl_spec_b(N);
@@ -143,7 +148,7 @@ XL_DEV void xl_spec_pack(v2f *buf, const uint32_t *off, const uint32_t *slot, co
         cur = sl;
         m = 0u;
       }
-      const uint32_t bits = __float_as_uint(pw);
+      const uint32_t bits = xl_spec_max_bits(pw);
       m = bits > m ? bits : m;
     }
     if (cur != ~0u) atomicMax(a.rowmax + (size_t)cur * a.W + j, m);
@@ -156,8 +161,11 @@ XL_DEV uint32_t xl_spec_shift_src(const uint32_t j, const uint32_t W) {
   return j < half ? j + half : (j < 2u * half ? j - half : j);
 }
 
-// spectrogram.c:150 (10 log10f) and png_util.c:53-63 (the pixel) of a row maximum
-XL_DEV float xl_spec_db(const float v) { return 10.0f * log10f(v); }
+// spectrogram.c:150 and png_util.c:53-63 (the pixel) of a row maximum.  The dB is 10 * log10f(v) with the log10f the reference gets from
+// its libm, the correctly rounded one.  The device's log10f is an ulp off here and there -- at v = 1e-20f, the floor every bin of a silent
+// input sits on, it gives -20.000002 and so pixel 54 where the reference writes 55 -- so this one value per bin and finished row is taken
+// in double and rounded once; the product is the float one.  The one definition: the narrow, bank, wide and wide-bank finishing passes.
+XL_DEV float xl_spec_db(const float v) { return 10.0f * (float)log10((double)v); }
 XL_DEV uint8_t xl_spec_pixel(const float d) {
   const float f = d + 255.0f;
   const int pixel = f >= 255.0f ? 255 : (f > 0.0f ? (int)f : 0);

@@ -20,7 +20,7 @@
 // piece of its arithmetic is xl_spectrum_dev.h's (xl_fft_lds, xl_sample via xl_spec_point, xl_spec_blue_mid,
 // xl_spec_power, the atomicMax on the float's bits); tables are made on the host in double.  The transforms are SCALAR FP32 ONLY, no
 // matrix instruction, no sin / cos: the file is compiled with SPEC_FLAGS and -ffp-contract=off like xl_spectrum.hip.  The finishing pass
-// alone takes one double log10 per bin and row (xl_specw_db).
+// takes one double log10 per bin and row (xl_spec_db), as every finishing pass of the family.
 #include "xl_spectrum.h"
 #include "xl_spectrum_wide_dev.h"
 
@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(XL_SPECW_COL_NT) xl_specw_col_out_kernel(const
 }
 
 // the finishing pass of a wide object's rows: xl_spec_finish_kernel's, with the row pass's bin order for a plain width (permuted) and
-// xl_specw_db
+// nothing else (xl_spec_db and xl_spec_pixel as there)
 __global__ void __launch_bounds__(256) xl_specw_finish_kernel(uint32_t *rowmax, float *db, uint8_t *px, const uint32_t W, const uint32_t N1,
                                                               const uint32_t N2, const bool permuted, const uint32_t cap, const int64_t r0) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;

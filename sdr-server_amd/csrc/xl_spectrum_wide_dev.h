@@ -3,7 +3,7 @@
 // (xl_spectrum_bank_wide.hip), as xl_spectrum_dev.h is shared by the one-workgroup kernels.  A kernel of either file is its LDS, its own
 // prologue -- transform t of the launch: which source buffer, which sample offset, which row slot, which slot of the scratch -- and one
 // call; both files are compiled with the same flags (Makefile: SPEC_FLAGS, -ffp-contract=off): a row of the wide bank is bit for bit the
-// row of the single wide object.  Also here: the finishing of one column of a wide row (xl_specw_finish_col, with xl_specw_db) and the
+// row of the single wide object.  Also here: the finishing of one column of a wide row (xl_specw_finish_col, with xl_spec_db) and the
 // list of the transform lengths that have kernels (xl_specw_dispatch).  See xl_spectrum_wide.hip's header for the method.
 #ifndef XL_SPECTRUM_WIDE_DEV_H_
 #define XL_SPECTRUM_WIDE_DEV_H_
@@ -70,7 +70,7 @@ XL_DEV void xl_specw_row(v2f *buf, float2 *row, const uint32_t k10, const float2
     uint32_t *m = mx();
     for (uint32_t q = tid; q < P; q += NT) {
       const float pw = xl_spec_power<false>(buf[q], (v2f){1.0f, 0.0f}, norm);
-      atomicMax(m + q, __float_as_uint(pw));
+      atomicMax(m + q, xl_spec_max_bits(pw));
     }
   }
 }
@@ -94,15 +94,10 @@ XL_DEV void xl_specw_col_out(v2f *buf, const float2 *in, const uint32_t m0, uint
     if (m < W) {
       const float2 cj = chirp[m];
       const float pw = xl_spec_power<true>(buf[c * N1 + m1], (v2f){cj.x, cj.y}, norm);
-      atomicMax(mx + m, __float_as_uint(pw));
+      atomicMax(mx + m, xl_spec_max_bits(pw));
     }
   }
 }
-
-// spectrogram.c:150: 10 * log10f(v) with the log10f the reference gets from its libm, the correctly rounded one.  The device's log10f is
-// an ulp off here and there -- at v = 1e-20f, the floor every bin of a silent input sits on, it gives -20.000002 and so pixel 54 where
-// the reference writes 55 -- so this one value per bin and row is taken in double and rounded once; the product is the float one.
-XL_DEV float xl_specw_db(const float v) { return 10.0f * (float)log10((double)v); }
 
 // Column j of a finished wide row: the maximum at position `from` of the row slot at rowmax[s ..] (the caller's bin order: a plain
 // width's xl_specw_col_pos, else the half swap) as dB to db[o + j] and as a pixel to px[o + j]; cleared for the row that reuses the slot
@@ -111,7 +106,7 @@ XL_DEV void xl_specw_finish_col(uint32_t *rowmax, float *db, uint8_t *px, const 
                                 const uint32_t j) {
   const float v = __uint_as_float(rowmax[s + from]);
   rowmax[s + from] = 0u;
-  const float d = xl_specw_db(v);
+  const float d = xl_spec_db(v);
   db[o + j] = d;
   px[o + j] = xl_spec_pixel(d);
 }

@@ -31,21 +31,25 @@ def to_complex(raw, fmt):
 def power_rows(x, sampling_rate, width):
     """spectrogram.c:84-148: row r is samples r * sampling_rate ..; its F = sampling_rate // width transforms of `width` samples
     (the S = sampling_rate % width after them skipped, :154), each bin's power |X / W|^2 + 1e-20 (:140-142), the maximum over the
-    row's transforms (:143, from -255 which no power undercuts).  Height = samples // sampling_rate (:93)."""
+    row's transforms (:148: fmaxf(temp[j], power) from -255, which no power undercuts and against which a NaN power loses: a transform
+    that holds a NaN sample does not contribute to its row, and a row of such transforms only stays at -255).
+    Height = samples // sampling_rate (:93)."""
     W, sr = width, sampling_rate
     F = sr // W
     H = x.size // sr
     rows = x[:H * sr].reshape(H, sr)[:, :F * W].reshape(H, F, W)
-    X = np.fft.fft(rows, axis=2) / W
-    p = X.real ** 2 + X.imag ** 2 + 1e-20
-    return p.max(axis=1)
+    with np.errstate(invalid="ignore"):
+        X = np.fft.fft(rows, axis=2) / W
+        p = X.real ** 2 + X.imag ** 2 + 1e-20
+    return np.fmax.reduce(p, axis=1, initial=-255.0)
 
 
 def shift_db(p):
     """spectrogram.c:150-158: 10 log10 per bin, halves of half = W // 2 swapped; an odd W's last bin stays last."""
     W = p.shape[1]
     half = W // 2
-    d = 10.0 * np.log10(p)
+    with np.errstate(invalid="ignore"):  # (a row left at -255: NaN, as log10f(-255) in the reference)
+        d = 10.0 * np.log10(p)
     out = d.copy()
     out[:, :half] = d[:, half:2 * half]
     out[:, half:2 * half] = d[:, :half]
@@ -64,7 +68,9 @@ def spectrogram(raw, fmt, sampling_rate, width):
     """(db float64 [H, W], pixels uint8 [H, W], amplitudes sqrt(p) float64 [H, W] in bin order) of a raw recording."""
     p = power_rows(to_complex(raw, fmt), sampling_rate, width)
     db = shift_db(p)
-    return db, pixels(db), np.sqrt(p)
+    with np.errstate(invalid="ignore"):
+        amp = np.sqrt(p)
+    return db, pixels(db), amp
 
 
 # ----------------------------------------------------------------------------------------------------- inputs of test/utils.c:137-174

@@ -101,9 +101,10 @@ def test_pixel_agreement_wide():
 @pytest.mark.parametrize("W", [16384, 20000])
 def test_all_zero_input(W):
     """zero samples: every power is exactly 1e-20f, every dB 10 log10f(1e-20f) with the host libm's correctly rounded log10f (-200.0
-    exactly), every pixel the restatement's 55.  The wide object's finishing pass takes its log10 in double and rounds once for this:
-    the device's own log10f(1e-20f) is -20.000002, which gave -200.00002 and pixel 54 when the pass used it (measured on an MI355X; the
-    object of the widths up to 8192, whose arithmetic stays as it is, still answers so)."""
+    exactly), every pixel the restatement's 55.  The finishing passes take their log10 in double and round once for this (xl_spec_db):
+    the device's own log10f(1e-20f) is -20.000002, which gave -200.00002 and pixel 54 when a pass used it (measured on an MI355X).  The
+    object of the widths up to 8192 answered so until it got the same dB function; its silent cases at every width, and the bits of
+    10 log10f next to every pixel boundary, are in tests/test_spectrogram_exact_gpu.py."""
     raw = np.zeros(2 * (2 * W + 100), np.float32)
     db, px = run_spectrum(raw, "cf32", W, W)
     assert db.shape == (2, W)

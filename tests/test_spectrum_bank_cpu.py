@@ -129,10 +129,12 @@ def test_bank_and_single_kernels_share_the_transform_arithmetic():
     prologue: the pack body (load, transforms, power, row maximum and its flush) and the finishing of a bin are defined in
     xl_spectrum_dev.h only, both kernel files call them, and neither transforms or flushes a maximum on its own"""
     dev = open(os.path.join(CSRC, "xl_spectrum_dev.h")).read()
-    for name in ("xl_fft_lds", "xl_spec_point", "xl_spec_blue_mid", "xl_spec_power", "xl_spec_db", "xl_spec_pixel", "xl_spec_shift_src",
-                 "xl_spec_pack", "xl_spec_finish_bin"):
+    for name in ("xl_fft_lds", "xl_spec_point", "xl_spec_blue_mid", "xl_spec_power", "xl_spec_max_bits", "xl_spec_db", "xl_spec_pixel",
+                 "xl_spec_shift_src", "xl_spec_pack", "xl_spec_finish_bin"):
         assert len(re.findall(r"^XL_DEV \w+ %s\(" % name, dev, re.M)) == 1, name
     assert "atomicMax" in dev
+    # a power's bits enter a maximum through xl_spec_max_bits only (the reference's fmaxf rule for a NaN power)
+    assert len(re.findall(r"__float_as_uint\(", re.sub(r"//[^\n]*", "", dev))) == 1
     for f in ("xl_spectrum.hip", "xl_spectrum_bank.hip"):
         src = open(os.path.join(CSRC, f)).read()
         code = re.sub(r"//[^\n]*", "", src)  # (the headers' prose names what the shared body does)

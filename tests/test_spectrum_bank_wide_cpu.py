@@ -124,10 +124,19 @@ def test_the_bank_takes_its_rules_from_the_plan_headers():
 # ------------------------------------------------------------------------------------------------------------ build and source
 def test_wide_passes_have_one_body():
     """the bit-identity of wide bank rows and single wide rows rests on one definition of what a workgroup does in each pass: defined in
-    xl_spectrum_wide_dev.h only; both kernel files call each once and neither transforms, takes a power or flushes a maximum itself"""
+    xl_spectrum_wide_dev.h only; both kernel files call each once and neither transforms, takes a power or flushes a maximum itself.
+    The dB of a finished column and the bits that enter a maximum are the narrow object's: one definition of each, in
+    xl_spectrum_dev.h, and no logarithm or bit cast of a power here"""
     dev = open(os.path.join(CSRC, "xl_spectrum_wide_dev.h")).read()
-    for name in ("xl_specw_col_in", "xl_specw_row", "xl_specw_col_out", "xl_specw_db", "xl_specw_finish_col"):
+    for name in ("xl_specw_col_in", "xl_specw_row", "xl_specw_col_out", "xl_specw_finish_col"):
         assert len(re.findall(r"^XL_DEV \w+ %s\(" % name, dev, re.M)) == 1, name
+    narrow = open(os.path.join(CSRC, "xl_spectrum_dev.h")).read()
+    for name in ("xl_spec_db", "xl_spec_max_bits"):
+        assert len(re.findall(r"^XL_DEV \w+ %s\(" % name, narrow, re.M)) == 1, name
+    code = re.sub(r"//[^\n]*", "", dev)
+    assert "xl_specw_db" not in dev and "log10" not in code and "__float_as_uint" not in code
+    assert len(re.findall(r"\bxl_spec_db\(", code)) == 1 and len(re.findall(r"atomicMax\([^;]*xl_spec_max_bits\(pw\)\);", code)) == 2
+    assert len(re.findall(r"atomicMax\(", code)) == 2
     for f in ("xl_spectrum_wide.hip", "xl_spectrum_bank_wide.hip"):
         src = open(os.path.join(CSRC, f)).read()
         code = re.sub(r"//[^\n]*", "", src)
@@ -135,7 +144,7 @@ def test_wide_passes_have_one_body():
         for call in (r"\bxl_specw_col_in<N1, N2, FMT, BLUE>\(", r"\bxl_specw_row<N1, N2, BLUE>\(", r"\bxl_specw_col_out<N1, N2>\(",
                      r"\bxl_specw_finish_col\(", r"\bxl_specw_dispatch\("):
             assert len(re.findall(call, code)) == 1, (f, call)
-        for own in ("atomicMax", "xl_fft_lds", "xl_spec_point", "xl_spec_power", "xl_spec_blue_mid", "log10", "xl_spec_pixel", "case "):
+        for own in ("atomicMax", "xl_fft_lds", "xl_spec_point", "xl_spec_power", "xl_spec_blue_mid", "log10", "xl_spec_db", "xl_spec_max_bits", "xl_spec_pixel", "case "):
             assert own not in code, (f, own)
     bank = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "xl_spectrum_bank_wide.hip")).read())
     assert "xl_ragged_find(" in bank and "xl_specw_col_pos(" in bank and "XL_SPECW_N2(" in bank
