@@ -13,8 +13,8 @@
 //   block        engine-owned copy of the current blocks (host path) -- or the caller's device buffer, in place
 //   taps         [tile][Tpad][ct] float2, tap i of the ct clients of a tile contiguous (one s_load_dwordx16)
 //   groups[ct]   XlGroup descriptors (<= 4 tiles of one class each) incl. the class's plan-time stream record
-//   nco          XlNcoClient per client; phase[2][slot] running NCO phases (committed / next)
-//   phtab[2]     [client][K_cap / 16] float2 phase tables (ping-pong), out[2] outputs (ping-pong), same indexing
+//   nco          XlNcoClient per client; phase[XL_NTAB][slot] running NCO phases (a ring: committed, then the calls tabulated ahead)
+//   phtab[XL_NTAB] [client][K_cap / 16] float2 phase tables (a ring: xl_ahead.h), out[2] outputs (ping-pong), same indexing
 //
 // Streaming rule (xl_grid.h): a client's outputs lie on the global grid n = k*D of ITS stream; output
 // k's newest sample is stream sample k*D.  Samples older than the client (it joined mid-stream) must read as zero.
@@ -25,8 +25,9 @@
 //
 // Streams.  A call's outputs depend on (raw history, blocks, phase table) only.  The phase table is data independent
 // (float32 recurrence p <- p * incr, xlating.c:70-73), so call c+1's table is tabulated inside call c's launches (the
-// "NCO role"), guessing that c+1 has the same shape; the running phases are double-buffered (committed / next) so that
-// a wrong guess is simply redone by a small launch of its own.  Everything runs on the caller's stream in stream order.
+// "NCO role") or, up to four calls ahead, by a chain launch on a side stream, guessing that the next calls have the same shape; the
+// running phases live in a ring beside the tables (committed, then ahead), so that a wrong guess is simply redone by a small launch
+// of its own.  The call's own launches run on the caller's stream in stream order; the look-ahead's rules are xl_ahead.h's.
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
@@ -39,6 +40,7 @@
 #include <vector>
 
 #include "../../include/xlating_batch.h"
+#include "xl_ahead.h"
 #include "xl_common.h"
 #include "xl_device.h"
 #include "xl_mixf_layout.h"
@@ -51,15 +53,7 @@
 
 #define XL_GROUP_MAX 64u  // most blocks per call
 
-namespace {
-
-// Phase tables / phase buffers in the engine's rings.  A chain launch made at call c for calls c+1 .. c+n overwrites the
-// tables of calls c+n-XL_NTAB+1 ..; with XL_NTAB = 2 n the latest of them belongs to the launch before the previous one, whose
-// readers ran while the previous launch was stepping -- the new launch never has to wait for them on a chain-bound engine.
-#define XL_NTAB (2 * XL_CHAIN_MAXCALLS)
-static inline int xl_nx(int i) { return (i + 1) % XL_NTAB; }
-
-}  // namespace
+static_assert(XL_AHEAD_MAXCALLS == XL_CHAIN_MAXCALLS, "xl_ahead.h plans the chain launches of xl_device.h");
 
 struct xlating_batch_t {
   uint32_t fs = 0;
@@ -197,43 +191,15 @@ struct xlating_batch_t {
   size_t h_out_alloc = 0;
   bool fetched = false;
 
-  // Rings of XL_NTAB phase buffers and phase tables: [pcur] = committed running phases, [pcur + 1] = after the next call,
-  // [pcur + 2] = after the one behind it (a chain launch may tabulate two calls ahead); table [tab] = the latest call's.
+  // The float families' phase look-ahead (xl_ahead.h: the ring's invariants are stated there): rings of phase buffers and phase tables,
+  // per table the events "its tabulation on a side stream is complete" / "its readers have been passed"; `ahead` holds the indices
+  // into them and makes every decision.
   float2 *d_phase[XL_NTAB] = {};
-  int pcur = 0;
   size_t phase_cap = 0;
   float2 *d_phtab[XL_NTAB] = {};
-  int tab = 0;              // table used by the latest call
-  // Look-ahead: tables [tab + 1] .. [tab + spec_n] hold the phases of the next spec_n calls assuming spec_S samples x
-  // spec_G blocks each (the phases after them: d_phase[pcur + 1 ..]); produced by the latest call's launches (spec_n = 1)
-  // or by one chain launch on the side stream (spec_n <= 2), whose completion is ev_chain[spec_ev].
-  int spec_n = 0;
-  uint32_t spec_S = 0, spec_G = 0, spec_flags = 0;
-  int spec_ev = 0;
-  bool spec_on_side = false;  // the look-ahead table was produced on nco_stream (ev_chain must be waited for)
-  hipStream_t last_nco = nullptr;  // the side stream of the latest chain launch
-  // ev_chain[t]: the tabulation of table t is complete (the caller's stream waits for it before the first launch that reads the
-  // table); ev_done[t]: the launches that read table t have been passed by the caller's stream (nco_stream waits for it before
-  // overwriting that table).
-  hipEvent_t ev_chain[XL_NTAB] = {}, ev_done[XL_NTAB] = {};  // per phase table
-  bool ev_done_valid[XL_NTAB] = {};
-  // Round 4: a launch that carries a completion event keeps the queue ~8 us from starting the next launch (a fifth of a one-block
-  // call), and in the steady side-stream pattern only ONE call in `chain_calls` needs its event: a chain launch made at call k
-  // overwrites the tables last read by calls k-7 .. k-4, and call k-4 is the previous chain-launching call.  So side-stream calls
-  // record ev_done only when they launch a chain; tab_call[] / done_call let a chain launch check that the latest recorded event
-  // post-dates every reader of its tables (calls run in order: an event behind call j covers all calls <= j), and fall back to an
-  // event recorded on the spot when it does not (irregular patterns only).
-  uint64_t tab_call[XL_NTAB] = {};  // ncalls + 1 of the latest call that read table t (0: never)
-  uint64_t done_call = 0;           // ncalls + 1 of the latest call that recorded an ev_done (0: none)
-  int done_tab = 0;                 // ... and which one
-  bool waited_valid = false;  // stream waited_stream has waited for ev_chain[waited_ev] since that event was last recorded
-  int waited_ev = 0;
-  hipStream_t waited_stream = nullptr;
-  int chain_calls = 4;  // XL_EXP_CHAIN_CALLS (tuning): most calls one side-stream chain launch tabulates ahead (1 .. XL_CHAIN_MAXCALLS)
-  int chain_ahead = 4;  // ... and how many the NEXT launch does: 1 after a wrong shape guess (the look-ahead it drops is then one call of
-                        // chain work the call has to wait out, not four), doubled by every launch whose calls were all consumed.
-                        // A stream of irregular block lengths, one block per call, 1024 clients: 134 us per call with four calls
-                        // ahead every time (profiles/r05_ragged_blocks.txt), against 39.5 us for constant lengths
+  hipEvent_t ev_chain[XL_NTAB] = {}, ev_done[XL_NTAB] = {};
+  XlAhead ahead = xl_ahead_init();
+  hipStream_t last_nco = nullptr;  // the side stream of the latest chain launch (nullptr: none since the masked pair was last re-created)
   bool exp_nofuse = false;  // XL_TUNING: keep the NCO tabulation a launch of its own
 
   uint32_t exp_flags = 0;  // tuning knobs
@@ -436,7 +402,7 @@ static int xl_batch_set_tuning(xlating_batch *b, const std::string &n, long valu
     b->exp_h = (int)value;
   } else if (n == "nco_calls_per_launch") {
     if (value < 1 || value > (long)XL_CHAIN_MAXCALLS) return -EINVAL;
-    b->chain_calls = (int)value;
+    b->ahead.chain_calls = (int)value;
   } else if (n == "nco_slice") {  // forward | inverse boundary of the in-launch NCO role, in 1/65536 of a call
     if (value < 0 || value > 65536) return -EINVAL;
     b->poly_slice_fi = (uint32_t)value;
@@ -668,7 +634,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   // tabulated ahead is for the old client set: drop it (the committed phases are untouched by it).
   (void)hipSetDevice(b->device);
   xl_batch_sync_all(b);
-  b->spec_n = 0;
+  xl_ahead_drop(&b->ahead);
   xl_q15_ahead_drop(b);
   // Every failure from here on rolls the client back (a phantom client with an undefined phase would otherwise be
   // planned and filtered on every later call, with no id in the caller's hands to remove it).
@@ -713,7 +679,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   {
     const float2 one = make_float2(1.0f, 0.0f);
     const short2 qone = make_short2(INT16_MAX, 0);  // xlating.c:546-547
-    if (hipMemcpy(b->d_phase[b->pcur] + id, &one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
+    if (hipMemcpy(b->d_phase[b->ahead.pcur] + id, &one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
     if (hipMemcpy(b->d_qphase[b->qcur] + id, &qone, sizeof(qone), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
   }
   return id;
@@ -956,8 +922,7 @@ static void xl_batch_reserve_cus(xlating_batch *b, uint32_t want) {
   b->last_nco = nullptr;
   b->reserve_r = 0;
   b->last_stream = b->own_stream;  // (everything was synchronised at the top of the plan)
-  for (int i = 0; i < XL_NTAB; ++i) b->ev_done_valid[i] = false, b->tab_call[i] = 0;
-  b->done_call = 0;
+  xl_ahead_reset(&b->ahead);
   if (want > 0u) {
     uint32_t chain_mask[8], main_mask[8];
     for (uint32_t wd = 0; wd < 8; ++wd) {
@@ -1022,7 +987,7 @@ static int xl_batch_plan(xlating_batch *b) {
   };
   xl_batch_sync_all(b);
   lap("sync");
-  b->spec_n = 0;
+  xl_ahead_drop(&b->ahead);
   xl_q15_ahead_drop(b);
   const uint32_t advanced = b->trel;  // samples since the previous plan: every plan-time stream record moves by this much
   xl_batch_free_plan(b, false);
@@ -1185,9 +1150,9 @@ fail:
   return xl_errno_of_last_hip_error();
 }
 
-// Tabulate the phases of a call as a launch of its own on stream `st`: committed phases -> table[tab] + next
+// Tabulate the phases of a call as a launch of its own on stream `st`: committed phases -> the call's table + next
 // phases.  Only needed when no table was tabulated ahead (first call, changed call shape, changed client set).
-static hipError_t xl_batch_nco(xlating_batch *b, const XlPos pos, int tab, hipStream_t st) {
+static hipError_t xl_batch_nco(xlating_batch *b, const XlPos pos, const XlAheadBegin &ah, hipStream_t st) {
   hipError_t e;
   hipEvent_t n0 = nullptr, n1 = nullptr;
   if (b->timing) {
@@ -1202,8 +1167,8 @@ static hipError_t xl_batch_nco(xlating_batch *b, const XlPos pos, int tab, hipSt
     e = hipEventRecord(n0, st);
     if (e != hipSuccess) return e;
   }
-  e = xl_launch_nco_table(b->d_nco, (uint32_t)b->nco.size(), b->d_phase[b->pcur], b->d_phase[xl_nx(b->pcur)],
-                          b->d_phtab[tab], pos, 0xFFFFFFFFu, b->nco_prio, st);
+  e = xl_launch_nco_table(b->d_nco, (uint32_t)b->nco.size(), b->d_phase[ah.phase_in], b->d_phase[ah.pcur],
+                          b->d_phtab[ah.tab], pos, 0xFFFFFFFFu, b->nco_prio, st);
   if (e != hipSuccess) return e;
   return n1 ? hipEventRecord(n1, st) : hipSuccess;
 }
@@ -1247,20 +1212,16 @@ struct XlCall {
   hipEvent_t wait_ev, record_ev;
   // decisions
   uint32_t maxK, maxKw;  // the most outputs any client / any wide client (a launch of their own) produces in this call
-  bool use_poly, side, fuse;
+  bool use_poly, side;
   int p;  // parity of this call: output buffer
-  int hb, hn, tab, pcur, chain_ev;
-  int spec_left;  // look-ahead calls that stay valid behind this one (a chain launch covers up to two)
-  bool tab_from_s;
-  // does this call record ev_done[tab]?  Side-stream calls: only the ones that launch a chain (see tab_call); non-side calls
-  // after a side stream was used: always
-  bool want_done;
+  int hb, hn;
+  XlAheadBegin ah;     // the phase look-ahead's decisions (xl_ahead.h): this call's table and phases, ...
+  XlAheadChain chain;  // ... its chain launch (n = 0: none), ...
+  bool want_done;      // ... and whether it records ev_done[ah.tab]
   // running flags
-  bool chain_wait;  // this call's table comes from the side stream: wait for it before the first reader
   bool rolled, nco_fused;
-  bool done_attached;    // ev_done[tab] rides on the call's last launch
+  bool done_attached;    // ev_done[ah.tab] rides on the call's last launch
   bool record_attached;  // the caller's record_ev rides on the last launch instead (no ev_done wanted there)
-  int launched_n;
   hipEvent_t f0, f1;  // timing: around the call's launches
   bool ended;         // xl_call_begin ended the call: it returns `ret`
   int ret;
@@ -1274,14 +1235,24 @@ XL_STAGE int xl_call_end(XlCall &c, int ret) {
   return 0;
 }
 
+// Executes the synchronisation a look-ahead decision asks for: `s` the call's stream, `ns` its side stream.
+XL_STAGE hipError_t xl_ahead_run(xlating_batch *b, const XlAheadOps &l, hipStream_t s, hipStream_t ns = nullptr) {
+  for (int i = 0; i < l.n; ++i) {
+    const XlAheadOp o = l.op[i];
+    hipStream_t st = o.stream == XL_AHEAD_S_CALL ? s : (o.stream == XL_AHEAD_S_SIDE ? ns : b->last_nco);
+    hipEvent_t ev = o.ev == XL_AHEAD_EV_DEP ? b->dep_ev : (o.ev == XL_AHEAD_EV_CHAIN ? b->ev_chain[o.idx] : b->ev_done[o.idx]);
+    const hipError_t e = o.op == XL_AHEAD_WAIT ? hipStreamWaitEvent(st, ev, 0) : hipEventRecord(ev, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // The first reader of a table that came from the side stream waits for its chain launch, once per stream and launch.
 XL_STAGE hipError_t xl_call_chain_wait(xlating_batch *b, XlCall &c) {
-  if (!c.chain_wait) return hipSuccess;
-  const hipError_t e = hipStreamWaitEvent(c.s, b->ev_chain[c.chain_ev], 0);
-  if (e != hipSuccess) return e;
-  c.chain_wait = false;
-  b->waited_valid = true, b->waited_ev = c.chain_ev, b->waited_stream = c.s;
-  return hipSuccess;
+  if (!c.ah.chain_wait) return hipSuccess;
+  const hipError_t e = hipStreamWaitEvent(c.s, b->ev_chain[c.ah.chain_ev], 0);
+  if (e == hipSuccess) xl_ahead_chain_waited(&b->ahead, &c.ah, c.s);
+  return e;
 }
 
 // The first launch of a call also rolls the raw history into d_hist[hn] (XlFirArgs, XlpArgs).
@@ -1391,21 +1362,9 @@ XL_STAGE int xl_call_begin(xlating_batch *b, XlCall &c) {
     int rc = xl_batch_build_all_set(b);
     if (rc != 0) return xl_call_end(c, rc);
   }
-  {
-    const bool light = xl_direct_is_light((c.use_poly ? b->macs_rest : b->macs_all) * (double)S);
-    // Who tabulates the NEXT call's phases: the NCO role inside this call's launches (fuse), or xl_nco_chain_kernel on
-    // the side stream, concurrently with them (side).  The side stream pays for calls of several blocks on the
-    // polyphase path, whose three launches are short against the chain (measured, 8 blocks per call: 42.7 -> 36.8 us per
-    // block at 1024 clients, 30.7 -> 28.8 at 128); a direct FIR launch hides the chain in its spare waves for free and
-    // would only lose the chain kernel's CUs (1024 clients, native: 203 -> 212 us per block), and with one block per
-    // call the cross-stream events cost more than the overlap gains (51.3 -> 58.6).
-    // One-block calls (the reference's call granularity) on the polyphase path: the three launches are short since the mix runs on
-    // the matrix cores, and a slice of the recurrence inside each made every one of them last as long as its slice (1024 clients:
-    // 50.2 us per block; the chain kernel beside them, four calls per launch: 47.7; 128 clients: 40.4 -> 29.2; 4096: 129 -> 134,
-    // hence the limit)
-    const bool one_block_side = G == 1 && c.use_poly && b->nco.size() <= XL_SIDE_ONE_BLOCK_MAX;
-    c.side = c.mode != XL_MODE_Q15 && (b->nco_side > 0 || (b->nco_side < 0 && (G >= 2 || one_block_side) && (c.use_poly || (light && b->cs_masked && c.s == XL_STREAM_ENGINE_P))));  // (a caller's own, unmasked stream would keep filling the chain's CUs)
-  }
+  c.side = xl_side_call(c.mode == XL_MODE_Q15, b->nco_side, G, c.use_poly, b->nco.size(),
+                        xl_direct_is_light((c.use_poly ? b->macs_rest : b->macs_all) * (double)S), b->cs_masked != nullptr,
+                        c.s == XL_STREAM_ENGINE_P);
   if (c.s == XL_STREAM_ENGINE_P) c.s = (c.side && b->cs_masked) ? b->cs_masked : b->own_stream;
   // Calls depend on each other through the engine's device state (history, phases, tables): a call on another stream than the
   // previous one is ordered behind it.  (Overlapping consecutive one-block calls through two compute streams -- round 4's
@@ -1442,8 +1401,8 @@ XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
   const bool ahead = b->q15_nco == 1u;
   const uint32_t ncl = (uint32_t)b->nco.size();
   const short2 *qphtab = b->d_qphtab[b->qtab];
-  if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[b->spec_ev], 0));
-  b->spec_n = 0;
+  XL_TRY(xl_ahead_run(b, xl_ahead_pending_wait(&b->ahead), s));
+  xl_ahead_drop(&b->ahead);
   b->poisoned = true;
   if (!ahead) {
     if (b->qa_pending) XL_TRY(hipStreamWaitEvent(s, b->ev_qchain, 0));  // (it reads the phases stepped in place below)
@@ -1510,95 +1469,50 @@ fail:
   return 1;
 }
 
-// Stage 3: this call's phase table: tabulated ahead by the previous call's launches if the shape guess was right.
+// Stage 3: this call's phase table: tabulated ahead by an earlier call's launches if the shape guess was right, else here.
 XL_STAGE int xl_call_table(xlating_batch *b, XlCall &c) {
-  hipStream_t s = c.s;
-  c.tab = xl_nx(b->tab), c.pcur = b->pcur, c.chain_ev = b->spec_ev;
-  c.tab_from_s = true;
-  if (b->spec_n > 0 && b->spec_S == c.S && b->spec_G == c.G && b->spec_flags == c.pos.pad) {
-    c.tab_from_s = !b->spec_on_side;
-    // (the second call of a chain launch's pair: this stream has already waited for that launch)
-    c.chain_wait = b->spec_on_side && !(b->waited_valid && b->waited_ev == c.chain_ev && b->waited_stream == s);
-    c.spec_left = b->spec_n - 1;
-  } else {
-    // (a look-ahead of the wrong shape may still be running on the side stream, on these very buffers)
-    if (b->spec_n > 0 && b->spec_on_side) XL_TRY(hipStreamWaitEvent(s, b->ev_chain[c.chain_ev], 0));
-    if (b->spec_n > 0) b->chain_ahead = 1;  // (a wrong guess: look less far ahead until the guesses hold again)
-    if (b->ev_done_valid[c.tab]) XL_TRY(hipStreamWaitEvent(s, b->ev_done[c.tab], 0));  // (same stream normally: a no-op)
-    XL_TRY(xl_batch_nco(b, c.pos, c.tab, s));
-  }
-  c.pcur = xl_nx(c.pcur);  // the phases written by that tabulation are now the committed ones
-  b->spec_n = 0;           // (from here on a failure poisons the engine)
-  b->poisoned = true;
-  // (with a look-ahead table still in hand the launches carry no NCO role: the call after this one has its table)
 #ifdef XL_TUNING
-  c.fuse = !c.side && c.spec_left == 0 && !b->exp_nofuse;  // tuning: tabulate by a launch of its own before every call
+  const bool nofuse = b->exp_nofuse;  // tuning: tabulate by a launch of its own before every call
 #else
-  c.fuse = !c.side && c.spec_left == 0;
+  const bool nofuse = false;
 #endif
+  c.ah = xl_ahead_begin(&b->ahead, (uint32_t)c.S, c.G, c.pos.pad, c.s, c.side, nofuse);
+  if (!c.ah.hit) {
+    XL_TRY(xl_ahead_run(b, c.ah.pre, c.s));
+    XL_TRY(xl_batch_nco(b, c.pos, c.ah, c.s));
+  }
+  xl_ahead_drop(&b->ahead);  // (from here on a failure poisons the engine)
+  b->poisoned = true;
   return 0;
 fail:
   return 1;
 }
 
-// Stage 4 (side-stream calls without a look-ahead table left): the NEXT call's table (same shape assumed) into
-// table[tab ^ 1], concurrently with the launches of the stages below.  That table was last read by the previous call's
-// launches (ev_done), the committed phases d_phase[pcur] were written by the tabulation of THIS call's table (earlier on
-// the same side stream, or on `s`: ordered below).
+// Stage 4 (side-stream calls without a look-ahead table left): the tables of the NEXT calls (same shape assumed), concurrently
+// with the launches of the stages below, by one chain launch that starts from the phases this call commits.
 XL_STAGE int xl_call_chain(xlating_batch *b, XlCall &c) {
-  hipStream_t s = c.s;
   // (the CU-masked pair of streams goes together: a chain kernel confined to CUs that the caller's own, unmasked
   // stream keeps filling would wait for kernel boundaries)
-  hipStream_t ns = (s == b->cs_masked && b->nco_masked) ? b->nco_masked : b->nco_stream;
-  if (ns != b->last_nco) {  // consecutive chains depend on each other through the phase buffers
-    if (b->last_nco) {
-      XL_TRY(hipEventRecord(b->dep_ev, b->last_nco));
-      XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
-    }
-    b->last_nco = ns;
-  }
-  if (c.tab_from_s) {  // this call's table was tabulated on `s` (just now, or by the previous call's launches): order the side stream behind it
-    XL_TRY(hipEventRecord(b->dep_ev, s));
-    XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
-  }
+  hipStream_t ns = (c.s == b->cs_masked && b->nco_masked) ? b->nco_masked : b->nco_stream;
+  const XlAheadChain ch = xl_ahead_chain(&b->ahead, &c.ah, ns != b->last_nco);
   XlChainCalls cc;
+  XL_TRY(xl_ahead_run(b, ch.pre, c.s, ns));
+  b->last_nco = ns;
   memset(&cc, 0, sizeof(cc));
-  cc.n = (uint32_t)std::min<int>(std::max(std::min(b->chain_calls, b->chain_ahead), 1), (int)XL_CHAIN_MAXCALLS);
-  b->chain_ahead = std::min(2 * b->chain_ahead, (int)XL_CHAIN_MAXCALLS);  // (this launch is made because the previous one's calls were all used)
-  int tt[XL_CHAIN_MAXCALLS];
-  for (int i = 0, t = c.tab, pp = c.pcur; i < (int)cc.n; ++i) {
-    t = xl_nx(t), pp = xl_nx(pp);
-    cc.tab[i] = b->d_phtab[t];
-    cc.state_out[i] = b->d_phase[pp];
-    tt[i] = t;
-  }
-  // the tables' last readers (XL_NTAB - 1 - i calls back): one wait for the latest of them covers the earlier ones that
-  // were recorded on the same stream (every wait is a queue packet of its own, ~4 us in front of the chain launch)
-  {
-    uint64_t need = 0;  // the latest call that read one of these tables
-    for (int i = 0; i < (int)cc.n; ++i) need = std::max(need, b->tab_call[tt[i]]);
-    if (need != 0) {
-      if (b->done_call >= need) {
-        XL_TRY(hipStreamWaitEvent(ns, b->ev_done[b->done_tab], 0));
-      } else if (!c.tab_from_s) {  // (tab_from_s: the side stream was just ordered behind everything on `s`)
-        XL_TRY(hipEventRecord(b->dep_ev, s));  // all earlier calls' launches precede this point of `s`
-        XL_TRY(hipStreamWaitEvent(ns, b->dep_ev, 0));
-      }
-    }
-  }
-  XL_TRY(xl_launch_nco_chain(b->d_nco, (uint32_t)b->nco.size(), b->d_phase[c.pcur], cc, xl_grid_next(c.pos),
-                             b->d_chain_stats, ns, b->ev_chain[xl_nx(c.tab)]));
-  c.launched_n = (int)cc.n;
-  b->waited_valid = false;  // (ev_chain[xl_nx(tab)] now stands for this launch)
+  cc.n = (uint32_t)ch.n;
+  for (int i = 0; i < ch.n; ++i) cc.tab[i] = b->d_phtab[ch.tab[i]], cc.state_out[i] = b->d_phase[ch.phase[i]];
+  XL_TRY(xl_launch_nco_chain(b->d_nco, (uint32_t)b->nco.size(), b->d_phase[ch.phase_in], cc, xl_grid_next(c.pos),
+                             b->d_chain_stats, ns, b->ev_chain[ch.ev]));
+  c.chain = ch;
   return 0;
 fail:
   return 1;
 }
 
-// Stage 5: the launches on the caller's stream begin: window images from [d_hist[hb] | blocks], phases from table[tab] ->
-// d_out[p]; the first launch also rolls the raw history into d_hist[hn], and the launches tabulate table[tab ^ 1]
-// for the next call.  Here: the call's timing events, whether it records ev_done[tab], and the direct launches of its launch
-// set.  Only the first launch of a call rolls the history and may carry the NCO role.
+// Stage 5: the launches on the caller's stream begin: window images from [d_hist[hb] | blocks], phases from the call's table ->
+// d_out[p]; the first launch also rolls the raw history into d_hist[hn], and the launches of a call that fuses tabulate the ring's
+// next table for the next call.  Here: the call's timing events, whether it records ev_done for its table, and the direct launches
+// of its launch set.  Only the first launch of a call rolls the history and may carry the NCO role.
 XL_STAGE int xl_call_direct(xlating_batch *b, XlCall &c) {
   hipStream_t s = c.s;
   Launch *const Ls = c.use_poly ? b->launches_rest : b->launches;
@@ -1610,7 +1524,7 @@ XL_STAGE int xl_call_direct(xlating_batch *b, XlCall &c) {
     }
     c.f0 = b->ev[b->ev.size() - 2], c.f1 = b->ev[b->ev.size() - 1];
   }
-  c.want_done = (c.side || b->last_nco != nullptr) && (!c.side || c.launched_n > 0);
+  c.want_done = xl_ahead_want_done(&b->ahead, c.side, c.chain.n);
   if (c.f0) XL_TRY(hipEventRecord(c.f0, s));
   for (int lq = 0; lq < XL_NLAUNCH && c.maxK > 0; ++lq) {
     Launch &L = Ls[lq];
@@ -1624,10 +1538,10 @@ XL_STAGE int xl_call_direct(xlating_batch *b, XlCall &c) {
     const bool flat = (b->exp_flags & 2u) || wgs > 2 * cap;
     a.flags = (L.all_wide ? 1u : 0u) | (flat ? 2u : 0u) | 4u | ((b->nco_prio & 3u) << 4);
     a.taps = c.use_poly ? b->d_taps_rest : b->d_taps;
-    a.phtab = b->d_phtab[c.tab];
+    a.phtab = b->d_phtab[c.ah.tab];
     if (!c.rolled) {
       xl_call_roll_args(b, c, a);
-      if (c.fuse) {
+      if (c.ah.fuse) {
         a.nco_clients = b->d_nco;
         a.nco_nclients = (uint32_t)b->nco.size();
         const uint32_t slots = L.idle_waves * a.xtiles;
@@ -1640,8 +1554,8 @@ XL_STAGE int xl_call_direct(xlating_batch *b, XlCall &c) {
           a.nco_wpw = std::max<uint32_t>(1, std::min<uint32_t>(b->nco_wpw, (uint32_t)L.nw));
           a.nco_blocks = (a.nco_nclients + XL_NCO_LANES * a.nco_wpw - 1) / (XL_NCO_LANES * a.nco_wpw);
         }
-        a.nco_state_in = b->d_phase[c.pcur], a.nco_state_out = b->d_phase[xl_nx(c.pcur)];
-        a.nco_tab = b->d_phtab[xl_nx(c.tab)];
+        a.nco_state_in = b->d_phase[c.ah.pcur], a.nco_state_out = b->d_phase[xl_nx(c.ah.pcur)];
+        a.nco_tab = b->d_phtab[xl_nx(c.ah.tab)];
         c.nco_fused = true;
       }
     }
@@ -1701,18 +1615,18 @@ XL_STAGE int xl_call_poly_class(xlating_batch *b, XlCall &c, PolyClass &pc, bool
   pa.segmax = pc.d_segmax, pa.seg_par = pc.seg_par, pa.seg_cap = pc.seg_cap;
   pc.seg_par ^= 1u;  // (a failed call leaves stale maxima behind at worst: a smaller scale than necessary, never a wrong one)
   pa.W = b->d_W, pa.X = pc.d_X, pa.ximg = pc.ximg ? 1u : 0u, pa.Y = pc.d_Y, pa.cols = pc.d_cols;
-  pa.phtab = b->d_phtab[c.tab], pa.out = b->d_out[c.p];
+  pa.phtab = b->d_phtab[c.ah.tab], pa.out = b->d_out[c.p];
   // the NEXT call's phase recurrence rides in these launches (a direct launch above carries all of it if there is
   // one): TWO slices, forward | inverse -- never the mix launch: no launch that issues matrix instructions hosts the role
   // 
-  const bool carry = c.fuse && !c.nco_fused;
+  const bool carry = c.ah.fuse && !c.nco_fused;
   const uint32_t sl1 = std::min(b->poly_slice_fi, 60000u);
   if (carry) {
     pa.nco_clients = b->d_nco, pa.nco_nclients = (uint32_t)b->nco.size();
     pa.nco_blocks = (pa.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
-    pa.nco_tab = b->d_phtab[xl_nx(c.tab)], pa.nco_prio = b->nco_prio;
+    pa.nco_tab = b->d_phtab[xl_nx(c.ah.tab)], pa.nco_prio = b->nco_prio;
     pa.nco_k0 = 0, pa.nco_k1 = sl1;
-    pa.nco_state_src = b->d_phase[c.pcur], pa.nco_state_dst = b->d_phase_run;
+    pa.nco_state_src = b->d_phase[c.ah.pcur], pa.nco_state_dst = b->d_phase_run;
   }
   // the call's last launch carries the "table has been read" event the side stream waits for
   const bool last_launch = c.side && c.rolled && last && c.maxKw == 0;  // (a wide launch follows: it reads the table too)
@@ -1743,10 +1657,10 @@ XL_STAGE int xl_call_poly_class(xlating_batch *b, XlCall &c, PolyClass &pc, bool
   if (traced == 2) XL_TRY(xl_ptrace(b, pa, s, false));
   if (pe[2]) XL_TRY(hipEventRecord(pe[2], s));
   if (carry) {
-    pa.nco_tab = b->d_phtab[xl_nx(c.tab)];
+    pa.nco_tab = b->d_phtab[xl_nx(c.ah.tab)];
     pa.nco_blocks = (pa.nco_nclients + XL_NCO_LANES - 1) / XL_NCO_LANES;
     pa.nco_k0 = sl1, pa.nco_k1 = 65536;
-    pa.nco_state_src = b->d_phase_run, pa.nco_state_dst = b->d_phase[xl_nx(c.pcur)];
+    pa.nco_state_src = b->d_phase_run, pa.nco_state_dst = b->d_phase[xl_nx(c.ah.pcur)];
     if (b->inv_skip_at > 0) pa.nco_skip_at = b->inv_skip_at, pa.nco_skip = pa.nco_blocks;
     c.nco_fused = true;
   }
@@ -1754,7 +1668,7 @@ XL_STAGE int xl_call_poly_class(xlating_batch *b, XlCall &c, PolyClass &pc, bool
   XL_TRY(xl_call_chain_wait(b, c));  // (the forward and mix launches do not read the table)
   {
     const bool attach = last_launch && traced != 3;  // (a traced inverse launch carries no event)
-    XL_TRY(xlp_launch_inverse(pa, s, attach ? (c.want_done ? b->ev_done[c.tab] : c.record_ev) : nullptr));
+    XL_TRY(xlp_launch_inverse(pa, s, attach ? (c.want_done ? b->ev_done[c.ah.tab] : c.record_ev) : nullptr));
     pc.last_inv = (int)xlp_inverse_pick(pa.M, pa.inv_reg, pa.nseg * pa.ncg * 4u);
     c.done_attached = attach && c.want_done;
     c.record_attached = attach && !c.want_done && c.record_ev != nullptr;
@@ -1772,7 +1686,7 @@ XL_STAGE int xl_call_wide_and_rolls(xlating_batch *b, XlCall &c) {
   hipStream_t s = c.s;
   if (c.maxKw > 0) {
     XL_TRY(xl_call_chain_wait(b, c));
-    XL_TRY(xl_batch_wide_launch(b, c, b->d_phtab[c.tab]));
+    XL_TRY(xl_batch_wide_launch(b, c, b->d_phtab[c.ah.tab]));
   }
   if (c.f1) XL_TRY(hipEventRecord(c.f1, s));
   if (!c.rolled)  // no client produced output in this call (tiny block): roll the history on its own
@@ -1785,36 +1699,11 @@ fail:
 
 // Stage 8: the "table has been read" event, the caller's event, the host commit and the look-ahead handed to the next call.
 XL_STAGE int xl_call_finish(xlating_batch *b, XlCall &c) {
-  hipStream_t s = c.s;
-  const int tab = c.tab;
-  // table[tab] has been read by everything enqueued so far (only the side stream ever waits for this)
-  // -- and a LATER side-stream chain launch may find this slot in its ring even when this call ran no side stream
-  // (alternating modes, alternating caller streams, nco_calls_per_launch < 4): once a side stream has been used the
-  // event is recorded for every call.  Engines that never use the side stream never pay for it.
-  if (c.side || b->last_nco != nullptr) b->tab_call[tab] = b->ncalls + 1;
-  if (c.want_done) {
-    if (!c.done_attached) XL_TRY(hipEventRecord(b->ev_done[tab], s));
-    b->ev_done_valid[tab] = true;
-    b->done_call = b->ncalls + 1, b->done_tab = tab;
-  } else {
-    b->ev_done_valid[tab] = false;
-  }
-  if (c.record_ev && !c.record_attached) XL_TRY(hipEventRecord(c.record_ev, s));
+  // the call's table has been read by everything enqueued so far
+  if (c.want_done && !c.done_attached) XL_TRY(hipEventRecord(b->ev_done[c.ah.tab], c.s));
+  if (c.record_ev && !c.record_attached) XL_TRY(hipEventRecord(c.record_ev, c.s));
+  xl_ahead_finish(&b->ahead, &c.ah, b->ncalls + 1, c.side, c.want_done, c.chain.n, c.nco_fused, (uint32_t)c.S, c.G, c.pos.pad);
   xl_call_commit(b, c);
-  b->pcur = c.pcur, b->tab = tab;
-  // ---- the NEXT call's phases, guessing it has the same shape, were tabulated inside the launches above;
-  // without them (tiny call, or the tuning switch) the next call tabulates for itself
-  if (c.launched_n > 0) {
-    b->spec_n = c.launched_n;
-    b->spec_on_side = true;
-    b->spec_ev = xl_nx(tab);
-  } else if (c.spec_left > 0) {
-    b->spec_n = c.spec_left;  // (same launch, same event)
-  } else if (c.nco_fused) {
-    b->spec_n = 1;
-    b->spec_on_side = false;
-  }
-  b->spec_S = (uint32_t)c.S, b->spec_G = c.G, b->spec_flags = c.pos.pad;
   return 0;
 fail:
   return 1;
@@ -1837,7 +1726,7 @@ static int xl_batch_run(xlating_batch *b, const void *d_blocks, size_t input_len
   }
   b->last_q15 = false;
   if (xl_call_table(b, c)) goto fail;
-  if (c.side && c.spec_left == 0 && xl_call_chain(b, c)) goto fail;
+  if (c.side && c.ah.spec_left == 0 && xl_call_chain(b, c)) goto fail;
   if (xl_call_direct(b, c)) goto fail;
   if (c.maxK > 0 && c.use_poly)
     for (PolyClass &pc : b->poly)
@@ -2074,10 +1963,10 @@ extern "C" int xlating_batch_client_phase(xlating_batch *b, int id, float *re, f
   if (b == nullptr || id < 0 || (size_t)id >= b->clients.size() || !b->clients[id].alive) return -EINVAL;
   if (hipSetDevice(b->device) != hipSuccess) return -EIO;
   xl_batch_sync_all(b);
-  // the look-ahead NCO role has already produced the phases AFTER the next call into d_phase[pcur^1];
-  // the committed ones (after the latest processed call) are d_phase[pcur]
+  // the look-ahead may already have produced the phases behind the next calls further along the ring; the committed ones
+  // (behind the latest processed call) are d_phase[pcur]
   float2 ph;
-  if (hipMemcpy(&ph, b->d_phase[b->pcur] + id, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+  if (hipMemcpy(&ph, b->d_phase[b->ahead.pcur] + id, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
   *re = ph.x;
   *im = ph.y;
   return 0;

@@ -511,7 +511,7 @@ XlReserve xl_reserve_want(const XlPlanOpts &o, size_t nclients, const std::vecto
                           bool exp_rounds1, int exp_reserve) {
   const uint32_t nwg = ((uint32_t)nclients + 63u) / 64u;
   const bool light = xl_direct_is_light(macs_all * o.max_samples) || (!poly.empty() && xl_direct_is_light(macs_rest * o.max_samples));
-  // (one-block calls of a polyphase plan take the side stream too, up to XL_SIDE_ONE_BLOCK_MAX clients: see side_call)
+  // (one-block calls of a polyphase plan take the side stream too, up to XL_SIDE_ONE_BLOCK_MAX clients: xl_side_call, xl_plan.h)
   const bool one_block_side = !poly.empty() && nclients <= XL_SIDE_ONE_BLOCK_MAX;
   // (a server that knows how many clients it admits says so -- option "expected_clients" --, and the reservation is made for
   // that many at once: the 25 ms of a stream re-creation then never fall on a call between two joins)
@@ -535,7 +535,7 @@ XlReserve xl_reserve_want(const XlPlanOpts &o, size_t nclients, const std::vecto
   load_wgs = xl_chain_load_with_hysteresis(load_wgs, last_band);
   const bool side_plan = (o.gcap >= 2 || one_block_side) && (!poly.empty() || light || o.nco_side > 0) && o.nco_side != 0;
   // (the no-reservation band and the rounds were measured on polyphase plans only; a direct-only plan -- whose side-stream chain needs
-  // the masked pair, see side_call -- keeps one CU per chain workgroup, up to half the chip)
+  // the masked pair, see xl_side_call -- keeps one CU per chain workgroup, up to half the chip)
   uint32_t want = !side_plan ? 0u : (poly.empty() ? ((nwg_res + 7u) / 8u <= 16u ? (nwg_res + 7u) / 8u : 0u) : xl_chain_reserve_per_xcd(nwg_res, load_wgs));
   // A wide two-half class (9 .. 14 k-blocks: xl_mixh2.hip) runs two workgroups per CU and launches M x column groups of them -- a
   // multiple of 512 at every 512 clients: on the 240 CUs a reservation of 16 leaves, BASELINE config 5 at 1024 clients took a third,

@@ -138,6 +138,24 @@ static inline void xl_clients_commit(std::vector<Client> &clients, uint32_t S, u
 // 1024 x 505 native (1615 M) 203 -> 227.
 static inline bool xl_direct_is_light(double macs_per_block) { return macs_per_block < 250e6; }
 
+// Who tabulates the NEXT call's phases: the NCO role inside this call's launches (false), or xl_nco_chain_kernel on the side
+// stream, concurrently with them (true).  q15: a Q15 call (its family has a look-ahead of its own); nco_side: option
+// "nco_side_stream"; light: xl_direct_is_light of the call's direct launches; masked_pair: the CU-masked stream pair exists;
+// engine_stream: the call runs on the engine's stream (a caller's own, unmasked stream would keep filling the chain's CUs).
+// The side stream pays for calls of several blocks on the polyphase path, whose three launches are short against the chain
+// (measured, 8 blocks per call: 42.7 -> 36.8 us per block at 1024 clients, 30.7 -> 28.8 at 128); a direct FIR launch hides the
+// chain in its spare waves for free and would only lose the chain kernel's CUs (1024 clients, native: 203 -> 212 us per block),
+// and with one block per call the cross-stream events cost more than the overlap gains (51.3 -> 58.6).
+// One-block calls (the reference's call granularity) on the polyphase path: the three launches are short since the mix runs on
+// the matrix cores, and a slice of the recurrence inside each made every one of them last as long as its slice (1024 clients:
+// 50.2 us per block; the chain kernel beside them, four calls per launch: 47.7; 128 clients: 40.4 -> 29.2; 4096: 129 -> 134,
+// hence the limit XL_SIDE_ONE_BLOCK_MAX).
+static inline bool xl_side_call(bool q15, int nco_side, unsigned G, bool use_poly, size_t nclients, bool light, bool masked_pair,
+                                bool engine_stream) {
+  const bool one_block_side = G == 1 && use_poly && nclients <= XL_SIDE_ONE_BLOCK_MAX;
+  return !q15 && (nco_side > 0 || (nco_side < 0 && (G >= 2 || one_block_side) && (use_poly || (light && masked_pair && engine_stream))));
+}
+
 // ---- direct launches
 extern const int kHeights[XL_NLAUNCH];
 bool xl_riders_window(size_t wgs, int nw, uint32_t Tpad, int ct, uint32_t K, size_t lds, int min_wgs);

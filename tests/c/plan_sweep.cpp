@@ -687,7 +687,39 @@ static void height_and_reservation(void) {
   CHECK(xl_reserve_recreate(2, 4) && xl_reserve_recreate(0, 1) && !xl_reserve_recreate(0, 0));
 }
 
+// ---- the per-call side / fused rule (xl_side_call) at its edges
+static void side_rule(void) {
+  const size_t at = XL_SIDE_ONE_BLOCK_MAX;
+  // arguments: q15, nco_side, G, use_poly, nclients, light, masked_pair, engine_stream
+  for (int nco_side = -1; nco_side <= 1; ++nco_side)  // Q15 calls: never
+    for (unsigned G : {1u, 2u, 8u})
+      for (int bits = 0; bits < 16; ++bits)
+        CHECK(!xl_side_call(true, nco_side, G, (bits & 1) != 0, (bits & 2) ? at + 1 : 64, (bits & 4) != 0, (bits & 8) != 0, true));
+  for (unsigned G : {1u, 2u, 8u})
+    for (int bits = 0; bits < 32; ++bits) {
+      const bool poly = (bits & 1) != 0, light = (bits & 2) != 0, pair = (bits & 4) != 0, eng = (bits & 8) != 0;
+      const size_t n = (bits & 16) ? at + 1 : at;
+      CHECK(!xl_side_call(false, 0, G, poly, n, light, pair, eng));  // option 0: never
+      CHECK(xl_side_call(false, 1, G, poly, n, light, pair, eng));   // option 1: every float call
+    }
+  // option -1, polyphase calls: several blocks always, one block up to XL_SIDE_ONE_BLOCK_MAX clients, whatever the stream
+  for (int bits = 0; bits < 8; ++bits) {
+    const bool light = (bits & 1) != 0, pair = (bits & 2) != 0, eng = (bits & 4) != 0;
+    CHECK(xl_side_call(false, -1, 2, true, at + 1, light, pair, eng));
+    CHECK(xl_side_call(false, -1, 1, true, at, light, pair, eng));
+    CHECK(!xl_side_call(false, -1, 1, true, at + 1, light, pair, eng));
+    CHECK(!xl_side_call(false, -1, 1, false, at, light, pair, eng));  // (a one-block direct call: never)
+  }
+  // option -1, direct-only calls of several blocks: light ones, with the masked pair, on the engine's stream only
+  for (int bits = 0; bits < 8; ++bits) {
+    const bool light = (bits & 1) != 0, pair = (bits & 2) != 0, eng = (bits & 4) != 0;
+    CHECK(xl_side_call(false, -1, 2, false, 64, light, pair, eng) == (light && pair && eng));
+  }
+  CHECK(xl_direct_is_light(249.9e6) && !xl_direct_is_light(250e6));
+}
+
 int main(void) {
+  side_rule();
   XlPlanOpts o = default_opts(16384, 4);
   churn(o, CHURN_STEPS);  // the size rule: classes of 32 members and more
   o.poly_mode = 1;
