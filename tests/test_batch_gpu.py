@@ -471,11 +471,14 @@ def test_polyphase_matrix_core_mix_tap_scales_and_full_scale_input(m, mix, monke
 @pytest.mark.parametrize("mix", [1, 3], ids=["mfma", "f32-mfma"])
 @pytest.mark.parametrize("D,fs", [(12, 576000), (33, 1584000), (50, 2400000), (64, 3072000)])
 def test_polyphase_matrix_core_mix_other_branch_counts(D, fs, mix, monkeypatch):
-    """The two-half matrix-core mix is built per number of k-blocks of 8 branches (1..8): the server default is 6 (D = 42), the
-    fixture shapes cover 1 (D = 5) and 3 (D = 21); here 2, 5, 7 and 8 (the last two keep a few operand registers in scratch) -- 48 kHz
-    clients off other sample rates, 12 taps per branch, both transform lengths by the size rule's forcing, every client vs the
-    oracle.  The float32 matrix-core mix (mix = 3, xl_mixf32.hip) is built per number of k-blocks whose operands stay in registers
-    (1..14; D = 100 and D = 400 -- the streaming kernel -- run in test_polyphase_forced_other_shapes)."""
+    """The two-half matrix-core mix is built per number of k-blocks of 8 branches (1..8 in xl_mixh.hip): the server default is 6
+    (D = 42), the fixture shapes cover 1 (D = 5) and 3 (D = 21); here 2, 5, 7 and 8 (the last two keep a few operand registers in
+    scratch) -- 48 kHz clients off other sample rates, 12 taps per branch, both transform lengths by the size rule's forcing, every
+    client vs the oracle.  The float32 matrix-core mix (mix = 3, xl_mixf32.hip) is built per number of k-blocks whose operands stay
+    in registers (1..14): the same four counts here, 13 (D = 100) and the streaming kernel (D = 400) in
+    test_polyphase_forced_other_shapes.  NOT covered by these shapes: count 4 of either mix, the wide two-half kernel's 9..12 and
+    14 (xl_mixh2.hip) and the float32 mix's 9..12 and 14 -- tests/test_mix_kblocks_gpu.py holds EVERY count of every mix kernel to
+    the oracle (tests/mix_kblock_cases.py: the table, pinned to the dispatch switches by tests/test_mix_kblocks_cpu.py)."""
     monkeypatch.setenv("XL_EXP_MIX", str(mix))
     taps = lpf(fs, 24000, fs // 210)
     assert len(taps) >= 9 * D // 2

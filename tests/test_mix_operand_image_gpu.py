@@ -14,15 +14,10 @@ import pytest
 
 import siggen
 import sdr_server_amd as xl
-from pyoracle import Oracle, population
+from mix_harness import ELEMS, FS, NCALLS, REL_TOL, _fcs, _rel_err, _run, _stream, population  # (shared with test_mix_kblocks_gpu.py)
+from pyoracle import Oracle
 
 pytestmark = pytest.mark.gpu
-
-FS = 2016000
-NSAMP = 16384          # samples per block
-ELEMS = 2 * NSAMP      # scalar elements per block = bytes of a cu8 block
-REL_TOL = 1e-5
-NCALLS = 3
 
 
 def _taps(ntaps):
@@ -31,44 +26,6 @@ def _taps(ntaps):
         assert code == 0 and t.size == 505
         return t
     return siggen.hamming_sinc(ntaps, 0.45 / {253: 21, 769: 64}[ntaps])
-
-
-def _stream(fmt, nblocks, seed):
-    n = ELEMS * nblocks
-    if fmt == "cu8":
-        return siggen.xs_u8(seed, n)
-    if fmt == "cs8":
-        return siggen.xs_s8(seed, n)
-    if fmt == "cs16":
-        return siggen.xs_s16(seed, n)
-    return (siggen.xs_s16(seed, n).astype(np.float32) / np.float32(32768)).astype(np.float32)
-
-
-def _fcs(nclients):
-    return [int(-0.45 * FS + (0.9 * FS / nclients) * c) + 17 * (c % 5) for c in range(nclients)]
-
-
-def _run(fmt, D, taps, fcs, m, image, x, nblocks, ncalls=NCALLS):
-    """One engine over ncalls calls of nblocks blocks: per client the concatenated outputs, and the plan's description."""
-    eng = xl.BatchEngine(FS, fmt, ELEMS, group_blocks=max(nblocks, 1))
-    eng.set_option("mix_operand_image", image)
-    if m:
-        eng.set_option("polyphase_m", m)
-    ids = [eng.add_client(D, taps, fc) for fc in fcs]
-    outs = [[] for _ in ids]
-    per_call = ELEMS * nblocks
-    for k in range(ncalls):
-        eng.process_host_group(x[k * per_call:(k + 1) * per_call], nblocks, "optimized")
-        eng.fetch()
-        for c, i in enumerate(ids):
-            outs[c].append(eng.output(i).copy())
-    d = eng.describe()
-    eng.close()
-    return [np.concatenate(o) for o in outs], d
-
-
-def _rel_err(a, b):
-    return float(np.abs(a.astype(np.complex128) - b.astype(np.complex128)).max() / max(np.abs(b).max(), 1e-30))
 
 
 # (D, taps, format, clients, blocks per call, transform length: 0 = the size rule's 256 points)
