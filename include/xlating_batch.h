@@ -192,6 +192,10 @@ int xlating_batch_output_host(xlating_batch *batch, int client_id, const float *
 int xlating_batch_output_host_cs16(xlating_batch *batch, int client_id, const int16_t **output, size_t *output_len);
 /* Device pointer to the client's last-block output (valid until the next process call). */
 int xlating_batch_output_device(xlating_batch *batch, int client_id, const void **d_output, size_t *output_len);
+/* The same for n clients in one call: d_outputs[i], output_lens[i] are what xlating_batch_output_device answers for client_ids[i]
+ * (float pairs of 8 bytes, or int16 pairs of 4 after an XL_MODE_Q15 call; NULL and 0 for a client that joined since the latest call).
+ * A host-side lookup: no device work.  0, or -EINVAL if any id is dead (or would be refused by the single call): nothing is filled. */
+int xlating_batch_outputs_device(xlating_batch *batch, size_t n, const int *client_ids, const void **d_outputs, size_t *output_lens);
 
 /* Current NCO phase of a client (synchronises the engine stream). */
 int xlating_batch_client_phase(xlating_batch *batch, int client_id, float *re, float *im);

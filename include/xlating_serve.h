@@ -1,0 +1,108 @@
+/*
+ * include/xlating_serve.h -- the whole loop in one object: one band on one GPU, from a client's wire request to the bytes in its file
+ * or socket.
+ *
+ * What a server's sdr_callback does with the pieces of this project -- admission (xlating_wire.h), the batch engine (xlating_batch.h),
+ * the second stage of clients whose rate does not divide the band rate (xlating_resample.h, xlating_resample_q15.h), delivery
+ * (xlating_delivery.h) and the writer threads (xlating_sinks.h) -- is done here, in C, behind about ten calls:
+ *
+ *     xlating_serve_create(&cfg, &s);
+ *     xlating_serve_request(s, msg, len, fd, response, &rlen, &id);     // per client message; send `response` back
+ *     xlating_serve_blocks_host(s, iq, input_len, nblocks);             // per device callback (or _blocks_device)
+ *     n = xlating_serve_dropped(s, ids, cap);                           // clients whose peer failed or fell behind: close them
+ *     xlating_serve_remove(s, id);                                      // a client that left
+ *     xlating_serve_flush(s); xlating_serve_destroy(s);
+ *
+ * Per blocks call: the engine call in the configured mode; one resampler-bank feed for the fractional clients (pointers from
+ * xlating_batch_outputs_device); ONE delivery batch holding the final row of every client (key: the client id; 8 bytes a sample in the
+ * cf32 family, 4 in the cs16 family), which is one launch and one device-to-host copy of exactly those bytes.  xlating_batch_fetch and
+ * the banks' _fetch are never called: a fractional client's engine row never crosses to the host, and after an XL_MODE_Q15 call only
+ * the int16 pairs do.  With overlap = 0 the call waits for that copy and queues the rows to the sinks before it returns; with
+ * overlap = 1 it queues the PREVIOUS call's rows, whose copy ran beside this call's launches, and the latest call's rows are queued by
+ * the next call, by xlating_serve_flush or by xlating_serve_remove of a client that has some.  Per client the bytes written are
+ * exactly the stream of the engine (an integer-rate client) or of the bank fed from the engine (a fractional client): the object adds
+ * no arithmetic.
+ *
+ * Ordering: the feed and the pack launch run on a stream of the object's own, behind an event recorded behind the engine call
+ * (xlating_batch_record_event); the next engine call is ordered behind an event recorded behind the pack launch (a device call waits
+ * for it on its stream, xlating_batch_process_device_group_ev; a host call waits for it on the host, as it does for the previous
+ * call), so the rows are read before they are rewritten; the bank's next feed is on the same stream as the pack launch before it.
+ *
+ * Memory: the delivery object's, delivery_slots x the largest call's rows on the device and pinned (xlating_delivery.h).
+ * Not thread-safe: one thread at a time per object.
+ */
+#ifndef SDR_SERVER_AMD_XLATING_SERVE_H_
+#define SDR_SERVER_AMD_XLATING_SERVE_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct xlating_serve_t xlating_serve;
+struct xlating_batch_t;
+
+enum { XL_SERVE_CF32 = 0, XL_SERVE_CS16 = 1 };
+
+typedef struct {
+  uint32_t band_sampling_rate;
+  int input_format;        /* XL_FMT_* (xlating_batch.h) */
+  uint32_t buffer_size;    /* bytes of a cu8 block: the engine's max_input_buffer_length */
+  unsigned group_blocks;   /* most blocks per call, 1 .. 64 (0: 1) */
+  int device;              /* HIP device ordinal, or -1 for the calling thread's current device */
+  int family;              /* XL_SERVE_CF32 | XL_SERVE_CS16 (XL_MODE_Q15 + the Q15 resampler bank) */
+  int native;              /* cf32 family: XL_MODE_NATIVE instead of XL_MODE_OPTIMIZED */
+  int any_rate;            /* admit through xlating_wire_admit_any_rate */
+  uint32_t lpf_cutoff_rate; /* (0: 5, the reference's default) */
+  const char *base_path;   /* FILE destinations: <base_path>/<id>.<cf32|cs16>[.gz]; copied */
+  int use_gzip;
+  unsigned writer_threads; /* (0: 2) */
+  size_t queue_bytes;      /* per client, allocated when its sink is attached; a row that does not fit drops the client
+                            * (0: 8 calls of a client at a quarter of the band rate = 8 x group_blocks x (buffer_size / 8 + 64) x 8 bytes;
+                            * set it from the rates you serve: 1024 clients cost 1024 x queue_bytes of host memory) */
+  unsigned delivery_slots; /* 2 .. 16 (0: 2) */
+  int overlap;             /* 0: a block's rows reach the sinks before its call returns; 1: during the next call / flush */
+} xlating_serve_config;
+
+/* 0, -EINVAL, -ENODEV, -ENOMEM, -EIO. */
+int xlating_serve_create(const xlating_serve_config *cfg, xlating_serve **out);
+
+/* One client message as it came off the socket: header + request.  The call parses it, admits it against the band of the clients
+ * running (0 if none), designs the taps, adds the engine client and, for a rate that does not divide, the second stage, and attaches
+ * the sink: FILE -> <base_path>/<id>.<cf32|cs16>[.gz]; SOCKET -> socket_fd, owned by the caller.  It writes the response bytes the
+ * reference's server would send: SUCCESS + id, FAILURE + INVALID_REQUEST / OUT_OF_BAND_FREQ, or FAILURE + INTERNAL_ERROR after
+ * undoing what it had added.  Returns 0 admitted (*client_id set), 1 refused (a response was written); -EAGAIN / -EPROTO from the wire
+ * parsers (also -EPROTO: a message that is no request), -EINVAL: no response was written. */
+int xlating_serve_request(xlating_serve *s, const uint8_t *msg, size_t len, int socket_fd, uint8_t response[7], size_t *response_len,
+                          int *client_id);
+/* A client that left: what it is still owed (overlap = 1) is queued first, then its queue is flushed and its file closed.  0, -EINVAL. */
+int xlating_serve_remove(xlating_serve *s, int client_id);
+
+/* nblocks consecutive blocks of input_len scalar elements each, back to back (xlating_batch_process_*_group).  0, or the engine's,
+ * the bank's or the delivery's error. */
+int xlating_serve_blocks_host(xlating_serve *s, const void *input, size_t input_len, unsigned nblocks);
+int xlating_serve_blocks_device(xlating_serve *s, const void *d_input, size_t input_len, unsigned nblocks, void *hip_stream);
+/* Everything processed so far has reached the OS, or its sink has failed. */
+int xlating_serve_flush(xlating_serve *s);
+
+/* The rows the latest call delivered, at each client's FINAL rate: an integer-rate client's engine row, a fractional client's bank
+ * row -- the arguments of xlating_spectrum_bank_feed_device.  Valid until the next blocks call; the feed that reads them must be
+ * ordered by the caller before it (e.g. synchronised).  0, -EINVAL (an id that is not a client: nothing is filled). */
+int xlating_serve_outputs_device(xlating_serve *s, size_t n, const int *client_ids, const void **d_rows, size_t *n_complex);
+/* Clients removed because their sink failed or overflowed (engine, bank and sinks), each reported once; returns how many were stored. */
+size_t xlating_serve_dropped(xlating_serve *s, int *client_ids, size_t cap);
+/* The sinks' totals since creation (xlating_sinks_stats): bytes handed to the OS / zlib, and rows refused because a sink had failed. */
+int xlating_serve_sink_stats(xlating_serve *s, uint64_t *bytes_written, uint64_t *blocks_dropped);
+/* The engine: options, describe, timing.  Clients are added and removed through this object only. */
+struct xlating_batch_t *xlating_serve_engine(xlating_serve *s);
+/* What the latest blocks call issued behind the engine call: kernel launches (the bank's feed, the pack), memory copies, and the
+ * bytes of the device-to-host copy. */
+int xlating_serve_last_ops(const xlating_serve *s, unsigned *launches_after_engine, unsigned *copies_after_engine, uint64_t *d2h_bytes);
+void xlating_serve_destroy(xlating_serve *s);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SDR_SERVER_AMD_XLATING_SERVE_H_ */

@@ -43,11 +43,17 @@ int xlating_sinks_attach_fd(xlating_sinks *sinks, int client_id, int fd, int clo
 /* Deliver client_id's stream to <base_path>/<client_id>.cf32 (use_gzip == 0) or <base_path>/<client_id>.cf32.gz
  * (dsp_worker.c:126-144).  0, -EINVAL, -EEXIST, -ENOMEM, or -errno of the failed open. */
 int xlating_sinks_attach_file(xlating_sinks *sinks, int client_id, const char *base_path, int use_gzip);
+/* The same, to <base_path>/<client_id>.<ext>[.gz]; ext: "cf32", or "cs16" for a client of the cs16 output family (raw interleaved
+ * int16 pairs).  attach_file is attach_file_as with "cf32".  Any other ext: -EINVAL. */
+int xlating_sinks_attach_file_as(xlating_sinks *sinks, int client_id, const char *base_path, const char *ext, int use_gzip);
 
 /* Queue n_complex samples (interleaved re, im) for client_id.  The data is copied; the call never blocks on the
  * peer.  0; -ENOENT (no such sink); -EPIPE (the sink has failed, or this block does not fit its queue: the sink
  * is marked failed and will be reported by xlating_sinks_failed). */
 int xlating_sinks_write(xlating_sinks *sinks, int client_id, const float *samples, size_t n_complex);
+/* The same for `bytes` bytes of any sample type (cs16 clients: 4 bytes a sample); write is write_bytes of n_complex * 8.  Queueing,
+ * back-pressure and failure are those of xlating_sinks_write. */
+int xlating_sinks_write_bytes(xlating_sinks *sinks, int client_id, const void *data, size_t bytes);
 
 /* After xlating_batch_fetch(): queue the latest output block of every attached client of `engine` (clients that
  * are not alive in the engine are skipped).  Returns the number of blocks queued, or -EINVAL. */

@@ -52,12 +52,12 @@ EXPORTED_SYMBOLS = (
     + ["xlating_batch_create", "xlating_batch_create_grouped", "xlating_batch_set_option", "xlating_batch_q15_matrix_admits", "xlating_batch_process_host_group",
        "xlating_batch_process_device_group", "xlating_batch_process_device_group_ev", "xlating_batch_output_len_block", "xlating_batch_add_client", "xlating_batch_remove_client", "xlating_batch_num_clients",
        "xlating_batch_process_host", "xlating_batch_process_device", "xlating_batch_output_len", "xlating_batch_fetch",
-       "xlating_batch_output_host", "xlating_batch_output_host_cs16", "xlating_batch_output_device", "xlating_batch_client_phase", "xlating_batch_client_phase_q15", "xlating_batch_sync",
+       "xlating_batch_output_host", "xlating_batch_output_host_cs16", "xlating_batch_output_device", "xlating_batch_outputs_device", "xlating_batch_client_phase", "xlating_batch_client_phase_q15", "xlating_batch_sync",
        "xlating_batch_query", "xlating_batch_record_event", "xlating_batch_timing", "xlating_batch_timing_read", "xlating_batch_timing_polyphase", "xlating_batch_timing_stride", "xlating_batch_describe", "xlating_batch_destroy",
        "xlating_hip_device_info"]
     + ["xlating_sinks_create", "xlating_sinks_attach_fd", "xlating_sinks_attach_file", "xlating_sinks_write",
        "xlating_sinks_submit", "xlating_sinks_failed", "xlating_sinks_flush", "xlating_sinks_detach", "xlating_sinks_stats",
-       "xlating_sinks_destroy"]
+       "xlating_sinks_destroy", "xlating_sinks_attach_file_as", "xlating_sinks_write_bytes"]
     + ["xlating_wire_parse_header", "xlating_wire_parse_request", "xlating_wire_build_request", "xlating_wire_build_response",
        "xlating_wire_build_header", "xlating_wire_parse_response", "xlating_wire_admit", "xlating_wire_add_client",
        "xlating_wire_admit_any_rate", "xlating_wire_resample_taps"]
@@ -192,6 +192,8 @@ def lib():
     L.xlating_batch_output_host_cs16.restype = C.c_int
     L.xlating_batch_output_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.xlating_batch_output_device.restype = C.c_int
+    L.xlating_batch_outputs_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.xlating_batch_outputs_device.restype = C.c_int
     L.xlating_batch_client_phase.argtypes = [C.c_void_p, C.c_int, _c_float_p, _c_float_p]
     L.xlating_batch_client_phase.restype = C.c_int
     L.xlating_batch_client_phase_q15.argtypes = [C.c_void_p, C.c_int, _c_i16_p, _c_i16_p]
@@ -210,6 +212,10 @@ def lib():
     L.xlating_sinks_attach_file.restype = C.c_int
     L.xlating_sinks_write.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.xlating_sinks_write.restype = C.c_int
+    L.xlating_sinks_attach_file_as.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int]
+    L.xlating_sinks_attach_file_as.restype = C.c_int
+    L.xlating_sinks_write_bytes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    L.xlating_sinks_write_bytes.restype = C.c_int
     L.xlating_sinks_submit.argtypes = [C.c_void_p, C.c_void_p]
     L.xlating_sinks_submit.restype = C.c_int
     L.xlating_sinks_failed.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_size_t]
@@ -456,6 +462,15 @@ class BatchEngine:
             raise XlatingError("xlating_batch_output_device", code)
         return p.value, n.value
 
+    def outputs_device(self, cids):
+        """-> (device pointers uint64 [n], lengths uint64 [n]): output_device of every listed client, in one call"""
+        a = np.ascontiguousarray(cids, dtype=np.intc)
+        p, n = np.zeros(a.size, np.uint64), np.zeros(a.size, np.uint64)
+        code = lib().xlating_batch_outputs_device(self.h, a.size, a.ctypes.data, p.ctypes.data, n.ctypes.data)
+        if code != 0:
+            raise XlatingError("xlating_batch_outputs_device", code)
+        return p, n
+
     def phase(self, cid):
         a, b = C.c_float(), C.c_float()
         code = lib().xlating_batch_client_phase(self.h, cid, C.byref(a), C.byref(b))
@@ -657,9 +672,18 @@ class Sinks:
     def attach_file(self, client_id, base_path, use_gzip=False):
         return lib().xlating_sinks_attach_file(self.h, client_id, str(base_path).encode(), 1 if use_gzip else 0)
 
+    def attach_file_as(self, client_id, base_path, ext, use_gzip=False):
+        """<base_path>/<client_id>.<ext>[.gz]; ext: "cf32" or "cs16" (any other: -EINVAL)"""
+        return lib().xlating_sinks_attach_file_as(self.h, client_id, str(base_path).encode(), ext.encode(), 1 if use_gzip else 0)
+
     def write(self, client_id, samples):
         a = np.ascontiguousarray(samples, dtype=np.complex64)
         return lib().xlating_sinks_write(self.h, client_id, a.ctypes.data_as(C.c_void_p), a.size)
+
+    def write_bytes(self, client_id, data):
+        """data: bytes, or an array whose bytes are queued as they are"""
+        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        return lib().xlating_sinks_write_bytes(self.h, client_id, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size)
 
     def submit(self, engine):
         return lib().xlating_sinks_submit(self.h, engine.h)
@@ -926,13 +950,8 @@ class SpectrumBank:
     @staticmethod
     def gather_engine(engine, streams):
         """-> (stream ids, device pointers, counts) of the listed clients' outputs of the engine's latest call"""
-        ids, ptrs, counts = [], [], []
-        for cid, sid in streams.items():
-            p, n = engine.output_device(cid)
-            ids.append(sid)
-            ptrs.append(p or 0)
-            counts.append(n)
-        return ids, ptrs, counts
+        ptrs, counts = engine.outputs_device(list(streams.keys()))  # (one call: xlating_batch_outputs_device)
+        return list(streams.values()), ptrs, counts
 
     def take_rows(self, stream_id, max_rows=1 << 20):
         """-> (db float32 [R, W], pixels uint8 [R, W]): the stream's completed rows not taken yet, oldest first."""
@@ -1176,3 +1195,241 @@ class ResamplerBankQ15(ResamplerBank):
         if n.value == 0:
             return np.zeros((0, 2), np.int16)
         return np.ctypeslib.as_array(p, shape=(n.value, 2)).copy()
+
+
+# ------------------------------------------------------------------------------------------------- delivery and serve (libxlating_serve.so)
+DELIVERY_SYMBOLS = ["xlating_delivery_create", "xlating_delivery_pack_device", "xlating_delivery_query", "xlating_delivery_wait",
+                    "xlating_delivery_row", "xlating_delivery_release", "xlating_delivery_last_ops", "xlating_delivery_chunk_bytes",
+                    "xlating_delivery_destroy"]
+SERVE_SYMBOLS = ["xlating_serve_create", "xlating_serve_request", "xlating_serve_remove", "xlating_serve_blocks_host",
+                 "xlating_serve_blocks_device", "xlating_serve_flush", "xlating_serve_outputs_device", "xlating_serve_dropped",
+                 "xlating_serve_engine", "xlating_serve_last_ops", "xlating_serve_sink_stats", "xlating_serve_destroy"]
+SERVE_FAMILY = {"cf32": 0, "cs16": 1}
+_vlib = None
+
+
+class ServeConfig(C.Structure):
+    """include/xlating_serve.h xlating_serve_config"""
+    _fields_ = [("band_sampling_rate", C.c_uint32), ("input_format", C.c_int), ("buffer_size", C.c_uint32), ("group_blocks", C.c_uint),
+                ("device", C.c_int), ("family", C.c_int), ("native", C.c_int), ("any_rate", C.c_int), ("lpf_cutoff_rate", C.c_uint32),
+                ("base_path", C.c_char_p), ("use_gzip", C.c_int), ("writer_threads", C.c_uint), ("queue_bytes", C.c_size_t),
+                ("delivery_slots", C.c_uint), ("overlap", C.c_int)]
+
+
+def serve_library_path():
+    return os.path.join(os.path.dirname(library_path()), "libxlating_serve.so")
+
+
+def serve_lib():
+    """include/xlating_delivery.h and include/xlating_serve.h: delivery of device rows, and the whole loop in one object."""
+    global _vlib
+    if _vlib is not None:
+        return _vlib
+    resample_lib()  # (torch's HIP runtime first, see lib(); the libraries this one links)
+    path = serve_library_path()
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    V = C.CDLL(path)
+    V.xlating_delivery_create.argtypes = [C.c_uint, C.POINTER(C.c_void_p)]
+    V.xlating_delivery_create.restype = C.c_int
+    V.xlating_delivery_pack_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_delivery_pack_device.restype = C.c_int
+    for name in ("xlating_delivery_query", "xlating_delivery_wait", "xlating_delivery_release"):
+        getattr(V, name).argtypes = [C.c_void_p, C.c_int]
+        getattr(V, name).restype = C.c_int
+    V.xlating_delivery_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    V.xlating_delivery_row.restype = C.c_int
+    V.xlating_delivery_last_ops.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint64)]
+    V.xlating_delivery_last_ops.restype = C.c_int
+    V.xlating_delivery_chunk_bytes.argtypes = []
+    V.xlating_delivery_chunk_bytes.restype = C.c_uint
+    V.xlating_delivery_destroy.argtypes = [C.c_void_p]
+    V.xlating_delivery_destroy.restype = None
+    V.xlating_serve_create.argtypes = [C.POINTER(ServeConfig), C.POINTER(C.c_void_p)]
+    V.xlating_serve_create.restype = C.c_int
+    V.xlating_serve_request.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    V.xlating_serve_request.restype = C.c_int
+    V.xlating_serve_remove.argtypes = [C.c_void_p, C.c_int]
+    V.xlating_serve_remove.restype = C.c_int
+    V.xlating_serve_blocks_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint]
+    V.xlating_serve_blocks_host.restype = C.c_int
+    V.xlating_serve_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]
+    V.xlating_serve_blocks_device.restype = C.c_int
+    V.xlating_serve_flush.argtypes = [C.c_void_p]
+    V.xlating_serve_flush.restype = C.c_int
+    V.xlating_serve_outputs_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_serve_outputs_device.restype = C.c_int
+    V.xlating_serve_dropped.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_size_t]
+    V.xlating_serve_dropped.restype = C.c_size_t
+    V.xlating_serve_engine.argtypes = [C.c_void_p]
+    V.xlating_serve_engine.restype = C.c_void_p
+    V.xlating_serve_last_ops.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint64)]
+    V.xlating_serve_last_ops.restype = C.c_int
+    V.xlating_serve_sink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    V.xlating_serve_sink_stats.restype = C.c_int
+    V.xlating_serve_destroy.argtypes = [C.c_void_p]
+    V.xlating_serve_destroy.restype = None
+    _vlib = V
+    return V
+
+
+def delivery_chunk_bytes():
+    return serve_lib().xlating_delivery_chunk_bytes()
+
+
+class Delivery:
+    """One `xlating_delivery *` (include/xlating_delivery.h): batches of device rows packed by one launch and moved to pinned host
+    memory by one copy each; tickets are waited for, read per key and released."""
+
+    def __init__(self, slots=2):
+        h = C.c_void_p()
+        code = serve_lib().xlating_delivery_create(slots, C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_delivery_create", code)
+        self.h = h
+
+    def pack(self, keys, ptrs, nbytes, stream=0):
+        """row i: nbytes[i] bytes at device address ptrs[i], tagged keys[i] -> a ticket (XlatingError: -EAGAIN, -EINVAL, ...)"""
+        k = np.ascontiguousarray(keys, dtype=np.intc)
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        b = np.ascontiguousarray(nbytes, dtype=np.uint64)
+        assert k.size == p.size == b.size
+        t = serve_lib().xlating_delivery_pack_device(self.h, k.size, k.ctypes.data, p.ctypes.data, b.ctypes.data, stream)
+        if t < 0:
+            raise XlatingError("xlating_delivery_pack_device", t)
+        return t
+
+    def query(self, ticket):
+        code = serve_lib().xlating_delivery_query(self.h, ticket)
+        if code < 0:
+            raise XlatingError("xlating_delivery_query", code)
+        return bool(code)
+
+    def wait(self, ticket):
+        code = serve_lib().xlating_delivery_wait(self.h, ticket)
+        if code != 0:
+            raise XlatingError("xlating_delivery_wait", code)
+
+    def row(self, ticket, key):
+        """-> uint8 [bytes]: a copy of the row tagged `key` (the ticket is done)"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        code = serve_lib().xlating_delivery_row(self.h, ticket, key, C.byref(p), C.byref(n))
+        if code != 0:
+            raise XlatingError("xlating_delivery_row", code)
+        if n.value == 0:
+            return np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n.value,)).copy()
+
+    def release(self, ticket):
+        code = serve_lib().xlating_delivery_release(self.h, ticket)
+        if code != 0:
+            raise XlatingError("xlating_delivery_release", code)
+
+    def last_ops(self):
+        """-> (kernel launches, memory copies, bytes of the device-to-host copy) of the latest pack"""
+        a, b, c = C.c_uint(0), C.c_uint(0), C.c_uint64(0)
+        serve_lib().xlating_delivery_last_ops(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            serve_lib().xlating_delivery_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Serve:
+    """One `xlating_serve *` (include/xlating_serve.h): one band on one GPU, from wire requests to files and sockets."""
+
+    def __init__(self, band_rate, in_fmt, buffer_size, base_path, family="cf32", native=False, any_rate=True, gzip=False, overlap=False,
+                 group_blocks=1, lpf_cutoff_rate=5, writer_threads=2, queue_bytes=0, delivery_slots=2, device=-1):
+        self._base = str(base_path).encode()
+        cfg = ServeConfig(band_rate, FMT[in_fmt], buffer_size, group_blocks, device, SERVE_FAMILY[family], 1 if native else 0,
+                          1 if any_rate else 0, lpf_cutoff_rate, self._base, 1 if gzip else 0, writer_threads, queue_bytes, delivery_slots,
+                          1 if overlap else 0)
+        h = C.c_void_p()
+        code = serve_lib().xlating_serve_create(C.byref(cfg), C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_serve_create", code)
+        self.h, self.in_fmt, self.family = h, in_fmt, family
+
+    def request(self, msg, socket_fd=-1):
+        """msg: header + request bytes -> (code, response bytes, client id | None); code 0 admitted, 1 refused"""
+        resp, n, cid = C.create_string_buffer(7), C.c_size_t(0), C.c_int(-1)
+        code = serve_lib().xlating_serve_request(self.h, bytes(msg), len(msg), socket_fd, resp, C.byref(n), C.byref(cid))
+        if code < 0:
+            raise XlatingError("xlating_serve_request", code)
+        return code, resp.raw[:n.value], (cid.value if code == 0 else None)
+
+    def remove(self, client_id):
+        code = serve_lib().xlating_serve_remove(self.h, client_id)
+        if code != 0:
+            raise XlatingError("xlating_serve_remove", code)
+
+    def blocks_host(self, x, nblocks=1):
+        x = np.ascontiguousarray(x, dtype=_NP[self.in_fmt])
+        assert x.size % nblocks == 0
+        code = serve_lib().xlating_serve_blocks_host(self.h, x.ctypes.data, x.size // nblocks, nblocks)
+        if code != 0:
+            raise XlatingError("xlating_serve_blocks_host", code)
+
+    def blocks_device(self, d_ptr, input_len, nblocks=1, stream=0):
+        sp = C.c_void_p(-1) if stream == "engine" else (C.c_void_p(stream) if stream else None)
+        code = serve_lib().xlating_serve_blocks_device(self.h, C.c_void_p(d_ptr), input_len, nblocks, sp)
+        if code != 0:
+            raise XlatingError("xlating_serve_blocks_device", code)
+
+    def flush(self):
+        code = serve_lib().xlating_serve_flush(self.h)
+        if code != 0:
+            raise XlatingError("xlating_serve_flush", code)
+
+    def outputs_device(self, cids):
+        """-> (device pointers uint64 [n], complex samples uint64 [n]) of the latest call's final rows"""
+        a = np.ascontiguousarray(cids, dtype=np.intc)
+        p, n = np.zeros(a.size, np.uint64), np.zeros(a.size, np.uint64)
+        code = serve_lib().xlating_serve_outputs_device(self.h, a.size, a.ctypes.data, p.ctypes.data, n.ctypes.data)
+        if code != 0:
+            raise XlatingError("xlating_serve_outputs_device", code)
+        return p, n
+
+    def dropped(self, cap=4096):
+        ids = (C.c_int * cap)()
+        n = serve_lib().xlating_serve_dropped(self.h, ids, cap)
+        return [ids[i] for i in range(n)]
+
+    def engine(self):
+        """The object's BatchEngine (owned by it: do not close it, add or remove clients through it)."""
+        e = BatchEngine.__new__(BatchEngine)
+        e.h = C.c_void_p(serve_lib().xlating_serve_engine(self.h))
+        e.in_fmt = self.in_fmt
+        e.close = lambda: None
+        return e
+
+    def last_ops(self):
+        """-> (launches behind the engine call, copies behind it, bytes of the device-to-host copy) of the latest blocks call"""
+        a, b, c = C.c_uint(0), C.c_uint(0), C.c_uint64(0)
+        serve_lib().xlating_serve_last_ops(self.h, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def sink_stats(self):
+        """-> (bytes handed to the OS / zlib, rows refused by a failed sink) since creation: Sinks.stats of the object's sinks"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        serve_lib().xlating_serve_sink_stats(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            serve_lib().xlating_serve_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1959,6 +1959,23 @@ extern "C" int xlating_batch_output_device(xlating_batch *b, int id, const void 
   return 0;
 }
 
+extern "C" int xlating_batch_outputs_device(xlating_batch *b, size_t n, const int *ids, const void **d_outputs, size_t *output_lens) {
+  if (b == nullptr || (n > 0 && (ids == nullptr || d_outputs == nullptr || output_lens == nullptr))) return -EINVAL;
+  // (checked for every id before anything is filled: what xlating_batch_output_device refuses)
+  if (n > 0 && b->d_out[b->ocur] == nullptr) return -EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    if (ids[i] < 0 || (size_t)ids[i] >= b->clients.size() || !b->clients[ids[i]].alive) return -EINVAL;
+    const Client &c = b->clients[ids[i]];
+    if (c.last_K != 0 && (size_t)c.out_off + c.last_K > b->out_alloc) return -EINVAL;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const Client &c = b->clients[ids[i]];
+    d_outputs[i] = c.last_K == 0 ? nullptr : b->d_out[b->ocur] + c.out_off;
+    output_lens[i] = c.last_K;
+  }
+  return 0;
+}
+
 extern "C" int xlating_batch_client_phase(xlating_batch *b, int id, float *re, float *im) {
   if (b == nullptr || id < 0 || (size_t)id >= b->clients.size() || !b->clients[id].alive) return -EINVAL;
   if (hipSetDevice(b->device) != hipSuccess) return -EIO;

@@ -1,0 +1,15 @@
+// xl_delivery.h -- the delivery object's launch (xl_delivery.hip) as its host side (xl_delivery.cpp) calls it.
+// Internal to libxlating_serve.so; the public interface is include/xlating_delivery.h, the layout xl_delivery_plan.h.
+#ifndef XL_DELIVERY_INTERNAL_H_
+#define XL_DELIVERY_INTERNAL_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "xl_delivery_plan.h"
+
+// runs, stage: device.  chunks: xl_dlv_chunks of the image's size; the launch writes image bytes of rows only, all below that size.
+// 0 or a hipError_t.
+int xl_dlv_launch(const XlDlvRun *runs, uint32_t nruns, uint32_t chunks, void *stage, hipStream_t st);
+
+#endif

@@ -325,7 +325,12 @@ extern "C" int xlating_sinks_attach_fd(xlating_sinks *S, int client_id, int fd, 
 }
 
 extern "C" int xlating_sinks_attach_file(xlating_sinks *S, int client_id, const char *base_path, int use_gzip) {
-  if (S == nullptr || client_id < 0 || base_path == nullptr) return -EINVAL;
+  return xlating_sinks_attach_file_as(S, client_id, base_path, "cf32", use_gzip);
+}
+
+extern "C" int xlating_sinks_attach_file_as(xlating_sinks *S, int client_id, const char *base_path, const char *ext, int use_gzip) {
+  if (S == nullptr || client_id < 0 || base_path == nullptr || ext == nullptr) return -EINVAL;
+  if (strcmp(ext, "cf32") != 0 && strcmp(ext, "cs16") != 0) return -EINVAL;
   {
     Worker *w = xl_worker_of(S, client_id);
     std::lock_guard<std::mutex> g(w->m);
@@ -334,7 +339,7 @@ extern "C" int xlating_sinks_attach_file(xlating_sinks *S, int client_id, const 
   std::unique_ptr<Sink> s(new (std::nothrow) Sink());
   if (!s) return -ENOMEM;
   s->id = client_id;
-  const std::string path = std::string(base_path) + "/" + std::to_string(client_id) + (use_gzip ? ".cf32.gz" : ".cf32");
+  const std::string path = std::string(base_path) + "/" + std::to_string(client_id) + "." + ext + (use_gzip ? ".gz" : "");
   if (use_gzip) {
     s->kind = K_GZ;
     s->gz = gzopen(path.c_str(), "wb");
@@ -358,9 +363,12 @@ extern "C" int xlating_sinks_attach_file(xlating_sinks *S, int client_id, const 
 }
 
 extern "C" int xlating_sinks_write(xlating_sinks *S, int client_id, const float *samples, size_t n_complex) {
-  if (S == nullptr || client_id < 0 || (samples == nullptr && n_complex > 0)) return -EINVAL;
+  return xlating_sinks_write_bytes(S, client_id, samples, n_complex * 2 * sizeof(float));
+}
+
+extern "C" int xlating_sinks_write_bytes(xlating_sinks *S, int client_id, const void *data, size_t n) {
+  if (S == nullptr || client_id < 0 || (data == nullptr && n > 0)) return -EINVAL;
   Worker *w = xl_worker_of(S, client_id);
-  const size_t n = n_complex * 2 * sizeof(float);
   std::unique_lock<std::mutex> lk(w->m);
   auto it = w->sinks.find(client_id);
   if (it == w->sinks.end()) return -ENOENT;
@@ -382,7 +390,7 @@ extern "C" int xlating_sinks_write(xlating_sinks *S, int client_id, const float 
   const size_t cap = s->ring.size();
   const size_t tail = (s->head + s->used) % cap;
   const size_t first = std::min(n, cap - tail);
-  const uint8_t *src = reinterpret_cast<const uint8_t *>(samples);
+  const uint8_t *src = static_cast<const uint8_t *>(data);
   memcpy(s->ring.data() + tail, src, first);
   memcpy(s->ring.data(), src + first, n - first);
   s->used += n;

@@ -1,0 +1,239 @@
+#!/usr/bin/env python3
+"""tools/serve_bench.py -- what the serve object (include/xlating_serve.h) costs and saves at the headline population: 1024 clients x
+48 kHz in a band of 2016000 Hz, the server's own 505-tap filter, cu8, 8 blocks of 262144 bytes per call; both output families.  Every
+client's sink is a pipe, and one reader thread drains them all.
+
+  (a) the pack kernel: HIP events around the pack launch of one call's rows and around a hipMemcpyAsync device-to-device copy of the
+      same bytes, alternating in one process (--pack; run it under `rocprofv3 --kernel-trace --stats` for the kernel's own time)
+  (b) the call period: a host clock around bursts of BURST calls, each burst ending in a flush and a synchronise INSIDE the clock, for
+      three loops alternating in one process, three rounds: the parent's (process_host_group + fetch + sinks.submit), Serve with
+      overlap 0, Serve with overlap 1.  Every loop is timed for the same work: BURST calls, BURST deliveries (with overlap 1 the flush
+      hands the last call's rows over) and the drain of the queues into the pipes.  A burst is what the clients' queues hold, because
+      the sinks cannot take 204 MB per call at the rate the device produces them (nobody is dropped; the tool checks); bursts repeat
+      until at least a second has been timed
+  (c) cs16: the bytes Serve moves to the host per call (counted) against what xlating_batch_fetch copies after a Q15 call (the whole
+      arena in float2-sized rows), and the two call periods
+
+Prints a report; profiles/serve_vs_parent.txt is one run of it on an MI355X."""
+import argparse
+import os
+import select
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("XL_TESTING", "1")
+import numpy as np  # noqa: E402
+
+import sdr_server_amd as xl  # noqa: E402
+
+BAND_RATE, BAND_FREQ, BUFFER, RATE = 2016000, 460100000, 262144, 48000
+
+
+class Drain(threading.Thread):
+    """one thread reading every pipe empty, until closed"""
+
+    def __init__(self):
+        super().__init__(daemon=True)
+        self.poll, self.fds, self.bytes, self.stop = select.epoll(), {}, 0, False
+        self.lock = threading.Lock()
+        self.null = os.open(os.devnull, os.O_WRONLY)
+        self.start()
+
+    def pipes(self, n):
+        """n write ends, made once and shared by the loops that run in turn"""
+        while len(self.fds) < n:
+            self.pipe()
+        with self.lock:
+            return list(self.fds.values())[:n]
+
+    def pipe(self):
+        r, w = os.pipe()
+        os.set_blocking(r, False)
+        try:
+            import fcntl
+            fcntl.fcntl(w, 1031, 1 << 20)  # F_SETPIPE_SZ (best effort: the per-user limit may refuse it)
+        except OSError:
+            pass
+        with self.lock:
+            self.fds[r] = w
+        self.poll.register(r, select.EPOLLIN)
+        return w
+
+    def run(self):
+        while not self.stop:
+            for fd, _ in self.poll.poll(0.05):
+                try:
+                    while True:  # (to /dev/null without a copy through this process)
+                        got = os.splice(fd, self.null, 1 << 20)
+                        if got == 0:
+                            break
+                        self.bytes += got
+                except (BlockingIOError, OSError):
+                    pass
+
+    def close(self):
+        self.stop = True
+        self.join()
+        for r, w in self.fds.items():
+            os.close(r), os.close(w)
+
+
+def centers(n):
+    return [BAND_FREQ - 900000 + (1800000 // n) * c for c in range(n)]
+
+
+def make_serve(n, family, overlap, group, drain, out_dir):
+    s = xl.Serve(BAND_RATE, "cu8", BUFFER, out_dir, family=family, native=False, any_rate=True, overlap=overlap, group_blocks=group,
+                 writer_threads=8, queue_bytes=(BURST + 2) * group * (BUFFER // 2 // 42 + 8) * 8, delivery_slots=2)
+    s.engine().set_option("expected_clients", min(n, 8192))
+    for c, w in zip(centers(n), drain.pipes(n)):
+        code, _, cid = s.request(xl.wire_build_request(c, RATE, BAND_FREQ, 1), socket_fd=w)
+        assert code == 0
+    return s
+
+
+def make_parent(n, variant, group, drain):
+    eng = xl.BatchEngine(BAND_RATE, "cu8", BUFFER, group_blocks=group)
+    eng.set_option("expected_clients", min(n, 8192))
+    sinks = xl.Sinks(writer_threads=8, queue_bytes=(BURST + 2) * group * (BUFFER // 2 // 42 + 8) * 8)
+    for c, w in zip(centers(n), drain.pipes(n)):
+        req = xl.WireRequest(c, RATE, BAND_FREQ, 1)
+        code, adm, why = xl.wire_admit(req, BAND_RATE, 0, 5)
+        assert code == 0
+        cid = xl.wire_add_client(eng, adm, BAND_RATE)
+        assert sinks.attach_fd(cid, w) == 0
+    return eng, sinks
+
+
+BURST = 8  # calls per timed burst; the queues hold BURST + 2 calls
+
+
+def period(step, sync, flush, x, seconds):
+    """seconds per call of `step` over bursts of BURST calls, each ending in `flush` (the hand-over of what is still owed and the
+    sinks' drain) and `sync`, all inside the clock, until `seconds` have been timed"""
+    step(x), step(x), flush(), sync()
+    n, timed = 0, 0.0
+    while timed < seconds:
+        t0 = time.perf_counter()
+        for _ in range(BURST):
+            step(x)
+        flush()
+        sync()
+        timed += time.perf_counter() - t0
+        n += BURST
+    return timed / n, n
+
+
+def run_periods(args, family, drain, out):
+    import torch
+
+    variant = "q15" if family == "cs16" else "optimized"
+    x = np.random.default_rng(1).integers(0, 256, BUFFER * args.group, dtype=np.uint8)
+    eng, sinks = make_parent(args.clients, variant, args.group, drain)
+    serves = {ov: make_serve(args.clients, family, ov, args.group, drain, args.out) for ov in (0, 1)}
+
+    def parent_step(x):
+        eng.process_host_group(x, args.group, variant)
+        eng.fetch()
+        if family == "cf32":
+            sinks.submit(eng)  # (after a Q15 call submit queues nothing: the parent has no cs16 delivery; its loop is engine + fetch)
+
+    loops = {"parent": (parent_step, torch.cuda.synchronize, sinks.flush)}
+    for ov, s in serves.items():
+        loops[f"serve overlap={ov}"] = (lambda x, s=s: s.blocks_host(x, args.group), torch.cuda.synchronize, s.flush)
+    res = {k: [] for k in loops}
+    for rnd in range(args.rounds):
+        for name, (step, sync, flush) in loops.items():
+            res[name].append(period(step, sync, flush, x, args.seconds))
+    out.append(f"[{family}] call period, {args.clients} clients x {RATE} Hz, {args.group} blocks per call, sinks: pipes drained by one thread, bursts of {BURST} calls")
+    for name, rs in res.items():
+        ms = [1e3 * p for p, _ in rs]
+        out.append(f"  {name:18s} ms per call, rounds: " + "  ".join(f"{m:8.3f}" for m in ms) + f"   (calls per round: {[n for _, n in rs]})")
+    pm = [p for p, _ in res["parent"]]
+    spread = (max(pm) - min(pm)) / min(pm)
+    out.append(f"  parent's spread over its rounds: {100 * spread:.1f} %")
+    for name in list(loops)[1:]:
+        r = np.median([p for p, _ in res[name]]) / np.median(pm)
+        out.append(f"  {name}: median period / parent's median = {r:.3f}")
+    dropped = {ov: len(s.dropped()) for ov, s in serves.items()}
+    failed = len(sinks.failed())
+    out.append(f"  clients dropped by back-pressure: parent {failed}, serve {dropped} (a dropped client shortens the calls after it)")
+    d2h = serves[0].last_ops()[2]
+    lens = [eng.output_len(c) for c in range(args.clients)]
+    arena = 8 * sum(lens)  # what the fetch copies: float2-sized rows whatever they hold (a lower bound: rows are padded)
+    out.append(f"  bytes to the host per call: serve {d2h} (counted), parent's fetch >= {arena} (8 x out_total)")
+    for s in serves.values():
+        s.close()
+    sinks.close()
+    eng.close()
+
+
+def run_pack(args, out):
+    """the pack launch of one call's rows against a device-to-device copy of the same bytes"""
+    import torch
+
+    esz, rows = 8, args.group * (BUFFER // 2 // 42)
+    n = args.clients
+    src = torch.randint(0, 256, (n * (rows * esz + 64),), dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    ptrs = [src.data_ptr() + i * (rows * esz + 64) for i in range(n)]
+    d = xl.Delivery(2)
+    st = torch.cuda.Stream()
+    times = {"pack": [], "d2d": []}
+    total = n * rows * esz
+    for it in range(args.pack_iters + 3):
+        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        with torch.cuda.stream(st):
+            a.record()
+            t = d.pack(list(range(n)), ptrs, [rows * esz] * n, st.cuda_stream)
+            b.record()
+            dst[:total].copy_(src[:total], non_blocking=True)
+            c.record()
+        d.wait(t)
+        d.release(t)
+        st.synchronize()
+        if it >= 3:
+            times["pack"].append(a.elapsed_time(b)), times["d2d"].append(b.elapsed_time(c))
+    p, q = np.median(times["pack"]), np.median(times["d2d"])
+    out.append(f"[pack] {n} rows of {rows * esz} bytes = {total / 1e6:.1f} MB; HIP events on the launch stream, median of {args.pack_iters}")
+    out.append(f"  table upload + pack launch: {p:.3f} ms = {2 * total / p / 1e6:.0f} GB/s read + written")
+    out.append(f"  device-to-device copy of the same bytes: {q:.3f} ms = {2 * total / q / 1e6:.0f} GB/s; pack / copy = {p / q:.2f}")
+    d.close()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clients", type=int, default=1024)
+    ap.add_argument("--group", type=int, default=8)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--pack-iters", type=int, default=20)
+    ap.add_argument("--families", default="cf32,cs16")
+    ap.add_argument("--pack", action="store_true", help="only (a): the pack launch against a device-to-device copy")
+    ap.add_argument("--out", default="/tmp/serve_bench_out")
+    ap.add_argument("--report", default=None)
+    a = ap.parse_args(argv)
+    import resource
+
+    soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)  # (two descriptors per client's pipe)
+    resource.setrlimit(resource.RLIMIT_NOFILE, (hard if hard != resource.RLIM_INFINITY else 1 << 16, hard))
+    os.makedirs(a.out, exist_ok=True)
+    out = [f"serve_bench: {xl.device_info()}"]
+    run_pack(a, out)
+    if not a.pack:
+        drain = Drain()
+        for family in a.families.split(","):
+            run_periods(a, family, drain, out)
+        drain.close()
+    text = "\n".join(out)
+    print(text)
+    if a.report:
+        with open(a.report, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

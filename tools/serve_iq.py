@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""tools/serve_iq.py -- tools/replay_iq.py's run through the serve object (include/xlating_serve.h): the same command line, the same
+files, but the loop -- admission, engine, second stage, delivery, sinks -- is the C object's, one call per block:
+
+  python tools/serve_iq.py capture.cu8 --format cu8 --band-rate 2016000 --band-freq 460100000 --out /tmp/out \\
+         --client 460112000:48000 --client 460050000:44100 --any-rate [--gzip] [--overlap] [--variant optimized | native | q15]
+
+Every --client CENTER_HZ:RATE_HZ is sent to the object as the 15-byte wire message and ends up as <out>/<id>.cf32[.gz], or with
+--variant q15 as <out>/<id>.cs16[.gz]: the sinks library writes both families, so --gzip works with q15 here.  With --waterfall-width W
+every admitted client fast enough also gets <out>/<id>.png from a spectrum bank fed with the object's final rows
+(xlating_serve_outputs_device) after every block.  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
+launch and one copy of exactly the delivered bytes."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import numpy as np  # noqa: E402
+
+import replay_iq  # noqa: E402
+import sdr_server_amd as xl  # noqa: E402
+
+DTYPES = replay_iq.DTYPES
+
+
+def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
+           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False):
+    """replay_iq.replay's arguments and its triple: {client_id: (center_hz, rate_hz)} of the admitted requests, [(center, rate,
+    failure_details)] of the refused ones, and the counters -- blocks, and the sinks' own bytes_written and blocks_dropped
+    (xlating_serve_sink_stats: what replay_iq reads from its Sinks objects)."""
+    q15 = variant == "q15"
+    os.makedirs(out_dir, exist_ok=True)
+    serve = xl.Serve(band_rate, fmt, buffer_size, out_dir, family="cs16" if q15 else "cf32", native=variant == "native", any_rate=any_rate,
+                     gzip=gzip, overlap=overlap, lpf_cutoff_rate=lpf_cutoff_rate, writer_threads=writer_threads,
+                     queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
+    eng = serve.engine()
+    if q15:
+        eng.set_option("q15_kernel", q15_kernel)
+        if q15_nco:
+            eng.set_option("q15_nco", q15_nco)
+    bank = xl.SpectrumBank(waterfall_width, "cs16" if q15 else "cf32", wide=waterfall_width > 8192) if waterfall_width else None
+    streams, rows, samples = {}, {}, {}
+    admitted, rejected = {}, []
+    for center, rate in clients:
+        code, resp, cid = serve.request(xl.wire_build_request(center, rate, band_freq, 0))
+        if code != 0:
+            rejected.append((center, rate, xl.wire_parse_response(resp)[2]))
+            continue
+        admitted[cid] = (center, rate)
+        if bank is not None and rate >= waterfall_width:
+            streams[cid], rows[cid], samples[cid] = bank.add(rate), [], 0
+    elem = np.dtype(DTYPES[fmt]).itemsize
+    per_block = buffer_size // elem
+    data = np.fromfile(path, dtype=DTYPES[fmt])
+    nblocks = 0
+    for off in range(0, data.size, per_block):
+        blk = data[off:off + per_block]
+        if blk.size % 2:
+            blk = blk[:-1]
+        if blk.size == 0:
+            break
+        serve.blocks_host(blk)
+        for cid in serve.dropped():
+            admitted.pop(cid, None)
+            if cid in streams:
+                bank.remove(streams.pop(cid))
+        if streams:
+            ids = list(streams)
+            ptrs, counts = serve.outputs_device(ids)
+            if overlap:  # (nothing has waited for the latest rows yet, and the bank reads them on another stream than the object's)
+                import torch
+
+                torch.cuda.synchronize()
+            bank.feed([streams[c] for c in ids], ptrs, counts)
+            for cid, n in zip(ids, counts.tolist()):
+                samples[cid] += n
+                if bank.rows_pending(streams[cid]):
+                    rows[cid].append(bank.take_rows(streams[cid])[1])
+        nblocks += 1
+    serve.flush()
+    written, dropped = serve.sink_stats()
+    for cid, sid in streams.items():
+        rows[cid].append(bank.take_rows(sid)[1])
+        px = np.concatenate(rows[cid])[:samples[cid] // admitted[cid][1]]
+        if px.shape[0] > 0:
+            replay_iq.write_gray_png(os.path.join(out_dir, f"{cid}.png"), px)
+    if bank is not None:
+        bank.close()
+    serve.close()
+    return admitted, rejected, {"blocks": nblocks, "bytes_written": written, "blocks_dropped": dropped}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("iq_file")
+    ap.add_argument("--format", default="cu8", choices=list(DTYPES))
+    ap.add_argument("--band-rate", type=int, default=2016000)
+    ap.add_argument("--band-freq", type=int, required=True)
+    ap.add_argument("--client", action="append", default=[], help="CENTER_HZ:RATE_HZ (repeatable)")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--buffer-size", type=int, default=262144)
+    ap.add_argument("--lpf-cutoff-rate", type=int, default=5)
+    ap.add_argument("--variant", default="optimized", choices=["native", "optimized", "q15"],
+                    help="q15: the cs16 output family; every client's samples are written as <id>.cs16[.gz] (int16 pairs)")
+    ap.add_argument("--q15-kernel", type=int, default=0, choices=[0, 1])
+    ap.add_argument("--q15-nco", type=int, default=0, choices=[0, 1])
+    ap.add_argument("--gzip", action="store_true", help="gzip the files (either family)")
+    ap.add_argument("--waterfall-width", type=int, default=None, help="also write <id>.png: each client's waterfall, this many bins wide")
+    ap.add_argument("--any-rate", action="store_true",
+                    help="admit rates that do not divide the band rate: integer decimation in the engine, then a resampler bank")
+    ap.add_argument("--overlap", action="store_true", help="a block's rows reach the sinks during the next block's call")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
+    adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate, a.variant,
+                          a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel, q15_nco=a.q15_nco,
+                          overlap=a.overlap)
+    for cid, (c, r) in adm.items():
+        print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{'cs16' if a.variant == 'q15' else 'cf32'}{'.gz' if a.gzip else ''}")
+    for c, r, why in rej:
+        print(f"rejected: center {c} Hz rate {r} Hz (details {why})")
+    print(st)
+
+
+if __name__ == "__main__":
+    main()
