@@ -50,6 +50,17 @@ int xlating_delivery_create(unsigned slots, xlating_delivery **out);
 int xlating_delivery_pack_device(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows, const size_t *bytes,
                                  void *hip_stream);
 
+/* The same batch, NARROWED on its way into the image: row i is n_complex[i] cf32 samples (8 bytes each) at the 8-byte aligned device
+ * address dev_rows[i] and is delivered as n_complex[i] cs16 samples (4 bytes each: re, im as int16), at most 0xFFFFFFFC delivered
+ * bytes a row; n_complex[i] == 0 is allowed, with any pointer.  Each float y becomes clamp(rne(y * 32768), -32768, 32767), rne = to
+ * nearest, ties to even; a NaN becomes 0 (csrc/xl_dlv_narrow.h): the Q15 family's scale, so +1.0 -> 32767 and -1.0 -> -32768.  Still
+ * ONE launch (a kernel of its own that reads 8 bytes and writes 4 a sample) and ONE copy, of half the bytes; the sources are not
+ * written.  In the image a row begins at the lowest offset behind its predecessor that is congruent to (its device address mod 32) / 2
+ * mod 16: at most 12 bytes of padding a row.  xlating_delivery_row gives the narrowed row of 4 * n_complex[i] bytes; tickets, slots,
+ * errors and everything else are pack_device's, and plain and narrowing batches may alternate on one object. */
+int xlating_delivery_pack_device_cs16(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows,
+                                      const size_t *n_complex, void *hip_stream);
+
 /* 1: the ticket's rows are in host memory; 0: not yet.  -EINVAL (no such ticket), -EIO.  Tickets complete in the order given out. */
 int xlating_delivery_query(xlating_delivery *d, int ticket);
 /* Blocks until they are.  0, -EINVAL, -EIO. */
@@ -60,8 +71,8 @@ int xlating_delivery_row(xlating_delivery *d, int ticket, int key, const void **
 /* Gives the ticket's slot back, in any order.  0, -EINVAL, -EBUSY (not done yet: nothing waits here), -EIO. */
 int xlating_delivery_release(xlating_delivery *d, int ticket);
 
-/* What the latest pack_device issued: kernel launches (1), memory copies (2: the table of rows up, the image down) and the bytes of
- * the device-to-host copy (the rows plus their alignment padding); 0, 0, 0 for an empty batch. */
+/* What the latest pack_device or pack_device_cs16 issued: kernel launches (1), memory copies (2: the table of rows up, the image
+ * down) and the bytes of the device-to-host copy (the rows as delivered plus their alignment padding); 0, 0, 0 for an empty batch. */
 int xlating_delivery_last_ops(const xlating_delivery *d, unsigned *launches, unsigned *copies, uint64_t *d2h_bytes);
 /* Bytes of the image one workgroup of the pack kernel moves (for tests). */
 unsigned xlating_delivery_chunk_bytes(void);

@@ -15,13 +15,13 @@
  *
  * Per blocks call: the engine call in the configured mode; one resampler-bank feed for the fractional clients (pointers from
  * xlating_batch_outputs_device); ONE delivery batch holding the final row of every client (key: the client id; 8 bytes a sample in the
- * cf32 family, 4 in the cs16 family), which is one launch and one device-to-host copy of exactly those bytes.  xlating_batch_fetch and
- * the banks' _fetch are never called: a fractional client's engine row never crosses to the host, and after an XL_MODE_Q15 call only
+ * cf32 family, 4 in the cs16 family and in XL_SERVE_CF32_AS_CS16), which is one launch and one device-to-host copy of exactly those
+ * bytes.  xlating_batch_fetch and the banks' _fetch are never called: a fractional client's engine row never crosses to the host, and after an XL_MODE_Q15 call only
  * the int16 pairs do.  With overlap = 0 the call waits for that copy and queues the rows to the sinks before it returns; with
  * overlap = 1 it queues the PREVIOUS call's rows, whose copy ran beside this call's launches, and the latest call's rows are queued by
  * the next call, by xlating_serve_flush or by xlating_serve_remove of a client that has some.  Per client the bytes written are
  * exactly the stream of the engine (an integer-rate client) or of the bank fed from the engine (a fractional client): the object adds
- * no arithmetic.
+ * no arithmetic -- in XL_SERVE_CF32_AS_CS16 that stream narrowed by the delivery's one rule, sample by sample.
  *
  * Ordering: the feed and the pack launch run on a stream of the object's own, behind an event recorded behind the engine call
  * (xlating_batch_record_event); the next engine call is ordered behind an event recorded behind the pack launch (a device call waits
@@ -44,7 +44,12 @@ extern "C" {
 typedef struct xlating_serve_t xlating_serve;
 struct xlating_batch_t;
 
-enum { XL_SERVE_CF32 = 0, XL_SERVE_CS16 = 1 };
+/* XL_SERVE_CF32_AS_CS16: the cf32 family in everything (the engine's mode, `native`, every input format, cf32 included, the float
+ * resampler bank) except the delivery, which narrows each row to cs16 on its way to the host (xlating_delivery_pack_device_cs16: round
+ * to nearest even of y * 32768, saturated; the Q15 family's scale without its truncating arithmetic or its slower call).  Files are
+ * <id>.cs16[.gz], 4 bytes a sample cross to the host and pass through the sinks; xlating_serve_outputs_device still gives the cf32 rows
+ * on the device (a spectrum bank fed from them is a "cf32" bank). */
+enum { XL_SERVE_CF32 = 0, XL_SERVE_CS16 = 1, XL_SERVE_CF32_AS_CS16 = 2 };
 
 typedef struct {
   uint32_t band_sampling_rate;
@@ -52,15 +57,16 @@ typedef struct {
   uint32_t buffer_size;    /* bytes of a cu8 block: the engine's max_input_buffer_length */
   unsigned group_blocks;   /* most blocks per call, 1 .. 64 (0: 1) */
   int device;              /* HIP device ordinal, or -1 for the calling thread's current device */
-  int family;              /* XL_SERVE_CF32 | XL_SERVE_CS16 (XL_MODE_Q15 + the Q15 resampler bank) */
-  int native;              /* cf32 family: XL_MODE_NATIVE instead of XL_MODE_OPTIMIZED */
+  int family;              /* XL_SERVE_CF32 | XL_SERVE_CS16 (XL_MODE_Q15 + the Q15 resampler bank) | XL_SERVE_CF32_AS_CS16 */
+  int native;              /* cf32 family and XL_SERVE_CF32_AS_CS16: XL_MODE_NATIVE instead of XL_MODE_OPTIMIZED */
   int any_rate;            /* admit through xlating_wire_admit_any_rate */
   uint32_t lpf_cutoff_rate; /* (0: 5, the reference's default) */
   const char *base_path;   /* FILE destinations: <base_path>/<id>.<cf32|cs16>[.gz]; copied */
   int use_gzip;
   unsigned writer_threads; /* (0: 2) */
   size_t queue_bytes;      /* per client, allocated when its sink is attached; a row that does not fit drops the client
-                            * (0: 8 calls of a client at a quarter of the band rate = 8 x group_blocks x (buffer_size / 8 + 64) x 8 bytes;
+                            * (0: 8 calls of a client at a quarter of the band rate = 8 x group_blocks x (buffer_size / 8 + 64) x 8 bytes,
+                            * x 4 bytes for XL_SERVE_CF32_AS_CS16;
                             * set it from the rates you serve: 1024 clients cost 1024 x queue_bytes of host memory) */
   unsigned delivery_slots; /* 2 .. 16 (0: 2) */
   int overlap;             /* 0: a block's rows reach the sinks before its call returns; 1: during the next call / flush */

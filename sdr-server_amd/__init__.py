@@ -1198,13 +1198,13 @@ class ResamplerBankQ15(ResamplerBank):
 
 
 # ------------------------------------------------------------------------------------------------- delivery and serve (libxlating_serve.so)
-DELIVERY_SYMBOLS = ["xlating_delivery_create", "xlating_delivery_pack_device", "xlating_delivery_query", "xlating_delivery_wait",
-                    "xlating_delivery_row", "xlating_delivery_release", "xlating_delivery_last_ops", "xlating_delivery_chunk_bytes",
-                    "xlating_delivery_destroy"]
+DELIVERY_SYMBOLS = ["xlating_delivery_create", "xlating_delivery_pack_device", "xlating_delivery_pack_device_cs16", "xlating_delivery_query",
+                    "xlating_delivery_wait", "xlating_delivery_row", "xlating_delivery_release", "xlating_delivery_last_ops",
+                    "xlating_delivery_chunk_bytes", "xlating_delivery_destroy"]
 SERVE_SYMBOLS = ["xlating_serve_create", "xlating_serve_request", "xlating_serve_remove", "xlating_serve_blocks_host",
                  "xlating_serve_blocks_device", "xlating_serve_flush", "xlating_serve_outputs_device", "xlating_serve_dropped",
                  "xlating_serve_engine", "xlating_serve_last_ops", "xlating_serve_sink_stats", "xlating_serve_destroy"]
-SERVE_FAMILY = {"cf32": 0, "cs16": 1}
+SERVE_FAMILY = {"cf32": 0, "cs16": 1, "cf32-cs16": 2}  # (2: the cf32 family, narrowed to cs16 by the delivery)
 _vlib = None
 
 
@@ -1234,6 +1234,8 @@ def serve_lib():
     V.xlating_delivery_create.restype = C.c_int
     V.xlating_delivery_pack_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     V.xlating_delivery_pack_device.restype = C.c_int
+    V.xlating_delivery_pack_device_cs16.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_delivery_pack_device_cs16.restype = C.c_int
     for name in ("xlating_delivery_query", "xlating_delivery_wait", "xlating_delivery_release"):
         getattr(V, name).argtypes = [C.c_void_p, C.c_int]
         getattr(V, name).restype = C.c_int
@@ -1297,6 +1299,18 @@ class Delivery:
         t = serve_lib().xlating_delivery_pack_device(self.h, k.size, k.ctypes.data, p.ctypes.data, b.ctypes.data, stream)
         if t < 0:
             raise XlatingError("xlating_delivery_pack_device", t)
+        return t
+
+    def pack_cs16(self, keys, ptrs, n_complex, stream=0):
+        """row i: n_complex[i] cf32 samples at the 8-byte aligned device address ptrs[i], delivered as cs16 (round to nearest even of
+        y * 32768, saturated; NaN -> 0) -> a ticket"""
+        k = np.ascontiguousarray(keys, dtype=np.intc)
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        c = np.ascontiguousarray(n_complex, dtype=np.uint64)
+        assert k.size == p.size == c.size
+        t = serve_lib().xlating_delivery_pack_device_cs16(self.h, k.size, k.ctypes.data, p.ctypes.data, c.ctypes.data, stream)
+        if t < 0:
+            raise XlatingError("xlating_delivery_pack_device_cs16", t)
         return t
 
     def query(self, ticket):

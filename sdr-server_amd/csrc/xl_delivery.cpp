@@ -1,7 +1,8 @@
 // xl_delivery.cpp -- the delivery object (include/xlating_delivery.h): device rows -> one dense image per batch -> pinned host memory.
 // A batch takes a free slot (its device staging, its pinned buffer, its event), lays its rows out (xl_delivery_plan.h), writes the table
 // of runs into the banks' ring of pinned tables (xl_bank_host.h) and enqueues: on the caller's stream the table's upload and the pack
-// launch (xl_delivery.hip), on the object's copy stream, behind the event `last`, the image's device-to-host copy and the slot's event.
+// launch (xl_delivery.hip, or for a narrowing batch xl_delivery_narrow.hip), on the object's copy stream, behind the event `last`, the
+// image's device-to-host copy and the slot's event.
 // Ordering: `last` is recorded behind every launch and waited for on the next batch's stream before its upload, so the single device
 // table is not replaced under a launch that reads it (the banks' rule); the copy stream is one queue, so tickets complete in order.
 #include "../../include/xlating_delivery.h"
@@ -46,7 +47,7 @@ struct xlating_delivery_t {
   int next_ticket = 0;
   unsigned launches = 0, copies = 0;
   uint64_t d2h_bytes = 0;
-  std::vector<uint64_t> src;  // (scratch of a call)
+  std::vector<uint64_t> src, count;  // (scratch of a call)
   std::vector<XlDlvRun> runs;
 };
 
@@ -129,23 +130,28 @@ static int xl_dlv_reserve(XlDlvSlot *s, size_t need) {
   return 0;
 }
 
-static int xl_dlv_pack(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows, const size_t *bytes, hipStream_t st) {
+// count: a row's bytes, or with `narrow` its cf32 samples, which cross as cs16
+static int xl_dlv_pack(xlating_delivery *d, bool narrow, size_t n, const int *keys, const void *const *dev_rows, const size_t *count,
+                       hipStream_t st) {
   XlDlvSlot *s = nullptr;
   for (XlDlvSlot &c : d->slots)
     if (c.ticket < 0 && s == nullptr) s = &c;
   if (s == nullptr) return -EAGAIN;
   // the layout, and the keys in order
-  s->by_key.resize(n), s->off.resize(n), s->bytes.resize(n), d->src.resize(n), d->runs.resize(n);
+  s->by_key.resize(n), s->off.resize(n), s->bytes.resize(n), d->src.resize(n), d->count.resize(n), d->runs.resize(n);
   for (size_t i = 0; i < n; ++i) {
     s->by_key[i] = std::make_pair(keys[i], i);
-    s->bytes[i] = bytes[i], d->src[i] = bytes[i] > 0 ? (uint64_t)reinterpret_cast<uintptr_t>(dev_rows[i]) : 0u;
+    d->count[i] = count[i], d->src[i] = count[i] > 0 ? (uint64_t)reinterpret_cast<uintptr_t>(dev_rows[i]) : 0u;
   }
   std::sort(s->by_key.begin(), s->by_key.end());
   for (size_t i = 1; i < n; ++i)
     if (s->by_key[i].first == s->by_key[i - 1].first) return -EINVAL;
   size_t nruns = 0;
   uint64_t total = 0;
-  if (xl_dlv_plan(n, d->src.data(), s->bytes.data(), s->off.data(), d->runs.data(), &nruns, &total) != 0) return -EINVAL;
+  const int planned = narrow ? xl_dlv_plan_narrow(n, d->src.data(), d->count.data(), s->off.data(), d->runs.data(), &nruns, &total)
+                             : xl_dlv_plan(n, d->src.data(), d->count.data(), s->off.data(), d->runs.data(), &nruns, &total);
+  if (planned != 0) return -EINVAL;
+  for (size_t i = 0; i < n; ++i) s->bytes[i] = narrow ? 4u * d->count[i] : d->count[i];  // (of the delivered row)
   XlRingTable *t = nullptr;
   const size_t tbytes = nruns * sizeof(XlDlvRun);
   if (nruns > 0) {
@@ -175,7 +181,8 @@ static int xl_dlv_pack(xlating_delivery *d, size_t n, const int *keys, const voi
     if (d->packed) XL_TRY_RET(hipStreamWaitEvent(st, d->last, 0));
     XL_TRY_RET(xl_ring_upload(&d->ring, t, tbytes, st));
     d->copies += 1;
-    XL_TRY_RET(xl_dlv_launch(static_cast<const XlDlvRun *>(d->ring.d_tab), (uint32_t)nruns, xl_dlv_chunks(total), s->d_stage, st));
+    XL_TRY_RET((narrow ? xl_dlv_narrow_launch : xl_dlv_launch)(static_cast<const XlDlvRun *>(d->ring.d_tab), (uint32_t)nruns,
+                                                               xl_dlv_chunks(total), s->d_stage, st));
     d->launches += 1;
     XL_TRY_RET(hipEventRecord(d->last, st));
     d->packed = true;
@@ -190,18 +197,28 @@ static int xl_dlv_pack(xlating_delivery *d, size_t n, const int *keys, const voi
   return ticket;
 }
 
-extern "C" int xlating_delivery_pack_device(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows,
-                                            const size_t *bytes, void *hip_stream) {
-  if (d == nullptr || n > XL_DLV_MAX_ROWS || (n > 0 && (keys == nullptr || dev_rows == nullptr || bytes == nullptr))) return -EINVAL;
+static int xl_dlv_pack_checked(xlating_delivery *d, bool narrow, size_t n, const int *keys, const void *const *dev_rows,
+                               const size_t *count, void *hip_stream) {
+  if (d == nullptr || n > XL_DLV_MAX_ROWS || (n > 0 && (keys == nullptr || dev_rows == nullptr || count == nullptr))) return -EINVAL;
   if (d->broken) return -EIO;
   int rc;
   try {
-    rc = xl_dlv_pack(d, n, keys, dev_rows, bytes, static_cast<hipStream_t>(hip_stream));
+    rc = xl_dlv_pack(d, narrow, n, keys, dev_rows, count, static_cast<hipStream_t>(hip_stream));
   } catch (const std::bad_alloc &) {  // (the call's vectors are sized before anything is enqueued)
     rc = -ENOMEM;
   }
   if (rc == -EIO) d->broken = true;
   return rc;
+}
+
+extern "C" int xlating_delivery_pack_device(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows,
+                                            const size_t *bytes, void *hip_stream) {
+  return xl_dlv_pack_checked(d, false, n, keys, dev_rows, bytes, hip_stream);
+}
+
+extern "C" int xlating_delivery_pack_device_cs16(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows,
+                                                 const size_t *n_complex, void *hip_stream) {
+  return xl_dlv_pack_checked(d, true, n, keys, dev_rows, n_complex, hip_stream);
 }
 
 extern "C" int xlating_delivery_query(xlating_delivery *d, int ticket) {

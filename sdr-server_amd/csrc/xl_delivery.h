@@ -11,5 +11,7 @@
 // runs, stage: device.  chunks: xl_dlv_chunks of the image's size; the launch writes image bytes of rows only, all below that size.
 // 0 or a hipError_t.
 int xl_dlv_launch(const XlDlvRun *runs, uint32_t nruns, uint32_t chunks, void *stage, hipStream_t st);
+// The same for the runs of xl_dlv_plan_narrow (xl_delivery_narrow.hip): cf32 sources, read only, their cs16 pairs into the image.
+int xl_dlv_narrow_launch(const XlDlvRun *runs, uint32_t nruns, uint32_t chunks, void *stage, hipStream_t st);
 
 #endif

@@ -34,6 +34,7 @@ struct xlating_serve_t {
   std::string base_path;
   int device = 0, mode = XL_MODE_OPTIMIZED;
   size_t esz = 8;  // bytes per delivered sample
+  bool narrow = false;  // XL_SERVE_CF32_AS_CS16: the cf32 family's rows, narrowed by the pack launch
   xlating_batch *eng = nullptr;
   xlating_sinks *sinks = nullptr;
   xlating_delivery *dlv = nullptr;
@@ -149,7 +150,8 @@ extern "C" int xlating_serve_create(const xlating_serve_config *cfg, xlating_ser
   if (out == nullptr) return -EINVAL;
   *out = nullptr;
   if (cfg == nullptr || cfg->band_sampling_rate == 0 || cfg->base_path == nullptr ||
-      (cfg->family != XL_SERVE_CF32 && cfg->family != XL_SERVE_CS16) || (cfg->family == XL_SERVE_CS16 && cfg->input_format == XL_FMT_CF32))
+      (cfg->family != XL_SERVE_CF32 && cfg->family != XL_SERVE_CS16 && cfg->family != XL_SERVE_CF32_AS_CS16) ||
+      (cfg->family == XL_SERVE_CS16 && cfg->input_format == XL_FMT_CF32))
     return -EINVAL;
   xlating_serve *s = new (std::nothrow) xlating_serve_t();
   if (s == nullptr) return -ENOMEM;
@@ -163,9 +165,12 @@ extern "C" int xlating_serve_create(const xlating_serve_config *cfg, xlating_ser
     if (s->cfg.writer_threads == 0) s->cfg.writer_threads = 2;
     if (s->cfg.delivery_slots == 0) s->cfg.delivery_slots = 2;
     // (8 calls of a client at a quarter of the band rate, 8 bytes a sample; allocated per client when its sink is attached)
-    if (s->cfg.queue_bytes == 0) s->cfg.queue_bytes = (size_t)8 * s->cfg.group_blocks * ((size_t)s->cfg.buffer_size / 2 / 4 + 64) * 8;
+    // (the narrowing family's at its 4 bytes a sample)
+    s->narrow = cfg->family == XL_SERVE_CF32_AS_CS16;
+    if (s->cfg.queue_bytes == 0)
+      s->cfg.queue_bytes = (size_t)8 * s->cfg.group_blocks * ((size_t)s->cfg.buffer_size / 2 / 4 + 64) * (s->narrow ? 4 : 8);
     s->mode = cfg->family == XL_SERVE_CS16 ? XL_MODE_Q15 : (cfg->native ? XL_MODE_NATIVE : XL_MODE_OPTIMIZED);
-    s->esz = cfg->family == XL_SERVE_CS16 ? 4 : 8;
+    s->esz = cfg->family == XL_SERVE_CF32 ? 8 : 4;
     s->device = xl_hip_select_device(cfg->device);
     if (s->device < 0) {
       XL_LOG_ERR("xlating_serve_create: no usable HIP device (%s); there is no CPU path", xlating_hip_device_info());
@@ -233,7 +238,7 @@ extern "C" int xlating_serve_request(xlating_serve *s, const uint8_t *msg, size_
   free(rtaps);
   bool sink = false;
   if (ok) {
-    const char *ext = s->cfg.family == XL_SERVE_CS16 ? "cs16" : "cf32";
+    const char *ext = s->cfg.family == XL_SERVE_CF32 ? "cf32" : "cs16";
     rc = req.destination == XL_WIRE_DESTINATION_FILE ? xlating_sinks_attach_file_as(s->sinks, id, s->base_path.c_str(), ext, s->cfg.use_gzip)
                                                       : xlating_sinks_attach_fd(s->sinks, id, socket_fd, 0);
     ok = sink = rc == 0;
@@ -301,7 +306,8 @@ static int xl_serve_run(xlating_serve *s) {
     if ((rc = xl_serve_final_rows(s, n, s->ids.data(), s->rows.data(), s->lens.data(), true)) != 0) return rc;
   }
   for (size_t i = 0; i < n; ++i) s->bytes[i] = s->lens[i] * s->esz;
-  const int t = xlating_delivery_pack_device(s->dlv, n, s->ids.data(), s->rows.data(), s->bytes.data(), s->st);
+  const int t = s->narrow ? xlating_delivery_pack_device_cs16(s->dlv, n, s->ids.data(), s->rows.data(), s->lens.data(), s->st)
+                          : xlating_delivery_pack_device(s->dlv, n, s->ids.data(), s->rows.data(), s->bytes.data(), s->st);
   if (t < 0) return t;
   unsigned l = 0, c = 0;
   (void)xlating_delivery_last_ops(s->dlv, &l, &c, &s->d2h_bytes);

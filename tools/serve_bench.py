@@ -3,8 +3,10 @@
 48 kHz in a band of 2016000 Hz, the server's own 505-tap filter, cu8, 8 blocks of 262144 bytes per call; both output families.  Every
 client's sink is a pipe, and one reader thread drains them all.
 
-  (a) the pack kernel: HIP events around the pack launch of one call's rows and around a hipMemcpyAsync device-to-device copy of the
-      same bytes, alternating in one process (--pack; run it under `rocprofv3 --kernel-trace --stats` for the kernel's own time)
+  (a) the pack kernels: HIP events around the pack launch of one call's rows, around the NARROWING pack launch of the same rows
+      (xlating_delivery_pack_device_cs16: the same bytes read, half of them written) and around a hipMemcpyAsync device-to-device
+      copy of the same bytes, alternating in one process, in rounds (--pack; run it under `rocprofv3 --kernel-trace --stats` for the
+      kernels' own times)
   (b) the call period: a host clock around bursts of BURST calls, each burst ending in a flush and a synchronise INSIDE the clock, for
       three loops alternating in one process, three rounds: the parent's (process_host_group + fetch + sinks.submit), Serve with
       overlap 0, Serve with overlap 1.  Every loop is timed for the same work: BURST calls, BURST deliveries (with overlap 1 the flush
@@ -13,6 +15,8 @@ client's sink is a pipe, and one reader thread drains them all.
       until at least a second has been timed
   (c) cs16: the bytes Serve moves to the host per call (counted) against what xlating_batch_fetch copies after a Q15 call (the whole
       arena in float2-sized rows), and the two call periods
+  (d) cf32-cs16 (--families cf32,cs16,cf32-cs16): the cf32 family's engine call, its rows narrowed to cs16 by the delivery; its parent
+      loop is the cf32 family's (the parent has no such delivery)
 
 Prints a report; profiles/serve_vs_parent.txt is one run of it on an MI355X."""
 import argparse
@@ -130,7 +134,7 @@ def period(step, sync, flush, x, seconds):
 def run_periods(args, family, drain, out):
     import torch
 
-    variant = "q15" if family == "cs16" else "optimized"
+    variant = "q15" if family == "cs16" else "optimized"  # ("cf32-cs16" runs the cf32 family's engine call)
     x = np.random.default_rng(1).integers(0, 256, BUFFER * args.group, dtype=np.uint8)
     eng, sinks = make_parent(args.clients, variant, args.group, drain)
     serves = {ov: make_serve(args.clients, family, ov, args.group, drain, args.out) for ov in (0, 1)}
@@ -138,7 +142,7 @@ def run_periods(args, family, drain, out):
     def parent_step(x):
         eng.process_host_group(x, args.group, variant)
         eng.fetch()
-        if family == "cf32":
+        if family != "cs16":
             sinks.submit(eng)  # (after a Q15 call submit queues nothing: the parent has no cs16 delivery; its loop is engine + fetch)
 
     loops = {"parent": (parent_step, torch.cuda.synchronize, sinks.flush)}
@@ -172,35 +176,56 @@ def run_periods(args, family, drain, out):
 
 
 def run_pack(args, out):
-    """the pack launch of one call's rows against a device-to-device copy of the same bytes"""
+    """the pack launch of one call's rows, the narrowing pack launch of the same rows and a device-to-device copy of the same bytes,
+    in turn, args.rounds rounds of args.pack_iters each"""
     import torch
 
     esz, rows = 8, args.group * (BUFFER // 2 // 42)
     n = args.clients
-    src = torch.randint(0, 256, (n * (rows * esz + 64),), dtype=torch.uint8, device="cuda")
+    src = (0.3 * torch.randn((n * (rows * esz + 64) // 4,), dtype=torch.float32, device="cuda")).view(torch.uint8)
     dst = torch.empty_like(src)
     ptrs = [src.data_ptr() + i * (rows * esz + 64) for i in range(n)]
     d = xl.Delivery(2)
     st = torch.cuda.Stream()
-    times = {"pack": [], "d2d": []}
     total = n * rows * esz
-    for it in range(args.pack_iters + 3):
-        a, b, c = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+    keys = list(range(n))
+
+    def timed(what):
+        a, b = (torch.cuda.Event(enable_timing=True) for _ in range(2))
         with torch.cuda.stream(st):
             a.record()
-            t = d.pack(list(range(n)), ptrs, [rows * esz] * n, st.cuda_stream)
+            if what == "d2d":
+                dst[:total].copy_(src[:total], non_blocking=True)
+            elif what == "pack":
+                t = d.pack(keys, ptrs, [rows * esz] * n, st.cuda_stream)
+            else:
+                t = d.pack_cs16(keys, ptrs, [rows] * n, st.cuda_stream)
             b.record()
-            dst[:total].copy_(src[:total], non_blocking=True)
-            c.record()
-        d.wait(t)
-        d.release(t)
+        if what != "d2d":
+            d.wait(t)
+            d.release(t)
         st.synchronize()
-        if it >= 3:
-            times["pack"].append(a.elapsed_time(b)), times["d2d"].append(b.elapsed_time(c))
-    p, q = np.median(times["pack"]), np.median(times["d2d"])
-    out.append(f"[pack] {n} rows of {rows * esz} bytes = {total / 1e6:.1f} MB; HIP events on the launch stream, median of {args.pack_iters}")
-    out.append(f"  table upload + pack launch: {p:.3f} ms = {2 * total / p / 1e6:.0f} GB/s read + written")
-    out.append(f"  device-to-device copy of the same bytes: {q:.3f} ms = {2 * total / q / 1e6:.0f} GB/s; pack / copy = {p / q:.2f}")
+        return a.elapsed_time(b)
+
+    names = ("pack", "narrow", "d2d")
+    for what in names:  # (the slots' buffers, the table, the clocks)
+        for _ in range(3):
+            timed(what)
+    med = {k: [] for k in names}
+    for rnd in range(args.rounds):
+        for what in names:
+            med[what].append(float(np.median([timed(what) for _ in range(args.pack_iters)])))
+    moved = {"pack": 2 * total, "narrow": total + total // 2, "d2d": 2 * total}
+    label = {"pack": "table upload + pack launch", "narrow": "table upload + narrowing pack launch", "d2d": "device-to-device copy of the same bytes"}
+    out.append(f"[pack] {n} rows of {rows * esz} bytes = {total / 1e6:.1f} MB of cf32; HIP events on the launch stream, "
+               f"{args.rounds} alternating rounds, median of {args.pack_iters} each")
+    for k in names:
+        m = float(np.median(med[k]))
+        out.append(f"  {label[k]:40s} ms, rounds: " + "  ".join(f"{v:7.3f}" for v in med[k]) +
+                   f"   median {m:.3f} ms = {moved[k] / m / 1e6:.0f} GB/s read + written ({moved[k] / 1e6:.1f} MB)")
+    p, q, c = (float(np.median(med[k])) for k in names)
+    spread = max((max(v) - min(v)) / min(v) for v in med.values())
+    out.append(f"  pack / copy = {p / c:.2f}; narrowing / plain pack = {q / p:.2f}; largest spread of one launch over its rounds: {100 * spread:.1f} %")
     d.close()
 
 
@@ -211,8 +236,8 @@ def main(argv=None):
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--pack-iters", type=int, default=20)
-    ap.add_argument("--families", default="cf32,cs16")
-    ap.add_argument("--pack", action="store_true", help="only (a): the pack launch against a device-to-device copy")
+    ap.add_argument("--families", default="cf32,cs16", help="of cf32, cs16, cf32-cs16")
+    ap.add_argument("--pack", action="store_true", help="only (a): the two pack launches against a device-to-device copy")
     ap.add_argument("--out", default="/tmp/serve_bench_out")
     ap.add_argument("--report", default=None)
     a = ap.parse_args(argv)

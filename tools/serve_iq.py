@@ -3,10 +3,12 @@
 files, but the loop -- admission, engine, second stage, delivery, sinks -- is the C object's, one call per block:
 
   python tools/serve_iq.py capture.cu8 --format cu8 --band-rate 2016000 --band-freq 460100000 --out /tmp/out \\
-         --client 460112000:48000 --client 460050000:44100 --any-rate [--gzip] [--overlap] [--variant optimized | native | q15]
+         --client 460112000:48000 --client 460050000:44100 --any-rate [--gzip] [--overlap] [--variant optimized | native | q15] [--cs16-out]
 
 Every --client CENTER_HZ:RATE_HZ is sent to the object as the 15-byte wire message and ends up as <out>/<id>.cf32[.gz], or with
---variant q15 as <out>/<id>.cs16[.gz]: the sinks library writes both families, so --gzip works with q15 here.  With --waterfall-width W
+--variant q15 as <out>/<id>.cs16[.gz]: the sinks library writes both families, so --gzip works with q15 here.  --cs16-out with
+--variant native | optimized also writes <out>/<id>.cs16[.gz], but from the cf32 family's streams, narrowed on their way to the host
+(family "cf32-cs16": round to nearest of y * 32768, saturated); the waterfalls are then still fed with the cf32 rows on the device.  With --waterfall-width W
 every admitted client fast enough also gets <out>/<id>.png from a spectrum bank fed with the object's final rows
 (xlating_serve_outputs_device) after every block.  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
 launch and one copy of exactly the delivered bytes."""
@@ -26,13 +28,14 @@ DTYPES = replay_iq.DTYPES
 
 
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
-           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False):
+           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False, cs16_out=False):
     """replay_iq.replay's arguments and its triple: {client_id: (center_hz, rate_hz)} of the admitted requests, [(center, rate,
     failure_details)] of the refused ones, and the counters -- blocks, and the sinks' own bytes_written and blocks_dropped
     (xlating_serve_sink_stats: what replay_iq reads from its Sinks objects)."""
     q15 = variant == "q15"
     os.makedirs(out_dir, exist_ok=True)
-    serve = xl.Serve(band_rate, fmt, buffer_size, out_dir, family="cs16" if q15 else "cf32", native=variant == "native", any_rate=any_rate,
+    family = "cs16" if q15 else ("cf32-cs16" if cs16_out else "cf32")  # (with q15 the files are cs16 anyway)
+    serve = xl.Serve(band_rate, fmt, buffer_size, out_dir, family=family, native=variant == "native", any_rate=any_rate,
                      gzip=gzip, overlap=overlap, lpf_cutoff_rate=lpf_cutoff_rate, writer_threads=writer_threads,
                      queue_bytes=64 * (buffer_size // 2 // 8 + 64) * 8)
     eng = serve.engine()
@@ -111,6 +114,8 @@ def parse_args(argv=None):
     ap.add_argument("--any-rate", action="store_true",
                     help="admit rates that do not divide the band rate: integer decimation in the engine, then a resampler bank")
     ap.add_argument("--overlap", action="store_true", help="a block's rows reach the sinks during the next block's call")
+    ap.add_argument("--cs16-out", action="store_true",
+                    help="with --variant native | optimized: write <id>.cs16[.gz], the cf32 family's streams narrowed by the delivery")
     return ap.parse_args(argv)
 
 
@@ -119,9 +124,10 @@ def main(argv=None):
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate, a.variant,
                           a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel, q15_nco=a.q15_nco,
-                          overlap=a.overlap)
+                          overlap=a.overlap, cs16_out=a.cs16_out)
+    ext = "cs16" if a.variant == "q15" or a.cs16_out else "cf32"
     for cid, (c, r) in adm.items():
-        print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{'cs16' if a.variant == 'q15' else 'cf32'}{'.gz' if a.gzip else ''}")
+        print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{ext}{'.gz' if a.gzip else ''}")
     for c, r, why in rej:
         print(f"rejected: center {c} Hz rate {r} Hz (details {why})")
     print(st)
