@@ -42,7 +42,8 @@ static inline int xl_nx(int i) { return (i + 1) % XL_NTAB; }
 /* One synchronisation operation: wait for / record event `ev` (of index idx, for the per-table events) on stream `stream`. */
 enum { XL_AHEAD_WAIT, XL_AHEAD_RECORD };
 enum { XL_AHEAD_S_CALL, XL_AHEAD_S_SIDE, XL_AHEAD_S_PREV_SIDE }; /* the call's stream, its side stream, the previous chain launch's */
-enum { XL_AHEAD_EV_DEP, XL_AHEAD_EV_CHAIN, XL_AHEAD_EV_DONE };   /* the engine's dep_ev (re-recorded at will), ev_chain[idx], ev_done[idx] */
+enum { XL_AHEAD_EV_DEP, XL_AHEAD_EV_CHAIN, XL_AHEAD_EV_DONE,     /* the engine's dep_ev (re-recorded at will), ev_chain[idx], ev_done[idx] */
+       XL_AHEAD_EV_QCHAIN, XL_AHEAD_EV_QREADY };                 /* ev_qchain, ev_qready: xl_q15_ahead.h's alone, side stream nco_stream */
 typedef struct {
   uint8_t op, stream, ev, idx;
 } XlAheadOp;

@@ -163,26 +163,18 @@ struct xlating_batch_t {
   float2 *d_taps_rest = nullptr;  // tap image of the optimized-mode launch set (the clients outside the polyphase classes)
   double *d_qtaps = nullptr;   // Q15 taps as doubles, same indexing as d_taps (XL_MODE_Q15)
   uint32_t *d_qinc = nullptr;  // per nco entry: packed Q15 phase increment
-  // per slot: running Q15 phase (xlating.c:546-547: starts at 32767 + 0j): [qcur] = the committed ones.  Option "q15_nco" = 0
-  // steps them in place; = 1 every tabulation goes [qcur] -> [qcur ^ 1] and the call's commit flips qcur
+  // The Q15 family's phases and its phase look-ahead (xl_q15_ahead.h: the invariants are stated there): per slot the running Q15 phase
+  // in two buffers, two phase tables, the events "the look-ahead is complete" / "the call's table is written" (created when the option
+  // is first set to 1); `qahead` holds the indices into them and makes every decision.
   short2 *d_qphase[2] = {nullptr, nullptr};
-  int qcur = 0;
-  // Q15 phase tables (every XL_PH_STRIDE-th phase): [qtab] = the latest call's, the other one a spare ("q15_nco" = 1: the table
-  // of the call being tabulated, in-stream or a call ahead)
   short2 *d_qphtab[2] = {nullptr, nullptr};
-  int qtab = 0;
-  bool last_q15 = false;       // the latest call produced cs16 outputs
+  hipEvent_t ev_qchain = nullptr, ev_qready = nullptr;
+  XlQ15Ahead qahead = xl_q15_ahead_init();
   // option "q15_nco": 0 (default) = xl_nco_q15_batch_kernel in front of every Q15 call's launches, in place; 1 = every tabulation
   // by xl_nco_q15_ahead_kernel, and behind a Q15 call the NEXT call's table (same shape assumed: xl_grid_next) on nco_stream while
-  // the call's launches run.  The decisions are xl_q15_ahead.h's.
+  // the call's launches run.
   uint32_t q15_nco = 0;
-  bool qa_pending = false;  // a look-ahead is in flight or complete: d_qphase[qcur ^ 1] and d_qphtab[qtab ^ 1] hold (or will hold) the call at qa_pos
-  XlPos qa_pos = {};
-  // ev_qchain: the look-ahead is complete.  ev_qready (recorded on the call's stream between its table and its FIR launches): the
-  // previous call's readers of the spare table have been passed, and the phases this call commits are written -- what the
-  // look-ahead launch overwrites and reads.  Created when the option is first set to 1.
-  hipEvent_t ev_qchain = nullptr, ev_qready = nullptr;
-  uint64_t qa_used = 0, qa_dropped = 0;  // since the option was set: look-aheads that served their call / that were tabulated for nothing
+  bool last_q15 = false;       // the latest call produced cs16 outputs
   XlNcoClient *d_nco = nullptr;
   float2 *d_out[2] = {nullptr, nullptr};
   int ocur = 0;  // d_out[ocur] holds the latest call's outputs
@@ -244,13 +236,6 @@ static void xl_batch_sync_all(xlating_batch *b) {
   if (b->nco_stream) (void)hipStreamSynchronize(b->nco_stream);
   if (b->cs_masked) (void)hipStreamSynchronize(b->cs_masked);
   if (b->nco_masked) (void)hipStreamSynchronize(b->nco_masked);
-}
-
-// Option "q15_nco": forget the table tabulated a call ahead.  The caller has waited for it (xl_batch_sync_all, or the call's
-// stream waits for ev_qchain): the committed phases d_qphase[qcur] and the latest call's table are untouched by it.
-static void xl_q15_ahead_drop(xlating_batch *b) {
-  if (b->qa_pending) b->qa_dropped++;
-  b->qa_pending = false;
 }
 
 // A plan buffer of at least `bytes`: the smallest spare one that fits (and is not more than twice too big), else a fresh
@@ -444,8 +429,7 @@ extern "C" int xlating_batch_set_option(xlating_batch *b, const char *name, long
     if (value != 0 && value != 1) return -EINVAL;
     if (hipSetDevice(b->device) != hipSuccess) return -EIO;
     xl_batch_sync_all(b);  // (a look-ahead in flight writes the buffers the next tabulation writes, whatever the option then says)
-    b->qa_pending = false;
-    b->qa_used = b->qa_dropped = 0;  // (counted since the option was set)
+    xl_q15_ahead_option_set(&b->qahead);
     if (value == 1 && b->ev_qchain == nullptr) {
       if (hipEventCreateWithFlags(&b->ev_qchain, hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&b->ev_qready, hipEventDisableTiming) != hipSuccess) {
@@ -635,7 +619,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
   (void)hipSetDevice(b->device);
   xl_batch_sync_all(b);
   xl_ahead_drop(&b->ahead);
-  xl_q15_ahead_drop(b);
+  xl_q15_ahead_drop(&b->qahead);
   // Every failure from here on rolls the client back (a phantom client with an undefined phase would otherwise be
   // planned and filtered on every later call, with no id in the caller's hands to remove it).
   auto rollback = [&](int code) {
@@ -680,7 +664,7 @@ extern "C" int xlating_batch_add_client(xlating_batch *b, uint32_t decimation, c
     const float2 one = make_float2(1.0f, 0.0f);
     const short2 qone = make_short2(INT16_MAX, 0);  // xlating.c:546-547
     if (hipMemcpy(b->d_phase[b->ahead.pcur] + id, &one, sizeof(one), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
-    if (hipMemcpy(b->d_qphase[b->qcur] + id, &qone, sizeof(qone), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
+    if (hipMemcpy(b->d_qphase[b->qahead.cur] + id, &qone, sizeof(qone), hipMemcpyHostToDevice) != hipSuccess) return rollback(-EIO);
   }
   return id;
 }
@@ -735,7 +719,7 @@ fail:
 static int xl_batch_build_all_set(xlating_batch *b) {
   if (b->all_built) return 0;
   xl_batch_sync_all(b);  // (launches in flight may still read the previous image)
-  xl_q15_ahead_drop(b);  // (... and a Q15 look-ahead the increments released below)
+  xl_q15_ahead_drop(&b->qahead);  // (... and a Q15 look-ahead the increments released below)
   xl_release_launch_set(b, b->launches);
   xl_plan_release(b, b->d_taps);
   xl_plan_release(b, b->d_qtaps);
@@ -988,7 +972,7 @@ static int xl_batch_plan(xlating_batch *b) {
   xl_batch_sync_all(b);
   lap("sync");
   xl_ahead_drop(&b->ahead);
-  xl_q15_ahead_drop(b);
+  xl_q15_ahead_drop(&b->qahead);
   const uint32_t advanced = b->trel;  // samples since the previous plan: every plan-time stream record moves by this much
   xl_batch_free_plan(b, false);
   b->classes.clear();
@@ -1240,7 +1224,11 @@ XL_STAGE hipError_t xl_ahead_run(xlating_batch *b, const XlAheadOps &l, hipStrea
   for (int i = 0; i < l.n; ++i) {
     const XlAheadOp o = l.op[i];
     hipStream_t st = o.stream == XL_AHEAD_S_CALL ? s : (o.stream == XL_AHEAD_S_SIDE ? ns : b->last_nco);
-    hipEvent_t ev = o.ev == XL_AHEAD_EV_DEP ? b->dep_ev : (o.ev == XL_AHEAD_EV_CHAIN ? b->ev_chain[o.idx] : b->ev_done[o.idx]);
+    hipEvent_t ev = o.ev == XL_AHEAD_EV_DEP      ? b->dep_ev
+                    : o.ev == XL_AHEAD_EV_CHAIN  ? b->ev_chain[o.idx]
+                    : o.ev == XL_AHEAD_EV_DONE   ? b->ev_done[o.idx]
+                    : o.ev == XL_AHEAD_EV_QCHAIN ? b->ev_qchain
+                                                 : b->ev_qready;
     const hipError_t e = o.op == XL_AHEAD_WAIT ? hipStreamWaitEvent(st, ev, 0) : hipEventRecord(ev, st);
     if (e != hipSuccess) return e;
   }
@@ -1389,40 +1377,33 @@ fail:
 // history.  The float phases stay where they are; a float phase table tabulated ahead was for a call at this stream
 // position and is dropped.
 //
-// The Q15 phase table.  Option "q15_nco" = 0: xl_nco_q15_batch_kernel on the call's stream, in place on d_qphase[qcur], into
-// d_qphtab[qtab].  = 1: xl_nco_q15_ahead_kernel, d_qphase[qcur] -> d_qphase[qcur ^ 1] into the spare table d_qphtab[qtab ^ 1] --
-// by the previous call on nco_stream if its guess (same shape, right behind it: xl_q15_ahead_serves) holds, else here on the call's
-// stream; the commit flips qcur and qtab.  Behind the commit the next call's table is started on nco_stream (xl_q15_ahead_may_launch),
-// which first waits for ev_qready: recorded between this call's table and its FIR launches, it stands for the readers of the table
-// about to be overwritten (the previous call's) and for the phases the look-ahead starts from (this call's).
+// The Q15 phase table: which buffers the call's tabulation reads and writes, whether an earlier call has made it already, which table
+// the launches read, what is tabulated ahead behind the commit and every wait and record around the two are xl_q15_ahead.h's.
+// The kernel that steps [phase_in] -> [phase_out] into table [tab] for a call at `pos`: this call's on its own stream after a wrong
+// guess, the next call's on nco_stream.
+XL_STAGE hipError_t xl_q15_tabulate(xlating_batch *b, int phase_in, int phase_out, int tab, XlPos pos, hipStream_t s) {
+  return xl_launch_nco_q15_ahead(b->d_nco, b->d_qinc, (uint32_t)b->nco.size(), b->d_qphase[phase_in], b->d_qphase[phase_out], b->d_qphtab[tab],
+                                 pos, b->nco_prio, s);
+}
+
 XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
   hipStream_t s = c.s;
   const bool matrix = b->q15_kernel == 1u;  // the eligible clients on the matrix cores, the float64 launches over the others
   const bool ahead = b->q15_nco == 1u;
   const uint32_t ncl = (uint32_t)b->nco.size();
-  const short2 *qphtab = b->d_qphtab[b->qtab];
+  XlQ15AheadBegin qa;    // the Q15 look-ahead's decisions for this call: its tabulation, its table ...
+  const short2 *qphtab;  // ... which the launches below read
   XL_TRY(xl_ahead_run(b, xl_ahead_pending_wait(&b->ahead), s));
   xl_ahead_drop(&b->ahead);
   b->poisoned = true;
-  if (!ahead) {
-    if (b->qa_pending) XL_TRY(hipStreamWaitEvent(s, b->ev_qchain, 0));  // (it reads the phases stepped in place below)
-    xl_q15_ahead_drop(b);
-    XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, ncl, b->d_qphase[b->qcur], b->d_qphtab[b->qtab], c.pos, s));
-  } else {
-    qphtab = b->d_qphtab[b->qtab ^ 1];
-    const bool hit = xl_q15_ahead_serves(b->qa_pending, b->qa_pos, c.pos) != 0;
-    // (a look-ahead of another shape writes the very buffers the tabulation below writes)
-    if (b->qa_pending) XL_TRY(hipStreamWaitEvent(s, b->ev_qchain, 0));
-    if (hit) {
-      b->qa_used++;
-      b->qa_pending = false;
-    } else {
-      xl_q15_ahead_drop(b);
-      XL_TRY(xl_launch_nco_q15_ahead(b->d_nco, b->d_qinc, ncl, b->d_qphase[b->qcur], b->d_qphase[b->qcur ^ 1], b->d_qphtab[b->qtab ^ 1],
-                                     c.pos, b->nco_prio, s));
-    }
-    XL_TRY(hipEventRecord(b->ev_qready, s));
-  }
+  qa = xl_q15_ahead_begin(&b->qahead, ahead, c.pos);
+  qphtab = b->d_qphtab[qa.tab];
+  XL_TRY(xl_ahead_run(b, qa.pre, s));
+  if (qa.in_place)
+    XL_TRY(xl_launch_nco_q15_batch(b->d_nco, b->d_qinc, ncl, b->d_qphase[qa.phase_in], b->d_qphtab[qa.tab], c.pos, s));
+  else if (!qa.hit)
+    XL_TRY(xl_q15_tabulate(b, qa.phase_in, qa.phase_out, qa.tab, c.pos, s));
+  XL_TRY(xl_ahead_run(b, qa.post, s));
   if (matrix && !b->qmm.tiles.empty() && c.maxK > 0) {
     XlQmmArgs m;
     memset(&m, 0, sizeof(m));
@@ -1451,17 +1432,16 @@ XL_STAGE int xl_call_q15(xlating_batch *b, XlCall &c) {
   if (c.record_ev) XL_TRY(hipEventRecord(c.record_ev, s));
   xl_call_commit(b, c);
   b->last_q15 = true;
-  if (ahead) {
-    b->qcur ^= 1, b->qtab ^= 1;
-    if (xl_q15_ahead_may_launch(c.pos, b->planned_immature, ncl)) {
-      const XlPos next = xl_grid_next(c.pos);
+  xl_q15_ahead_commit(&b->qahead, &qa);
+  {
+    const XlQ15AheadNext nx = xl_q15_ahead_next(&b->qahead, ahead, c.pos, b->planned_immature, ncl);
+    if (nx.launch) {
       b->poisoned = true;  // (a failed look-ahead launch leaves the spare buffers and the side stream in an unknown state)
-      XL_TRY(hipStreamWaitEvent(b->nco_stream, b->ev_qready, 0));
-      XL_TRY(xl_launch_nco_q15_ahead(b->d_nco, b->d_qinc, ncl, b->d_qphase[b->qcur], b->d_qphase[b->qcur ^ 1], b->d_qphtab[b->qtab ^ 1],
-                                     next, b->nco_prio, b->nco_stream));
-      XL_TRY(hipEventRecord(b->ev_qchain, b->nco_stream));
+      XL_TRY(xl_ahead_run(b, nx.pre, s, b->nco_stream));
+      XL_TRY(xl_q15_tabulate(b, nx.phase_in, nx.phase_out, nx.tab, nx.pos, b->nco_stream));
+      XL_TRY(xl_ahead_run(b, nx.post, s, b->nco_stream));
       b->poisoned = false;
-      b->qa_pending = true, b->qa_pos = next;
+      xl_q15_ahead_launched(&b->qahead, &nx);
     }
   }
   return 0;
@@ -1795,7 +1775,7 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
     }
   }
   if (b->q15_nco == 1u)
-    d += " | q15 nco: ahead, " + std::to_string(b->qa_used) + " used, " + std::to_string(b->qa_dropped) + " dropped";
+    d += " | q15 nco: ahead, " + std::to_string(b->qahead.used) + " used, " + std::to_string(b->qahead.dropped) + " dropped";
   if (b->reserve_r) d += " | side kernel: " + std::to_string(8u * b->reserve_r) + " CUs reserved";
   if (pending) d += " | re-plan pending (client set or options changed: the next process call plans again)";
   const size_t len = std::min(d.size(), n - 1);
@@ -1863,7 +1843,7 @@ extern "C" int xlating_batch_sync(xlating_batch *b) {
   if (hipSetDevice(b->device) != hipSuccess) return -EIO;
   if (hipStreamSynchronize(b->last_stream) != hipSuccess) return -EIO;
   // (a Q15 phase table being tabulated a call ahead, option "q15_nco": enqueued work of the engine like the call's own)
-  if (b->qa_pending && hipStreamSynchronize(b->nco_stream) != hipSuccess) return -EIO;
+  if (xl_q15_ahead_pending(&b->qahead) && hipStreamSynchronize(b->nco_stream) != hipSuccess) return -EIO;
   return 0;
 }
 
@@ -1995,9 +1975,9 @@ extern "C" int xlating_batch_client_phase_q15(xlating_batch *b, int id, int16_t 
     return -EINVAL;
   if (hipSetDevice(b->device) != hipSuccess) return -EIO;
   xl_batch_sync_all(b);
-  // (option "q15_nco": a pending look-ahead has already written the phases AFTER the next call into d_qphase[qcur ^ 1])
+  // (option "q15_nco": a pending look-ahead has already written the phases AFTER the next call beside the committed ones: xl_q15_ahead.h)
   short2 ph;
-  if (hipMemcpy(&ph, b->d_qphase[b->qcur] + id, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+  if (hipMemcpy(&ph, b->d_qphase[b->qahead.cur] + id, sizeof(ph), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
   *re = ph.x;
   *im = ph.y;
   return 0;

@@ -1,14 +1,9 @@
 // tests/c/ahead_sweep.cpp -- stand-alone host program (its own main; tests/test_ahead_cpu.py builds it with ASan + UBSan and runs it):
 // the float families' phase look-ahead (csrc/xl_ahead.h) driven through sequences of calls in the order of the engine's stages
 // (xl_batch.cpp: xl_call_begin's stream hand-over, xl_call_q15's drop, xl_call_table, xl_call_chain, the launches with xl_call_chain_wait
-// in front of the first reader, xl_call_finish; add_client, xl_batch_plan, xl_batch_reserve_cus), against a model of the device that is
-// this program's own:
-//   - a stream is a vector clock; a launch ticks its stream and carries the clock; X happens before Y iff Y's clock has reached X's tick
-//     of X's stream
-//   - an event holds the clock of its latest record; a wait joins it into the waiting stream (HIP: the latest record enqueued before the
-//     wait -- the host enqueues in program order, so that is the event's current value); a never-recorded event is no wait
-//   - every phase table and phase buffer remembers its writer, the latest tick per stream of its readers, and WHAT it holds: a table the
-//     phases it started from and the position and shape it was tabulated for, a buffer a hash chained over every float call's shape
+// in front of the first reader, xl_call_finish; add_client, xl_batch_plan, xl_batch_reserve_cus), against the device model of
+// ahead_model.h, which the Q15 look-ahead's sweep shares: streams as vector clocks, events, and phase tables and buffers that remember
+// their writer, their readers and what they hold (a buffer: a hash chained over every float call's shape).
 // Checked for every call: (a) its launches read a table written before them, for this call's position and shape, from the phases the
 // previous call committed; (b) every write of a table or buffer comes after its earlier writer and readers; (c) the committed buffer holds
 // the chain of all float calls so far; (d), (e) the steady-state and ev_done counts of steady() below.
@@ -21,63 +16,25 @@
 
 #include "xl_ahead.h"
 
-enum { ST_A, ST_B, ST_OWN, ST_CS_MASKED, ST_NCO, ST_NCO_MASKED, NST };  // two caller streams, the engine's streams
-enum { ENGINE = -1 };                                                    // XL_STREAM_ENGINE_P
+#include "ahead_model.h"
 
-static unsigned long g_checks = 0;
-static char g_ctx[512];
-#define CHECK(cond)                                                                 \
-  do {                                                                              \
-    ++g_checks;                                                                     \
-    if (!(cond)) {                                                                  \
-      fprintf(stderr, "FAIL %s:%d: %s | %s\n", __FILE__, __LINE__, #cond, g_ctx); \
-      exit(1);                                                                      \
-    }                                                                               \
-  } while (0)
+enum { ENGINE = -1 };  // XL_STREAM_ENGINE_P
 
-struct Clock {
-  uint32_t t[NST];
-};
-struct Event {
-  bool recorded;
-  Clock c;
-};
-struct Op {
-  int s;
-  Clock c;
-};
-struct Res {  // a phase table or a phase buffer
-  int wstream;  // -1: initialised by the host
-  uint32_t wtick;
-  uint32_t rtick[NST];
-  uint64_t hash;  // buffer: the phases it holds; table: the phases it was tabulated from
-  uint32_t trel, S, G, flags;
-};
-struct Shape {
-  uint32_t S, G, flags;
-};
 static const Shape kShapes[2] = {{4096u, 1u, 0u}, {4096u, 4u, 1u}};
-
-static uint64_t mix(uint64_t h, uint64_t v) {
-  h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
-  return h * 0xD6E8FEB86659FD93ull;
-}
-static uint64_t step_hash(uint64_t h, Shape sh) { return mix(mix(mix(h, sh.S), sh.G), sh.flags + 11u); }
 
 struct Counts {
   unsigned chain_waits, done_records, launches, launched_calls, hits, misses, chain_pre_ops, chain_pre_done_waits;
   int last_n;
 };
 
-struct Model {
+struct Model : Streams {
   XlAhead a;
   // the engine's side of it
   int last_stream, last_nco;  // stream indices; last_nco -1: none
   bool masked, dirty, nofuse;
   uint64_t ncalls;
   uint32_t trel;
-  // the device
-  Clock st[NST];
+  // the device (its streams: Streams::st)
   Event dep, chain[XL_NTAB], done[XL_NTAB];
   Res tab[XL_NTAB], ph[XL_NTAB];
   // what is true
@@ -94,35 +51,6 @@ static void model_init(Model &m, int chain_calls, bool masked, bool nofuse) {
   m.committed = m.ph[m.a.pcur].hash = 1u;
 }
 
-static Op launch(Model &m, int s) {
-  m.st[s].t[s]++;
-  const Op o = {s, m.st[s]};
-  return o;
-}
-static void record(Model &m, Event &e, int s) { e.recorded = true, e.c = m.st[s]; }
-static void wait(Model &m, int s, const Event &e) {
-  if (!e.recorded) return;
-  for (int i = 0; i < NST; ++i)
-    if (e.c.t[i] > m.st[s].t[i]) m.st[s].t[i] = e.c.t[i];
-}
-static void sync_all(Model &m) {  // xl_batch_sync_all: the host waits for every stream
-  Clock j = m.st[0];
-  for (int s = 1; s < NST; ++s)
-    for (int i = 0; i < NST; ++i)
-      if (m.st[s].t[i] > j.t[i]) j.t[i] = m.st[s].t[i];
-  for (int s = 0; s < NST; ++s) m.st[s] = j;
-}
-static bool written_before(const Res &r, const Op &o) { return r.wstream < 0 || r.wtick <= o.c.t[r.wstream]; }
-static void res_read(Res &r, const Op &o) {
-  CHECK(written_before(r, o));  // (a): the reader comes after the tabulation that wrote what it reads
-  if (o.c.t[o.s] > r.rtick[o.s]) r.rtick[o.s] = o.c.t[o.s];
-}
-static void res_write(Res &r, const Op &o) {
-  CHECK(written_before(r, o));
-  for (int s = 0; s < NST; ++s) CHECK(r.rtick[s] <= o.c.t[s]);  // (b): every earlier reader has happened
-  r.wstream = o.s, r.wtick = o.c.t[o.s];
-  memset(r.rtick, 0, sizeof(r.rtick));
-}
 // one tabulation inside launch `o`: d_phase[pin] -> table [t], d_phase[pout], for a call of `sh` at `trel`
 static void tabulate(Model &m, const Op &o, int pin, int t, int pout, uint32_t trel, Shape sh) {
   CHECK(pin >= 0 && pin < XL_NTAB && t >= 0 && t < XL_NTAB && pout >= 0 && pout < XL_NTAB && pin != pout);

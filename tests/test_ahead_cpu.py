@@ -1,6 +1,6 @@
 """CPU test (-m "not gpu") of the float families' phase look-ahead (csrc/xl_ahead.h, every decision of xl_batch.cpp's look-ahead stages): a
 stand-alone host program with its own main (tests/c/ahead_sweep.cpp), built with ASan and UBSan and run as a process of its own, drives the
-header through call sequences in the order of the engine's stages against its own model of streams, events and happens-before: every
+header through call sequences in the order of the engine's stages against a model of streams, events and happens-before (tests/c/ahead_model.h): every
 sequence of five symbols out of 18 (side / fused / Q15 calls, two shapes, two caller streams and the engine's, a join, a re-plan, a re-plan
 that re-creates the masked stream pair) for each chain_calls, 6000 fixed-seed random sequences of 64, and the steady patterns' counts.  The
 header must also compile as plain C without any HIP header."""

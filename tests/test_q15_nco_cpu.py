@@ -1,9 +1,10 @@
 """CPU tests (-m "not gpu") of the Q15 phase look-ahead (engine option "q15_nco"; csrc/xl_kernels.hip: xl_nco_q15_ahead_kernel): the
 kernel's code object, the yardstick kernel's instruction text against the parent commit's, the premises of the packed step (every
-increment component in -32767 .. 32767; no saturating line of the recurrence ever acts on a reachable state), and the engine's decisions
-(csrc/xl_q15_ahead.h) in a stand-alone program under ASan and UBSan."""
+increment component in -32767 .. 32767; no saturating line of the recurrence ever acts on a reachable state), and the look-ahead's state and
+decisions (csrc/xl_q15_ahead.h) in a stand-alone program under ASan and UBSan."""
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +17,8 @@ from pyoracle import Oracle
 CSRC = os.path.join(ROOT, "sdr-server_amd", "csrc")
 KERNELS = os.path.join("sdr-server_amd", "csrc", "xl_kernels.hip")
 ONLY_ASM = ["--cuda-device-only", "-S"]
+CXX = shutil.which("g++") or "/opt/rocm/lib/llvm/bin/clang++"
+CC = shutil.which("gcc") or "/opt/rocm/lib/llvm/bin/clang"
 
 
 def _makefile_hipflags():
@@ -158,10 +161,24 @@ def test_no_clamp_of_the_step_is_reachable():
 
 
 def test_ahead_sweep_under_the_sanitizers(tmp_path):
+    """tests/c/q15_ahead_sweep.cpp, a program of its own: the two predicates position by position, then the header's state and decisions
+    through every sequence of five symbols out of 13 (from option 0 and 1, from trel = 0 and just short of 2^31), 6000 random sequences
+    of 64 and the steady patterns, on the device model it shares with the float look-ahead's sweep (tests/c/ahead_model.h)."""
     exe = str(tmp_path / "q15_ahead_sweep")
-    r = subprocess.run(["gcc", "-std=c11", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
-                        os.path.join(ROOT, "tests", "c", "q15_ahead_sweep.c"), "-o", exe], capture_output=True, text=True)
+    r = subprocess.run([CXX, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-I", CSRC, os.path.join(ROOT, "tests", "c", "q15_ahead_sweep.cpp"), "-o", exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-500:], r.stderr[-2000:])
-    assert int(r.stdout.split()[1]) >= 500000, r.stdout  # (the sweeps ran)
+    positions, sequences = (int(v) for v in r.stdout.split()[1:3])
+    assert positions >= 500000, r.stdout  # (the per-position sweeps ran)
+    assert sequences > 4 * 13 ** 5, r.stdout  # at least one check per sequence of the exhaustive part: 4 settings x 13^5
+
+
+def test_header_is_plain_c_without_hip():
+    src = open(os.path.join(CSRC, "xl_q15_ahead.h")).read()
+    includes = [ln.split()[1] for ln in src.splitlines() if ln.startswith("#include")]
+    assert includes == ["<stdbool.h>", "<stdint.h>", '"xl_grid.h"', '"xl_ahead.h"'], includes
+    r = subprocess.run([CC, "-std=c11", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-x", "c", os.path.join(CSRC, "xl_q15_ahead.h")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
