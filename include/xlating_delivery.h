@@ -61,6 +61,26 @@ int xlating_delivery_pack_device(xlating_delivery *d, size_t n, const int *keys,
 int xlating_delivery_pack_device_cs16(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows,
                                       const size_t *n_complex, void *hip_stream);
 
+/* pack_device_cs16 with a GAIN per row and the row's LEVEL recorded.  gain_log2[i] (a host array of n, read before the call returns)
+ * is a power of two, -48 .. 48: each float y of row i becomes clamp(rne(y * 2^(15 + gain_log2[i])), -32768, 32767), a NaN 0
+ * (csrc/xl_dlv_gain.h: the product is exact, there is one rounding; integer arithmetic on the float's fields).  With every gain 0 the
+ * image is byte for byte pack_device_cs16's.  A gain outside -48 .. 48, of an empty row too, is -EINVAL and nothing is done.
+ * Per row the launch also reports three uint32 (xlating_delivery_row_level): peak_bits, the bit pattern of the largest magnitude among
+ * the row's floats BEFORE the gain, NaNs aside (0 for an empty or all-NaN row, 0x7F800000 for an Inf; as a float it is that magnitude);
+ * clipped, the floats where the clamp acted (a rounded magnitude above 32767 for a positive value, above 32768 for a negative; an Inf
+ * counts, a NaN does not); nans, the NaN floats.  Integer maxima and sums: bit-identical for a row whatever rows share its batch and in
+ * whatever order.  The table of levels lies behind the image at the next 16-byte boundary, 12 bytes a non-empty row, and crosses in the
+ * SAME copy: still ONE launch and ONE device-to-host copy.  The table is zeroed on `hip_stream` before the launch by a memset node,
+ * which xlating_delivery_last_ops counts among the copies: 1 launch, 3 memory operations (the table of rows up, the zeroing, image
+ * and levels down), and d2h_bytes = the image rounded up to 16 + 12 x the non-empty rows.  Tickets, slots, errors and everything else
+ * are pack_device's; the three pack calls may alternate on one object. */
+int xlating_delivery_pack_device_cs16_gain(xlating_delivery *d, size_t n, const int *keys, const void *const *dev_rows,
+                                           const size_t *n_complex, const int8_t *gain_log2, void *hip_stream);
+/* After the ticket is done: the level of the row tagged `key` of a pack_device_cs16_gain batch (0, 0, 0 for an empty row).
+ * 0, -EINVAL (no such ticket or key, a null pointer), -EBUSY (not done yet), -EIO; -ENODATA: the ticket is one of pack_device or
+ * pack_device_cs16, which record no levels. */
+int xlating_delivery_row_level(xlating_delivery *d, int ticket, int key, uint32_t *peak_bits, uint32_t *clipped, uint32_t *nans);
+
 /* 1: the ticket's rows are in host memory; 0: not yet.  -EINVAL (no such ticket), -EIO.  Tickets complete in the order given out. */
 int xlating_delivery_query(xlating_delivery *d, int ticket);
 /* Blocks until they are.  0, -EINVAL, -EIO. */
@@ -72,7 +92,8 @@ int xlating_delivery_row(xlating_delivery *d, int ticket, int key, const void **
 int xlating_delivery_release(xlating_delivery *d, int ticket);
 
 /* What the latest pack_device or pack_device_cs16 issued: kernel launches (1), memory copies (2: the table of rows up, the image
- * down) and the bytes of the device-to-host copy (the rows as delivered plus their alignment padding); 0, 0, 0 for an empty batch. */
+ * down) and the bytes of the device-to-host copy (the rows as delivered plus their alignment padding); 0, 0, 0 for an empty batch.
+ * After pack_device_cs16_gain: 1 launch, 3 memory operations (the zeroing of the level table is one), the bytes stated there. */
 int xlating_delivery_last_ops(const xlating_delivery *d, unsigned *launches, unsigned *copies, uint64_t *d2h_bytes);
 /* Bytes of the image one workgroup of the pack kernel moves (for tests). */
 unsigned xlating_delivery_chunk_bytes(void);

@@ -106,6 +106,40 @@ struct xlating_batch_t *xlating_serve_engine(xlating_serve *s);
 /* What the latest blocks call issued behind the engine call: kernel launches (the bank's feed, the pack), memory copies, and the
  * bytes of the device-to-host copy. */
 int xlating_serve_last_ops(const xlating_serve *s, unsigned *launches_after_engine, unsigned *copies_after_engine, uint64_t *d2h_bytes);
+
+/* ---- XL_SERVE_CF32_AS_CS16 only (every other family: -EINVAL): a power-of-two gain per client and a level meter.
+ * A cf32 stream has no scale of its own, and a deep decimation leaves a weak signal few of the 16 bits: each client's row may be
+ * delivered as clamp(rne(y * 2^(15 + g))) with its own g in -48 .. 48 (xlating_delivery_pack_device_cs16_gain), and every delivered
+ * row's level comes back with it: peak_bits (the bit pattern of the largest magnitude before the gain), clipped (floats where the
+ * clamp acted) and nans.  The object packs through that call exactly when levels are enabled or some client's gain is not 0 or is
+ * automatic: still one pack launch and one device-to-host copy, one more memory operation in xlating_serve_last_ops (the zeroing of
+ * the level table) and 12 bytes a non-empty row more in d2h_bytes.  Otherwise a call is, launch for launch and byte for byte, what it
+ * is without these functions. */
+/* The client's gain from the next blocks call on; default 0.  Ends automatic gain for the client.  0, -EINVAL (another family, no such
+ * client, a gain outside -48 .. 48). */
+int xlating_serve_set_gain(xlating_serve *s, int client_id, int gain_log2);
+/* Automatic gain on or off (csrc/xl_serve_gain.h holds the policy; turning it off keeps the gain it had reached).  After each call
+ * whose rows are queued to the sinks, from the row's level and the gain g it was packed with, with top the exponent such that
+ * |peak| * 2^g lies in [2^(top - 1), 2^top): clipped > 0 or top > 0 lowers the gain by max(1, top); a nonzero peak with top <= -3 in
+ * each of the last 8 such calls raises it by 1 and the count restarts; silence changes nothing; the gain stays in -48 .. 48.  A
+ * constant level ends with |peak| * 2^g in [1/8, 1).  LAG: a new gain holds from the next call that has not been packed yet -- with
+ * overlap = 0 a step in level at call N is answered from call N + 1 on, with overlap = 1 (call N's rows are queued during call N + 1,
+ * behind its pack) from call N + 2 on; the calls between clip, and are counted.  0, -EINVAL. */
+int xlating_serve_set_auto_gain(xlating_serve *s, int client_id, int on);
+/* Levels without any gain: every call packs through the gain call (all gains 0 deliver the bytes of the plain rule).  0, -EINVAL. */
+int xlating_serve_enable_levels(xlating_serve *s, int on);
+/* The level of each client's row in the latest call whose rows have been QUEUED TO THE SINKS (with overlap = 1 the call before the
+ * latest, until a flush), the gain that row was packed with, and the client's clipped floats since it joined.  Any output array may be
+ * NULL.  Zeros until such a call was delivered through the gain call.  0, -EINVAL (another family; an id that is not a client:
+ * nothing is filled). */
+int xlating_serve_levels(xlating_serve *s, size_t n, const int *client_ids, uint32_t *peak_bits, uint32_t *clipped, uint32_t *nans,
+                         int8_t *gain_log2, uint64_t *clipped_total);
+/* The client's latest gain changes, at most 64 and at most cap, oldest first, whether made by xlating_serve_set_gain or by the
+ * policy: from sample first_sample[i] of the client's delivered stream (4 bytes each in its file) the gain is gain_log2[i]; before the
+ * first change it is 0.  A consumer undoes the gain exactly: y = int16 * 2^-(15 + g).  Returns the number of entries written, or
+ * -EINVAL. */
+int xlating_serve_gain_log(xlating_serve *s, int client_id, size_t cap, uint64_t *first_sample, int8_t *gain_log2);
+
 void xlating_serve_destroy(xlating_serve *s);
 
 #ifdef __cplusplus

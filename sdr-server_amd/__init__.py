@@ -1200,10 +1200,13 @@ class ResamplerBankQ15(ResamplerBank):
 # ------------------------------------------------------------------------------------------------- delivery and serve (libxlating_serve.so)
 DELIVERY_SYMBOLS = ["xlating_delivery_create", "xlating_delivery_pack_device", "xlating_delivery_pack_device_cs16", "xlating_delivery_query",
                     "xlating_delivery_wait", "xlating_delivery_row", "xlating_delivery_release", "xlating_delivery_last_ops",
-                    "xlating_delivery_chunk_bytes", "xlating_delivery_destroy"]
+                    "xlating_delivery_chunk_bytes", "xlating_delivery_destroy", "xlating_delivery_pack_device_cs16_gain",
+                    "xlating_delivery_row_level"]
 SERVE_SYMBOLS = ["xlating_serve_create", "xlating_serve_request", "xlating_serve_remove", "xlating_serve_blocks_host",
                  "xlating_serve_blocks_device", "xlating_serve_flush", "xlating_serve_outputs_device", "xlating_serve_dropped",
-                 "xlating_serve_engine", "xlating_serve_last_ops", "xlating_serve_sink_stats", "xlating_serve_destroy"]
+                 "xlating_serve_engine", "xlating_serve_last_ops", "xlating_serve_sink_stats", "xlating_serve_destroy",
+                 "xlating_serve_set_gain", "xlating_serve_set_auto_gain", "xlating_serve_enable_levels", "xlating_serve_levels",
+                 "xlating_serve_gain_log"]
 SERVE_FAMILY = {"cf32": 0, "cs16": 1, "cf32-cs16": 2}  # (2: the cf32 family, narrowed to cs16 by the delivery)
 _vlib = None
 
@@ -1236,6 +1239,10 @@ def serve_lib():
     V.xlating_delivery_pack_device.restype = C.c_int
     V.xlating_delivery_pack_device_cs16.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     V.xlating_delivery_pack_device_cs16.restype = C.c_int
+    V.xlating_delivery_pack_device_cs16_gain.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_delivery_pack_device_cs16_gain.restype = C.c_int
+    V.xlating_delivery_row_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    V.xlating_delivery_row_level.restype = C.c_int
     for name in ("xlating_delivery_query", "xlating_delivery_wait", "xlating_delivery_release"):
         getattr(V, name).argtypes = [C.c_void_p, C.c_int]
         getattr(V, name).restype = C.c_int
@@ -1269,6 +1276,15 @@ def serve_lib():
     V.xlating_serve_last_ops.restype = C.c_int
     V.xlating_serve_sink_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     V.xlating_serve_sink_stats.restype = C.c_int
+    for name in ("xlating_serve_set_gain", "xlating_serve_set_auto_gain"):
+        getattr(V, name).argtypes = [C.c_void_p, C.c_int, C.c_int]
+        getattr(V, name).restype = C.c_int
+    V.xlating_serve_enable_levels.argtypes = [C.c_void_p, C.c_int]
+    V.xlating_serve_enable_levels.restype = C.c_int
+    V.xlating_serve_levels.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6
+    V.xlating_serve_levels.restype = C.c_int
+    V.xlating_serve_gain_log.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+    V.xlating_serve_gain_log.restype = C.c_int
     V.xlating_serve_destroy.argtypes = [C.c_void_p]
     V.xlating_serve_destroy.restype = None
     _vlib = V
@@ -1312,6 +1328,28 @@ class Delivery:
         if t < 0:
             raise XlatingError("xlating_delivery_pack_device_cs16", t)
         return t
+
+    def pack_device_cs16_gain(self, keys, ptrs, n_complex, gain_log2, stream=0):
+        """pack_cs16 with a power-of-two gain per row, -48 .. 48 (y * 2^(15 + gain), rounded once, saturated; NaN -> 0), and every
+        row's level recorded (row_level) -> a ticket"""
+        k = np.ascontiguousarray(keys, dtype=np.intc)
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        c = np.ascontiguousarray(n_complex, dtype=np.uint64)
+        g = np.ascontiguousarray(np.clip(np.asarray(gain_log2, dtype=np.int64), -128, 127), dtype=np.int8)  # (the library refuses)
+        assert k.size == p.size == c.size == g.size
+        t = serve_lib().xlating_delivery_pack_device_cs16_gain(self.h, k.size, k.ctypes.data, p.ctypes.data, c.ctypes.data, g.ctypes.data, stream)
+        if t < 0:
+            raise XlatingError("xlating_delivery_pack_device_cs16_gain", t)
+        return t
+
+    def row_level(self, ticket, key):
+        """-> (peak_bits, clipped, nans) of the row tagged `key` of a pack_device_cs16_gain ticket that is done (XlatingError -ENODATA
+        for a ticket of pack or pack_cs16)"""
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        code = serve_lib().xlating_delivery_row_level(self.h, ticket, key, C.byref(a), C.byref(b), C.byref(c))
+        if code != 0:
+            raise XlatingError("xlating_delivery_row_level", code)
+        return a.value, b.value, c.value
 
     def query(self, ticket):
         code = serve_lib().xlating_delivery_query(self.h, ticket)
@@ -1411,6 +1449,41 @@ class Serve:
         if code != 0:
             raise XlatingError("xlating_serve_outputs_device", code)
         return p, n
+
+    def set_gain(self, client_id, gain_log2):
+        """family "cf32-cs16": the client's rows as y * 2^(15 + gain_log2) from the next blocks call on; ends automatic gain"""
+        code = serve_lib().xlating_serve_set_gain(self.h, client_id, int(gain_log2))
+        if code != 0:
+            raise XlatingError("xlating_serve_set_gain", code)
+
+    def set_auto_gain(self, client_id, on=True):
+        code = serve_lib().xlating_serve_set_auto_gain(self.h, client_id, 1 if on else 0)
+        if code != 0:
+            raise XlatingError("xlating_serve_set_auto_gain", code)
+
+    def enable_levels(self, on=True):
+        code = serve_lib().xlating_serve_enable_levels(self.h, 1 if on else 0)
+        if code != 0:
+            raise XlatingError("xlating_serve_enable_levels", code)
+
+    def levels(self, cids):
+        """-> dict of arrays [n]: peak_bits, clipped, nans (uint32), gain_log2 (int8) of the latest call queued to the sinks, and
+        clipped_total (uint64) since each client joined"""
+        a = np.ascontiguousarray(cids, dtype=np.intc)
+        out = {"peak_bits": np.zeros(a.size, np.uint32), "clipped": np.zeros(a.size, np.uint32), "nans": np.zeros(a.size, np.uint32),
+               "gain_log2": np.zeros(a.size, np.int8), "clipped_total": np.zeros(a.size, np.uint64)}
+        code = serve_lib().xlating_serve_levels(self.h, a.size, a.ctypes.data, *[v.ctypes.data for v in out.values()])
+        if code != 0:
+            raise XlatingError("xlating_serve_levels", code)
+        return out
+
+    def gain_log(self, client_id, cap=64):
+        """-> [(first_sample, gain_log2)]: the client's latest gain changes, oldest first"""
+        f, g = np.zeros(cap, np.uint64), np.zeros(cap, np.int8)
+        n = serve_lib().xlating_serve_gain_log(self.h, client_id, cap, f.ctypes.data, g.ctypes.data)
+        if n < 0:
+            raise XlatingError("xlating_serve_gain_log", n)
+        return [(int(f[i]), int(g[i])) for i in range(n)]
 
     def dropped(self, cap=4096):
         ids = (C.c_int * cap)()

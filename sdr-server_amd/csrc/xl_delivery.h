@@ -13,5 +13,8 @@
 int xl_dlv_launch(const XlDlvRun *runs, uint32_t nruns, uint32_t chunks, void *stage, hipStream_t st);
 // The same for the runs of xl_dlv_plan_narrow (xl_delivery_narrow.hip): cf32 sources, read only, their cs16 pairs into the image.
 int xl_dlv_narrow_launch(const XlDlvRun *runs, uint32_t nruns, uint32_t chunks, void *stage, hipStream_t st);
+// The same image from the runs of xl_dlv_plan_gain (xl_delivery_gain.hip), each run under its gain; levels: the level table on the
+// device, XL_DLV_LEVEL_WORDS uint32 a run, ZEROED on st before this launch: the launch adds every run's level to its entry.
+int xl_dlv_gain_launch(const XlDlvGainRun *runs, uint32_t nruns, uint32_t chunks, void *stage, uint32_t *levels, hipStream_t st);
 
 #endif

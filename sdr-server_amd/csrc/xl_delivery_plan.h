@@ -116,4 +116,56 @@ XL_DLV_FN int xl_dlv_span(const XlDlvRun *r, uint32_t c, uint64_t *a, uint64_t *
   return *a < *b;
 }
 
+/* ------------------------------------------------------------------- the narrowed layout with a gain and a level a row
+ * (xlating_delivery_pack_device_cs16_gain, xl_delivery_gain.hip).  The image is xl_dlv_plan_narrow's, byte for byte in the same places:
+ * the run record below carries an XlDlvRun, so xl_dlv_span and xl_dlv_narrow_src serve it as they are; beside it the run's gain (the
+ * gain belongs to the RUN: two short rows that share a 16-byte slot may differ) and the index of its entry of the LEVEL TABLE, which
+ * lies behind the image at the next 16-byte boundary: XL_DLV_LEVEL_WORDS uint32 a run (peak_bits, clipped, nans: xl_dlv_gain.h), in
+ * the order of the runs.  Image and table cross to the host in one copy of *full bytes. */
+#define XL_DLV_GAIN_LO (-48) /* xl_dlv_gain.h's XL_DLV_GAIN_MIN .. XL_DLV_GAIN_MAX (tests/c/delivery_gain_sweep.c holds them equal) */
+#define XL_DLV_GAIN_HI 48
+#define XL_DLV_LEVEL_WORDS 3u
+#define XL_DLV_LEVEL_PEAK 0u
+#define XL_DLV_LEVEL_CLIPPED 1u
+#define XL_DLV_LEVEL_NANS 2u
+#define XL_DLV_NO_LEVEL (~(uint32_t)0) /* an empty row's */
+
+typedef struct {
+  XlDlvRun r;    /* as xl_dlv_plan_narrow fills it */
+  int32_t gain;  /* XL_DLV_GAIN_LO .. XL_DLV_GAIN_HI */
+  uint32_t lvl;  /* its entry of the level table */
+} XlDlvGainRun;
+
+/* Lays out n narrowed rows with gain[i] each.  off, *total: as of xl_dlv_plan_narrow (scratch: room for n XlDlvRun).  lvl[i] (n
+ * entries): row i's entry of the level table, or XL_DLV_NO_LEVEL for an empty row.  runs (room for n), *nruns.  *lvl_off: where the
+ * table begins, *full: where it ends -- both 0 when there is no run.  0, or -1: xl_dlv_plan_narrow's refusals, or a gain outside
+ * XL_DLV_GAIN_LO .. XL_DLV_GAIN_HI (an empty row's included); nothing is to be used then. */
+static inline int xl_dlv_plan_gain(size_t n, const uint64_t *src, const uint64_t *n_complex, const int8_t *gain, uint64_t *off,
+                                   uint32_t *lvl, XlDlvRun *scratch, XlDlvGainRun *runs, size_t *nruns, uint64_t *total,
+                                   uint64_t *lvl_off, uint64_t *full) {
+  for (size_t i = 0; i < n; ++i)
+    if (gain[i] < XL_DLV_GAIN_LO || gain[i] > XL_DLV_GAIN_HI) return -1;
+  if (xl_dlv_plan_narrow(n, src, n_complex, off, scratch, nruns, total) != 0) return -1;
+  size_t k = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (n_complex[i] == 0) {
+      lvl[i] = XL_DLV_NO_LEVEL;
+      continue;
+    }
+    runs[k].r = scratch[k], runs[k].gain = gain[i], runs[k].lvl = (uint32_t)k;
+    lvl[i] = (uint32_t)k;
+    ++k;
+  }
+  *lvl_off = k > 0 ? (*total + 15u) & ~(uint64_t)15 : 0u;
+  *full = k > 0 ? *lvl_off + 4u * XL_DLV_LEVEL_WORDS * (uint64_t)k : 0u;
+  return 0;
+}
+
+/* xl_dlv_first for these records */
+XL_DLV_FN uint32_t xl_dlv_gain_first(const XlDlvGainRun *runs, uint32_t found, uint32_t c) {
+  const uint64_t lo = (uint64_t)c * XL_DLV_CHUNK;
+  while (found > 0u && runs[found - 1u].r.off + runs[found - 1u].r.bytes > lo) --found;
+  return found;
+}
+
 #endif /* XL_DELIVERY_PLAN_H_ */

@@ -19,12 +19,22 @@
 #include "../../include/xlating_sinks.h"
 #include "../../include/xlating_wire.h"
 #include "xl_common.h"
+#include "xl_serve_gain.h"
 
 namespace {
 
 struct XlServeClient {
   int rs = -1;           // its stream of the resampler bank, or -1: the rate divides the band rate
   uint32_t band_freq = 0;
+  // XL_SERVE_CF32_AS_CS16: the client's gain and meter (xl_serve_gain.h holds the policy and the log)
+  int8_t gain = 0;       // from the next call that is packed
+  bool agc = false;      // xlating_serve_set_auto_gain
+  XlServeGainState agc_state = {0};
+  XlServeGainLog log = {};
+  uint64_t packed = 0;   // samples of its delivered stream packed so far: where a new gain begins
+  uint64_t clipped_total = 0;
+  uint32_t peak_bits = 0, clipped = 0, nans = 0;  // of the latest call queued to its sink
+  int8_t level_gain = 0;                          // the gain that call was packed with
 };
 
 }  // namespace
@@ -47,6 +57,10 @@ struct xlating_serve_t {
   int pending = -1;                          // the ticket not handed to the sinks yet
   std::vector<int> pending_ids;              // its keys that are still owed their row (a client that is forgotten leaves the list)
   std::vector<int> handing;                  // (scratch of a hand-over)
+  bool levels_on = false;                    // xlating_serve_enable_levels
+  bool pending_gained = false, handing_gained = false;  // the ticket is one of pack_device_cs16_gain ...
+  std::map<int, int8_t> pending_gain, handing_gain;     // ... packed with these gains, by client id
+  std::vector<int8_t> gains;                 // (scratch of a call)
   std::vector<int> dropped;
   unsigned launches = 0, copies = 0;
   uint64_t d2h_bytes = 0;
@@ -129,6 +143,16 @@ static int xl_serve_deliver(xlating_serve *s, int t) {
     size_t n = 0;
     if ((rc = xlating_delivery_row(s->dlv, t, id, &p, &n)) != 0) break;
     if (n > 0) (void)xlating_sinks_write_bytes(s->sinks, id, p, n);  // (-EPIPE: reported by xlating_sinks_failed below)
+    if (!s->handing_gained) continue;
+    // the row's level, and what the client's policy makes of it: a new gain holds from the next call that is packed
+    XlServeClient &c = s->clients[id];
+    if ((rc = xlating_delivery_row_level(s->dlv, t, id, &c.peak_bits, &c.clipped, &c.nans)) != 0) break;
+    c.level_gain = s->handing_gain[id];
+    c.clipped_total += c.clipped;
+    if (!c.agc) continue;
+    const int32_t g = xl_serve_gain_step(&c.agc_state, c.peak_bits, c.clipped, c.level_gain, c.gain);
+    if (g != c.gain) xl_serve_gain_log_add(&c.log, c.packed, g);
+    c.gain = (int8_t)g;
   }
   s->handing.clear();
   const int rr = xlating_delivery_release(s->dlv, t);
@@ -143,6 +167,8 @@ static int xl_serve_hand_over(xlating_serve *s) {
   s->pending = -1;
   s->handing.swap(s->pending_ids);
   s->pending_ids.clear();
+  s->handing_gain.swap(s->pending_gain), s->handing_gained = s->pending_gained;
+  s->pending_gain.clear(), s->pending_gained = false;
   return xl_serve_deliver(s, t);
 }
 
@@ -306,9 +332,18 @@ static int xl_serve_run(xlating_serve *s) {
     if ((rc = xl_serve_final_rows(s, n, s->ids.data(), s->rows.data(), s->lens.data(), true)) != 0) return rc;
   }
   for (size_t i = 0; i < n; ++i) s->bytes[i] = s->lens[i] * s->esz;
-  const int t = s->narrow ? xlating_delivery_pack_device_cs16(s->dlv, n, s->ids.data(), s->rows.data(), s->lens.data(), s->st)
-                          : xlating_delivery_pack_device(s->dlv, n, s->ids.data(), s->rows.data(), s->bytes.data(), s->st);
+  // the pack with gains and levels exactly when somebody asked for either; otherwise the call is what it always was
+  bool gained = s->narrow && s->levels_on;
+  for (const auto &kv : s->clients) gained = gained || (s->narrow && (kv.second.gain != 0 || kv.second.agc));
+  s->gains.clear();
+  if (gained)
+    for (size_t i = 0; i < n; ++i) s->gains.push_back(s->clients[s->ids[i]].gain);
+  const int t = gained ? xlating_delivery_pack_device_cs16_gain(s->dlv, n, s->ids.data(), s->rows.data(), s->lens.data(), s->gains.data(), s->st)
+                : s->narrow ? xlating_delivery_pack_device_cs16(s->dlv, n, s->ids.data(), s->rows.data(), s->lens.data(), s->st)
+                            : xlating_delivery_pack_device(s->dlv, n, s->ids.data(), s->rows.data(), s->bytes.data(), s->st);
   if (t < 0) return t;
+  if (s->narrow)
+    for (size_t i = 0; i < n; ++i) s->clients[s->ids[i]].packed += s->lens[i];
   unsigned l = 0, c = 0;
   (void)xlating_delivery_last_ops(s->dlv, &l, &c, &s->d2h_bytes);
   s->launches += l, s->copies += c;
@@ -319,8 +354,11 @@ static int xl_serve_run(xlating_serve *s) {
   // is forgotten, and with it its id in this ticket's list
   const int prev = s->pending;
   s->handing.swap(s->pending_ids);
+  s->handing_gain.swap(s->pending_gain), s->handing_gained = s->pending_gained;
   s->pending = t;
   s->pending_ids = s->ids;
+  s->pending_gain.clear(), s->pending_gained = gained;
+  for (size_t i = 0; gained && i < n; ++i) s->pending_gain[s->ids[i]] = s->gains[i];
   if (prev >= 0) rc = xl_serve_deliver(s, prev);  // (overlap: the previous call's rows, whose copy ran beside this call's launches)
   if (!s->cfg.overlap) {
     const int rh = xl_serve_hand_over(s);
@@ -391,6 +429,57 @@ extern "C" int xlating_serve_sink_stats(xlating_serve *s, uint64_t *bytes_writte
   if (s == nullptr) return -EINVAL;
   xlating_sinks_stats(s->sinks, bytes_written, blocks_dropped);
   return 0;
+}
+
+// the client of a call that XL_SERVE_CF32_AS_CS16 alone answers, or nullptr
+static XlServeClient *xl_serve_gain_client(xlating_serve *s, int client_id) {
+  if (s == nullptr || !s->narrow) return nullptr;
+  const auto it = s->clients.find(client_id);
+  return it == s->clients.end() ? nullptr : &it->second;
+}
+
+extern "C" int xlating_serve_set_gain(xlating_serve *s, int client_id, int gain_log2) {
+  XlServeClient *c = xl_serve_gain_client(s, client_id);
+  if (c == nullptr || gain_log2 < XL_SERVE_GAIN_MIN || gain_log2 > XL_SERVE_GAIN_MAX) return -EINVAL;
+  if (gain_log2 != c->gain) xl_serve_gain_log_add(&c->log, c->packed, gain_log2);
+  c->gain = (int8_t)gain_log2, c->agc = false;
+  return 0;
+}
+
+extern "C" int xlating_serve_set_auto_gain(xlating_serve *s, int client_id, int on) {
+  XlServeClient *c = xl_serve_gain_client(s, client_id);
+  if (c == nullptr) return -EINVAL;
+  if ((on != 0) != c->agc) c->agc_state.quiet = 0;
+  c->agc = on != 0;
+  return 0;
+}
+
+extern "C" int xlating_serve_enable_levels(xlating_serve *s, int on) {
+  if (s == nullptr || !s->narrow) return -EINVAL;
+  s->levels_on = on != 0;
+  return 0;
+}
+
+extern "C" int xlating_serve_levels(xlating_serve *s, size_t n, const int *client_ids, uint32_t *peak_bits, uint32_t *clipped, uint32_t *nans,
+                                    int8_t *gain_log2, uint64_t *clipped_total) {
+  if (s == nullptr || !s->narrow || (n > 0 && client_ids == nullptr)) return -EINVAL;
+  for (size_t i = 0; i < n; ++i)
+    if (s->clients.count(client_ids[i]) == 0) return -EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    const XlServeClient &c = s->clients[client_ids[i]];
+    if (peak_bits) peak_bits[i] = c.peak_bits;
+    if (clipped) clipped[i] = c.clipped;
+    if (nans) nans[i] = c.nans;
+    if (gain_log2) gain_log2[i] = c.level_gain;
+    if (clipped_total) clipped_total[i] = c.clipped_total;
+  }
+  return 0;
+}
+
+extern "C" int xlating_serve_gain_log(xlating_serve *s, int client_id, size_t cap, uint64_t *first_sample, int8_t *gain_log2) {
+  XlServeClient *c = xl_serve_gain_client(s, client_id);
+  if (c == nullptr || (cap > 0 && (first_sample == nullptr || gain_log2 == nullptr))) return -EINVAL;
+  return (int)xl_serve_gain_log_read(&c->log, cap > XL_SERVE_GAIN_LOG ? XL_SERVE_GAIN_LOG : (uint32_t)cap, first_sample, gain_log2);
 }
 
 extern "C" struct xlating_batch_t *xlating_serve_engine(xlating_serve *s) { return s ? s->eng : nullptr; }

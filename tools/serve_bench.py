@@ -18,6 +18,11 @@ client's sink is a pipe, and one reader thread drains them all.
   (d) cf32-cs16 (--families cf32,cs16,cf32-cs16): the cf32 family's engine call, its rows narrowed to cs16 by the delivery; its parent
       loop is the cf32 family's (the parent has no such delivery)
 
+  (e) --gain: only the pack launch with a gain and a level a row (xlating_delivery_pack_device_cs16_gain, every gain 0: the same
+      bytes) against the narrowing pack launch it grew from (xlating_delivery_pack_device_cs16, xl_dlv_narrow_kernel) on the same
+      batch, the rows of the headline call; HIP events, the two alternating in one process, the spread of each over its rounds
+      reported (profiles/serve_gain_vs_parent.txt)
+
 Prints a report; profiles/serve_vs_parent.txt is one run of it on an MI355X."""
 import argparse
 import os
@@ -229,6 +234,53 @@ def run_pack(args, out):
     d.close()
 
 
+def run_gain(args, out):
+    """the narrowing pack launch and the pack launch with gains and levels on the same rows, in turn, args.rounds rounds of
+    args.pack_iters each; the events enclose the table's upload, the zeroing of the level table (gain only) and the launch"""
+    import torch
+
+    rows, n = args.group * (BUFFER // 2 // 42), args.clients
+    src = (0.3 * torch.randn((n * (rows * 8 + 64) // 4,), dtype=torch.float32, device="cuda")).view(torch.uint8)
+    ptrs = [src.data_ptr() + i * (rows * 8 + 64) for i in range(n)]
+    d = xl.Delivery(2)
+    st = torch.cuda.Stream()
+    keys, lens, gains = list(range(n)), [rows] * n, [0] * n
+
+    def timed(what):
+        a, b = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        with torch.cuda.stream(st):
+            a.record()
+            t = d.pack_cs16(keys, ptrs, lens, st.cuda_stream) if what == "narrow" else d.pack_device_cs16_gain(keys, ptrs, lens, gains, st.cuda_stream)
+            b.record()
+        d.wait(t)
+        if what == "gain":
+            assert d.row_level(t, 0)[0] > 0
+        d.release(t)
+        st.synchronize()
+        return a.elapsed_time(b)
+
+    names = ("narrow", "gain")
+    for what in names:
+        for _ in range(3):
+            timed(what)
+    med = {k: [] for k in names}
+    for rnd in range(args.rounds):
+        for what in names:
+            med[what].append(float(np.median([timed(what) for _ in range(args.pack_iters)])))
+    label = {"narrow": "table upload + narrowing pack launch (parent)", "gain": "table upload + zeroing + pack launch with gains, levels"}
+    out.append(f"[gain] {n} rows of {rows} cf32 samples = {n * rows * 8 / 1e6:.1f} MB read, {n * rows * 4 / 1e6:.1f} MB written; HIP events on the "
+               f"launch stream, {args.rounds} alternating rounds, median of {args.pack_iters} each")
+    for k in names:
+        m, lo, hi = float(np.median(med[k])), min(med[k]), max(med[k])
+        out.append(f"  {label[k]:56s} ms, rounds: " + "  ".join(f"{v:7.3f}" for v in med[k]) +
+                   f"   median {m:.3f} ms, spread over its rounds {100 * (hi - lo) / lo:.1f} %")
+    p, g = (float(np.median(med[k])) for k in names)
+    spread = (max(med["narrow"]) - min(med["narrow"])) / min(med["narrow"])
+    out.append(f"  with gains and levels / parent = {g / p:.3f}; the parent's own spread is {100 * spread:.1f} %: the difference "
+               f"{'exceeds' if abs(g / p - 1.0) > spread else 'lies within'} it")
+    d.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", type=int, default=1024)
@@ -238,6 +290,7 @@ def main(argv=None):
     ap.add_argument("--pack-iters", type=int, default=20)
     ap.add_argument("--families", default="cf32,cs16", help="of cf32, cs16, cf32-cs16")
     ap.add_argument("--pack", action="store_true", help="only (a): the two pack launches against a device-to-device copy")
+    ap.add_argument("--gain", action="store_true", help="only (e): the pack launch with gains and levels against the narrowing pack launch")
     ap.add_argument("--out", default="/tmp/serve_bench_out")
     ap.add_argument("--report", default=None)
     a = ap.parse_args(argv)
@@ -247,8 +300,11 @@ def main(argv=None):
     resource.setrlimit(resource.RLIMIT_NOFILE, (hard if hard != resource.RLIM_INFINITY else 1 << 16, hard))
     os.makedirs(a.out, exist_ok=True)
     out = [f"serve_bench: {xl.device_info()}"]
-    run_pack(a, out)
-    if not a.pack:
+    if a.gain:
+        run_gain(a, out)
+    else:
+        run_pack(a, out)
+    if not a.pack and not a.gain:
         drain = Drain()
         for family in a.families.split(","):
             run_periods(a, family, drain, out)

@@ -10,7 +10,10 @@ Every --client CENTER_HZ:RATE_HZ is sent to the object as the 15-byte wire messa
 --variant native | optimized also writes <out>/<id>.cs16[.gz], but from the cf32 family's streams, narrowed on their way to the host
 (family "cf32-cs16": round to nearest of y * 32768, saturated); the waterfalls are then still fed with the cf32 rows on the device.  With --waterfall-width W
 every admitted client fast enough also gets <out>/<id>.png from a spectrum bank fed with the object's final rows
-(xlating_serve_outputs_device) after every block.  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
+(xlating_serve_outputs_device) after every block.  With --cs16-out, --gain G delivers every client's stream as y * 2^(15 + G) (G a
+power of two's exponent, -48 .. 48) and --auto-gain lets the object choose each client's G from its level (include/xlating_serve.h);
+both also write <out>/<id>.gain: lines "first_sample gain_log2" from the client's gain log -- from that sample of the file on, the
+int16 values are y * 2^(15 + gain_log2); before the first line the gain is 0 -- and a last line "clipped_total N".  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
 launch and one copy of exactly the delivered bytes."""
 import argparse
 import os
@@ -28,7 +31,8 @@ DTYPES = replay_iq.DTYPES
 
 
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
-           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False, cs16_out=False):
+           gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False, cs16_out=False, gain=None,
+           auto_gain=False):
     """replay_iq.replay's arguments and its triple: {client_id: (center_hz, rate_hz)} of the admitted requests, [(center, rate,
     failure_details)] of the refused ones, and the counters -- blocks, and the sinks' own bytes_written and blocks_dropped
     (xlating_serve_sink_stats: what replay_iq reads from its Sinks objects)."""
@@ -43,6 +47,9 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
         eng.set_option("q15_kernel", q15_kernel)
         if q15_nco:
             eng.set_option("q15_nco", q15_nco)
+    metered = family == "cf32-cs16" and (gain is not None or auto_gain)
+    if (gain is not None or auto_gain) and not metered:
+        raise ValueError("--gain and --auto-gain need --cs16-out with --variant native | optimized")
     bank = xl.SpectrumBank(waterfall_width, "cs16" if q15 else "cf32", wide=waterfall_width > 8192) if waterfall_width else None
     streams, rows, samples = {}, {}, {}
     admitted, rejected = {}, []
@@ -52,6 +59,11 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             rejected.append((center, rate, xl.wire_parse_response(resp)[2]))
             continue
         admitted[cid] = (center, rate)
+        if metered:
+            if gain is not None:
+                serve.set_gain(cid, gain)
+            if auto_gain:
+                serve.set_auto_gain(cid, True)
         if bank is not None and rate >= waterfall_width:
             streams[cid], rows[cid], samples[cid] = bank.add(rate), [], 0
     elem = np.dtype(DTYPES[fmt]).itemsize
@@ -84,6 +96,14 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
         nblocks += 1
     serve.flush()
     written, dropped = serve.sink_stats()
+    if metered:  # (tool-level: the sinks write the samples only)
+        ids = sorted(admitted)
+        totals = serve.levels(ids)["clipped_total"].tolist() if ids else []
+        for cid, total in zip(ids, totals):
+            with open(os.path.join(out_dir, f"{cid}.gain"), "w") as f:
+                for first, g in serve.gain_log(cid):
+                    f.write(f"{first} {g}\n")
+                f.write(f"clipped_total {total}\n")
     for cid, sid in streams.items():
         rows[cid].append(bank.take_rows(sid)[1])
         px = np.concatenate(rows[cid])[:samples[cid] // admitted[cid][1]]
@@ -116,6 +136,10 @@ def parse_args(argv=None):
     ap.add_argument("--overlap", action="store_true", help="a block's rows reach the sinks during the next block's call")
     ap.add_argument("--cs16-out", action="store_true",
                     help="with --variant native | optimized: write <id>.cs16[.gz], the cf32 family's streams narrowed by the delivery")
+    ap.add_argument("--gain", type=int, default=None, metavar="G",
+                    help="with --cs16-out: deliver y * 2^(15 + G), G in -48 .. 48; also writes <id>.gain")
+    ap.add_argument("--auto-gain", action="store_true",
+                    help="with --cs16-out: the object picks each client's gain from its level; also writes <id>.gain")
     return ap.parse_args(argv)
 
 
@@ -124,7 +148,7 @@ def main(argv=None):
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate, a.variant,
                           a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel, q15_nco=a.q15_nco,
-                          overlap=a.overlap, cs16_out=a.cs16_out)
+                          overlap=a.overlap, cs16_out=a.cs16_out, gain=a.gain, auto_gain=a.auto_gain)
     ext = "cs16" if a.variant == "q15" or a.cs16_out else "cf32"
     for cid, (c, r) in adm.items():
         print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{ext}{'.gz' if a.gzip else ''}")
