@@ -14,8 +14,9 @@
  *     xlating_serve_flush(s); xlating_serve_destroy(s);
  *
  * Per blocks call: the engine call in the configured mode; one resampler-bank feed for the fractional clients (pointers from
- * xlating_batch_outputs_device); ONE delivery batch holding the final row of every client (key: the client id; 8 bytes a sample in the
- * cf32 family, 4 in the cs16 family and in XL_SERVE_CF32_AS_CS16), which is one launch and one device-to-host copy of exactly those
+ * xlating_batch_outputs_device); one tuner-bank feed for the clients of xlating_serve_set_tune, if there are any; ONE delivery batch
+ * holding the final row of every client (key: the client id; 8 bytes a sample in the cf32 family, 4 in the cs16 family and in
+ * XL_SERVE_CF32_AS_CS16), which is one launch and one device-to-host copy of exactly those
  * bytes.  xlating_batch_fetch and the banks' _fetch are never called: a fractional client's engine row never crosses to the host, and after an XL_MODE_Q15 call only
  * the int16 pairs do.  With overlap = 0 the call waits for that copy and queues the rows to the sinks before it returns; with
  * overlap = 1 it queues the PREVIOUS call's rows, whose copy ran beside this call's launches, and the latest call's rows are queued by
@@ -139,6 +140,27 @@ int xlating_serve_levels(xlating_serve *s, size_t n, const int *client_ids, uint
  * first change it is 0.  A consumer undoes the gain exactly: y = int16 * 2^-(15 + g).  Returns the number of entries written, or
  * -EINVAL. */
 int xlating_serve_gain_log(xlating_serve *s, int client_id, size_t cap, uint64_t *first_sample, int8_t *gain_log2);
+
+/* ---- XL_SERVE_CF32 and XL_SERVE_CF32_AS_CS16 (XL_SERVE_CS16: -EINVAL; a Q15 rotator does not exist): tune a running client.
+ * A client's centre frequency is fixed by its request; this moves its signal afterwards, phase-continuously, by a rotation of its
+ * FINAL row (xlating_tune.h): from the next blocks call on, sample by sample, y[j] * exp(2 pi i phi_j / 2^64) with phi stepping by
+ * shift_hz and ramping by ramp_hz_per_s (Hz per second: a Doppler correction follows a pass without a call per block).  The steps
+ * are xlating_tune_from_hz(shift_hz, ramp_hz_per_s, rate) with the client's final rate as the double
+ * (double)band_rate * L / ((double)D * M), L = M = 1 for an integer-rate client; a positive shift moves the spectrum up.
+ * THE ROTATION FOLLOWS THE CLIENT'S FILTERS: a shift moves the signal inside the band the request bought; it does not widen that band,
+ * and what the filters removed stays removed.
+ * The first call puts the client into the object's tuner bank (created then) with phase 0, where it stays, at (0, 0) too: its phase
+ * is continuous over every later change.  Per blocks call the tuned clients' final rows go through ONE tuner feed (one launch, one
+ * table copy, counted in xlating_serve_last_ops) behind the resampler bank's, and everything behind it -- the pack, the gain and the
+ * levels, xlating_serve_outputs_device and with it a spectrum bank -- sees the tuned row.  With no client ever tuned a call is, launch
+ * for launch and byte for byte, what it is without these functions.
+ * 0; -EINVAL: the cs16 family, no such client, or a quotient that is not finite or not below 0.5 in magnitude; the banks' errors. */
+int xlating_serve_set_tune(xlating_serve *s, int client_id, double shift_hz, double ramp_hz_per_s);
+/* The client's latest changes of rotation, at most 64 and at most cap, oldest first: from sample first_sample[i] of the client's
+ * delivered stream the steps are F[i] and R[i] (turns * 2^64 per sample and per sample^2, xlating_tune.h); the phase at the first
+ * entry's sample is 0 and continues through every later entry, and before the first entry the stream is not rotated.  With it a
+ * consumer knows the exact rotation of every delivered sample.  Returns the number of entries written, or -EINVAL. */
+int xlating_serve_tune_log(xlating_serve *s, int client_id, size_t cap, uint64_t *first_sample, int64_t *F, int64_t *R);
 
 void xlating_serve_destroy(xlating_serve *s);
 

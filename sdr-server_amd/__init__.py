@@ -1202,11 +1202,155 @@ DELIVERY_SYMBOLS = ["xlating_delivery_create", "xlating_delivery_pack_device", "
                     "xlating_delivery_wait", "xlating_delivery_row", "xlating_delivery_release", "xlating_delivery_last_ops",
                     "xlating_delivery_chunk_bytes", "xlating_delivery_destroy", "xlating_delivery_pack_device_cs16_gain",
                     "xlating_delivery_row_level"]
+# ------------------------------------------------------------------------------------------------- tuner bank (libxlating_tune.so)
+TUNE_SYMBOLS = ["xlating_tune_bank_create", "xlating_tune_bank_add", "xlating_tune_bank_remove", "xlating_tune_bank_set",
+                "xlating_tune_bank_feed_device", "xlating_tune_bank_output_device", "xlating_tune_bank_state",
+                "xlating_tune_bank_last_feed_ops", "xlating_tune_bank_destroy", "xlating_tune_cs", "xlating_tune_from_hz",
+                "xlating_tune_chunk_samples"]
+_tlib = None
+
+
+def tune_library_path():
+    return os.path.join(os.path.dirname(library_path()), "libxlating_tune.so")
+
+
+def tune_lib():
+    """include/xlating_tune.h: the phase-continuous rotator bank behind the engine."""
+    global _tlib
+    if _tlib is not None:
+        return _tlib
+    lib()  # (torch's HIP runtime first, see lib())
+    path = tune_library_path()
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    T = C.CDLL(path)
+    T.xlating_tune_bank_create.argtypes = [C.POINTER(C.c_void_p)]
+    T.xlating_tune_bank_create.restype = C.c_int
+    T.xlating_tune_bank_add.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64]
+    T.xlating_tune_bank_add.restype = C.c_int
+    T.xlating_tune_bank_remove.argtypes = [C.c_void_p, C.c_int]
+    T.xlating_tune_bank_remove.restype = C.c_int
+    T.xlating_tune_bank_set.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64]
+    T.xlating_tune_bank_set.restype = C.c_int
+    T.xlating_tune_bank_feed_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    T.xlating_tune_bank_feed_device.restype = C.c_int
+    T.xlating_tune_bank_output_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    T.xlating_tune_bank_output_device.restype = C.c_int
+    T.xlating_tune_bank_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_uint64)]
+    T.xlating_tune_bank_state.restype = C.c_int
+    T.xlating_tune_bank_last_feed_ops.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    T.xlating_tune_bank_last_feed_ops.restype = C.c_int
+    T.xlating_tune_bank_destroy.argtypes = [C.c_void_p]
+    T.xlating_tune_bank_destroy.restype = None
+    T.xlating_tune_cs.argtypes = [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    T.xlating_tune_cs.restype = None
+    T.xlating_tune_from_hz.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    T.xlating_tune_from_hz.restype = C.c_int
+    T.xlating_tune_chunk_samples.argtypes = []
+    T.xlating_tune_chunk_samples.restype = C.c_uint
+    _tlib = T
+    return T
+
+
+def tune_cs(p):
+    """-> (cos, sin) of 2 pi p / 2^32 as float32, by the tuner bank's rule (csrc/xl_tune_rule.h); p: 0 .. 2^32 - 1"""
+    c, s = C.c_float(0), C.c_float(0)
+    tune_lib().xlating_tune_cs(int(p) & 0xFFFFFFFF, C.byref(c), C.byref(s))
+    return np.float32(c.value), np.float32(s.value)
+
+
+def tune_from_hz(shift_hz, ramp_hz_per_s, rate):
+    """-> (F, R): the steps of a shift in Hz and a ramp in Hz per second at a sample rate (XlatingError -EINVAL: a quotient that is
+    not finite or not below 0.5 in magnitude)"""
+    F, R = C.c_int64(0), C.c_int64(0)
+    code = tune_lib().xlating_tune_from_hz(float(shift_hz), float(ramp_hz_per_s), float(rate), C.byref(F), C.byref(R))
+    if code != 0:
+        raise XlatingError("xlating_tune_from_hz", code)
+    return F.value, R.value
+
+
+def tune_chunk_samples():
+    return tune_lib().xlating_tune_chunk_samples()
+
+
+class TuneBank:
+    """One `xlating_tune_bank *` (include/xlating_tune.h): many complex float32 streams, each rotated by its own phase-continuous
+    shift (P, F, R), advanced together by one feed of device buffers; the latest feed's rows are read per stream on the device."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        code = tune_lib().xlating_tune_bank_create(C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_tune_bank_create", code)
+        self.h = h
+
+    def add(self, P=0, F=0, R=0):
+        sid = tune_lib().xlating_tune_bank_add(self.h, int(P) & 0xFFFFFFFFFFFFFFFF, int(F), int(R))
+        if sid < 0:
+            raise XlatingError("xlating_tune_bank_add", sid)
+        return sid
+
+    def remove(self, stream_id):
+        code = tune_lib().xlating_tune_bank_remove(self.h, stream_id)
+        if code != 0:
+            raise XlatingError("xlating_tune_bank_remove", code)
+
+    def set(self, stream_id, F, R=0):
+        """new steps from the next sample fed on; the phase is untouched"""
+        code = tune_lib().xlating_tune_bank_set(self.h, stream_id, int(F), int(R))
+        if code != 0:
+            raise XlatingError("xlating_tune_bank_set", code)
+
+    def feed(self, ids, ptrs, counts, stream=0):
+        """stream ids[i] rotates counts[i] complex samples at device address ptrs[i], read in place, ordered on `stream`."""
+        a = np.ascontiguousarray(ids, dtype=np.intc)
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        assert a.size == p.size == c.size
+        code = tune_lib().xlating_tune_bank_feed_device(self.h, a.size, a.ctypes.data, p.ctypes.data, c.ctypes.data, stream)
+        if code != 0:
+            raise XlatingError("xlating_tune_bank_feed_device", code)
+
+    def output_device(self, stream_id):
+        """-> (device pointer | None, complex samples) of the stream's row of the latest feed; valid until the next feed"""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        code = tune_lib().xlating_tune_bank_output_device(self.h, stream_id, C.byref(p), C.byref(n))
+        if code != 0:
+            raise XlatingError("xlating_tune_bank_output_device", code)
+        return p.value, n.value
+
+    def state(self, stream_id):
+        """-> (P, F, R, consumed) as the next sample fed will see them: Python integers, host state, no waiting"""
+        P, F, R, n = C.c_uint64(0), C.c_int64(0), C.c_int64(0), C.c_uint64(0)
+        code = tune_lib().xlating_tune_bank_state(self.h, stream_id, C.byref(P), C.byref(F), C.byref(R), C.byref(n))
+        if code != 0:
+            raise XlatingError("xlating_tune_bank_state", code)
+        return P.value, F.value, R.value, n.value
+
+    def last_feed_ops(self):
+        """-> (kernel launches, memory copies) the latest feed issued"""
+        a, b = C.c_uint(0), C.c_uint(0)
+        tune_lib().xlating_tune_bank_last_feed_ops(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            tune_lib().xlating_tune_bank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 SERVE_SYMBOLS = ["xlating_serve_create", "xlating_serve_request", "xlating_serve_remove", "xlating_serve_blocks_host",
                  "xlating_serve_blocks_device", "xlating_serve_flush", "xlating_serve_outputs_device", "xlating_serve_dropped",
                  "xlating_serve_engine", "xlating_serve_last_ops", "xlating_serve_sink_stats", "xlating_serve_destroy",
                  "xlating_serve_set_gain", "xlating_serve_set_auto_gain", "xlating_serve_enable_levels", "xlating_serve_levels",
-                 "xlating_serve_gain_log"]
+                 "xlating_serve_gain_log", "xlating_serve_set_tune", "xlating_serve_tune_log"]
 SERVE_FAMILY = {"cf32": 0, "cs16": 1, "cf32-cs16": 2}  # (2: the cf32 family, narrowed to cs16 by the delivery)
 _vlib = None
 
@@ -1229,6 +1373,7 @@ def serve_lib():
     if _vlib is not None:
         return _vlib
     resample_lib()  # (torch's HIP runtime first, see lib(); the libraries this one links)
+    tune_lib()
     path = serve_library_path()
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
@@ -1285,6 +1430,10 @@ def serve_lib():
     V.xlating_serve_levels.restype = C.c_int
     V.xlating_serve_gain_log.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
     V.xlating_serve_gain_log.restype = C.c_int
+    V.xlating_serve_set_tune.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+    V.xlating_serve_set_tune.restype = C.c_int
+    V.xlating_serve_tune_log.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_serve_tune_log.restype = C.c_int
     V.xlating_serve_destroy.argtypes = [C.c_void_p]
     V.xlating_serve_destroy.restype = None
     _vlib = V
@@ -1484,6 +1633,21 @@ class Serve:
         if n < 0:
             raise XlatingError("xlating_serve_gain_log", n)
         return [(int(f[i]), int(g[i])) for i in range(n)]
+
+    def set_tune(self, client_id, shift_hz, ramp_hz_per_s=0.0):
+        """families "cf32" and "cf32-cs16": the client's final row rotated, phase-continuously, by shift_hz ramping by ramp_hz_per_s
+        from the next blocks call on (include/xlating_serve.h; the rotation follows the client's filters)"""
+        code = serve_lib().xlating_serve_set_tune(self.h, client_id, float(shift_hz), float(ramp_hz_per_s))
+        if code != 0:
+            raise XlatingError("xlating_serve_set_tune", code)
+
+    def tune_log(self, client_id, cap=64):
+        """-> [(first_sample, F, R)]: the client's latest changes of rotation, oldest first"""
+        f, F, R = np.zeros(cap, np.uint64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        n = serve_lib().xlating_serve_tune_log(self.h, client_id, cap, f.ctypes.data, F.ctypes.data, R.ctypes.data)
+        if n < 0:
+            raise XlatingError("xlating_serve_tune_log", n)
+        return [(int(f[i]), int(F[i]), int(R[i])) for i in range(n)]
 
     def dropped(self, cap=4096):
         ids = (C.c_int * cap)()

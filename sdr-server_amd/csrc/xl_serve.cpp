@@ -1,6 +1,7 @@
 // xl_serve.cpp -- the serve object (include/xlating_serve.h): one band on one GPU, from the wire request to the sink.  It owns an
-// engine, at most one resampler bank of its family, a delivery object and the sinks, and calls nothing but their public functions; the
-// ordering rule between them is stated in the header and kept in xl_serve_run below.  No arithmetic on samples happens here.
+// engine, at most one resampler bank of its family, at most one tuner bank, a delivery object and the sinks, and calls nothing but their
+// public functions; the ordering rule between them is stated in the header and kept in xl_serve_run below.  No arithmetic on samples
+// happens here.
 #include "../../include/xlating_serve.h"
 
 #include <errno.h>
@@ -17,21 +18,35 @@
 #include "../../include/xlating_resample.h"
 #include "../../include/xlating_resample_q15.h"
 #include "../../include/xlating_sinks.h"
+#include "../../include/xlating_tune.h"
 #include "../../include/xlating_wire.h"
 #include "xl_common.h"
 #include "xl_serve_gain.h"
 
 namespace {
 
+// the latest XL_SERVE_TUNE_LOG changes of a client's rotation, oldest first (xlating_serve_tune_log)
+#define XL_SERVE_TUNE_LOG 64
+struct XlServeTuneLog {
+  uint64_t first_sample[XL_SERVE_TUNE_LOG];
+  int64_t F[XL_SERVE_TUNE_LOG], R[XL_SERVE_TUNE_LOG];
+  uint32_t n = 0, head = 0;
+};
+
 struct XlServeClient {
   int rs = -1;           // its stream of the resampler bank, or -1: the rate divides the band rate
   uint32_t band_freq = 0;
+  // xlating_serve_set_tune: the client's stream of the tuner bank (-1 until its first call), its final rate, the log of its changes
+  int tn = -1;
+  bool tn_fed = false;   // the latest blocks call rotated its row
+  double rate = 0.0;
+  XlServeTuneLog tune_log;
   // XL_SERVE_CF32_AS_CS16: the client's gain and meter (xl_serve_gain.h holds the policy and the log)
   int8_t gain = 0;       // from the next call that is packed
   bool agc = false;      // xlating_serve_set_auto_gain
   XlServeGainState agc_state = {0};
   XlServeGainLog log = {};
-  uint64_t packed = 0;   // samples of its delivered stream packed so far: where a new gain begins
+  uint64_t packed = 0;   // samples of its delivered stream packed so far: where a new gain or a new rotation begins
   uint64_t clipped_total = 0;
   uint32_t peak_bits = 0, clipped = 0, nans = 0;  // of the latest call queued to its sink
   int8_t level_gain = 0;                          // the gain that call was packed with
@@ -50,6 +65,7 @@ struct xlating_serve_t {
   xlating_delivery *dlv = nullptr;
   xlating_resample_bank *rb = nullptr;       // cf32 family, created with the first fractional client
   xlating_resample_q15_bank *rq = nullptr;   // cs16 family
+  xlating_tune_bank *tb = nullptr;           // created with the first xlating_serve_set_tune
   hipStream_t st = nullptr;                  // the feed and the pack launch
   hipEvent_t ev_call = nullptr, ev_pack = nullptr;  // behind the engine call; behind the pack launch
   bool packed = false;                       // ev_pack has been recorded
@@ -65,9 +81,9 @@ struct xlating_serve_t {
   unsigned launches = 0, copies = 0;
   uint64_t d2h_bytes = 0;
   // (scratch of a call)
-  std::vector<int> ids, rs_ids;
-  std::vector<const void *> rows, rs_rows;
-  std::vector<size_t> lens, rs_lens, bytes;
+  std::vector<int> ids, rs_ids, tn_ids;
+  std::vector<const void *> rows, rs_rows, tn_rows;
+  std::vector<size_t> lens, rs_lens, tn_lens, bytes;
 };
 
 // the bank's functions for either family
@@ -105,13 +121,14 @@ static void xl_serve_bank_ops(xlating_serve *s, unsigned *launches, unsigned *co
   else (void)xlating_resample_bank_last_feed_ops(s->rb, launches, copies);
 }
 
-// the client leaves the engine, the bank and the sinks
+// the client leaves the engine, the banks and the sinks
 static void xl_serve_forget(xlating_serve *s, int id) {
   const auto it = s->clients.find(id);
   if (it == s->clients.end()) return;
   (void)xlating_sinks_detach(s->sinks, id);
   (void)xlating_batch_remove_client(s->eng, id);
   if (it->second.rs >= 0) (void)xl_serve_bank_remove(s, it->second.rs);
+  if (it->second.tn >= 0) (void)xlating_tune_bank_remove(s->tb, it->second.tn);
   s->clients.erase(it);
   // the row the pending ticket holds under this id is nobody's now: the engine gives the id to the next client that joins, and that
   // client's stream starts with its own first block
@@ -273,6 +290,7 @@ extern "C" int xlating_serve_request(xlating_serve *s, const uint8_t *msg, size_
     try {
       XlServeClient c;
       c.rs = rsid, c.band_freq = req.band_freq;
+      c.rate = (double)s->cfg.band_sampling_rate * rs.L / ((double)adm.decimation * rs.M);
       s->clients[id] = c;
     } catch (const std::bad_alloc &) {
       ok = false;
@@ -307,6 +325,16 @@ static int xl_serve_final_rows(xlating_serve *s, size_t n, const int *ids, const
   return rc;
 }
 
+// ... replaced once more by the tuner bank's for the clients the latest call rotated
+static int xl_serve_tuned_rows(xlating_serve *s, size_t n, const int *ids, const void **rows, size_t *lens) {
+  int rc = 0;
+  for (size_t i = 0; rc == 0 && i < n; ++i) {
+    const XlServeClient &c = s->clients[ids[i]];
+    if (c.tn >= 0 && c.tn_fed) rc = xlating_tune_bank_output_device(s->tb, c.tn, &rows[i], &lens[i]);
+  }
+  return rc;
+}
+
 // everything behind the engine call: feed, pack, hand-over
 static int xl_serve_run(xlating_serve *s) {
   int rc = 0;
@@ -331,6 +359,21 @@ static int xl_serve_run(xlating_serve *s) {
     s->launches += l, s->copies += c;
     if ((rc = xl_serve_final_rows(s, n, s->ids.data(), s->rows.data(), s->lens.data(), true)) != 0) return rc;
   }
+  // the tuned clients' final rows through one tuner feed, behind the resampler bank's on the same stream
+  s->tn_ids.clear(), s->tn_rows.clear(), s->tn_lens.clear();
+  for (size_t i = 0; i < n; ++i) {
+    XlServeClient &c = s->clients[s->ids[i]];
+    c.tn_fed = c.tn >= 0;
+    if (c.tn_fed) s->tn_ids.push_back(c.tn), s->tn_rows.push_back(s->rows[i]), s->tn_lens.push_back(s->lens[i]);
+  }
+  if (!s->tn_ids.empty()) {
+    if ((rc = xlating_tune_bank_feed_device(s->tb, s->tn_ids.size(), s->tn_ids.data(), s->tn_rows.data(), s->tn_lens.data(), s->st)) != 0)
+      return rc;
+    unsigned l = 0, c = 0;
+    (void)xlating_tune_bank_last_feed_ops(s->tb, &l, &c);
+    s->launches += l, s->copies += c;
+    if ((rc = xl_serve_tuned_rows(s, n, s->ids.data(), s->rows.data(), s->lens.data())) != 0) return rc;
+  }
   for (size_t i = 0; i < n; ++i) s->bytes[i] = s->lens[i] * s->esz;
   // the pack with gains and levels exactly when somebody asked for either; otherwise the call is what it always was
   bool gained = s->narrow && s->levels_on;
@@ -342,8 +385,7 @@ static int xl_serve_run(xlating_serve *s) {
                 : s->narrow ? xlating_delivery_pack_device_cs16(s->dlv, n, s->ids.data(), s->rows.data(), s->lens.data(), s->st)
                             : xlating_delivery_pack_device(s->dlv, n, s->ids.data(), s->rows.data(), s->bytes.data(), s->st);
   if (t < 0) return t;
-  if (s->narrow)
-    for (size_t i = 0; i < n; ++i) s->clients[s->ids[i]].packed += s->lens[i];
+  for (size_t i = 0; i < n; ++i) s->clients[s->ids[i]].packed += s->lens[i];
   unsigned l = 0, c = 0;
   (void)xlating_delivery_last_ops(s->dlv, &l, &c, &s->d2h_bytes);
   s->launches += l, s->copies += c;
@@ -413,7 +455,8 @@ extern "C" int xlating_serve_outputs_device(xlating_serve *s, size_t n, const in
   if (s == nullptr || (n > 0 && (client_ids == nullptr || d_rows == nullptr || n_complex == nullptr))) return -EINVAL;
   for (size_t i = 0; i < n; ++i)
     if (s->clients.count(client_ids[i]) == 0) return -EINVAL;
-  return xl_serve_final_rows(s, n, client_ids, d_rows, n_complex, false);
+  const int rc = xl_serve_final_rows(s, n, client_ids, d_rows, n_complex, false);
+  return rc != 0 ? rc : xl_serve_tuned_rows(s, n, client_ids, d_rows, n_complex);
 }
 
 extern "C" size_t xlating_serve_dropped(xlating_serve *s, int *client_ids, size_t cap) {
@@ -482,6 +525,52 @@ extern "C" int xlating_serve_gain_log(xlating_serve *s, int client_id, size_t ca
   return (int)xl_serve_gain_log_read(&c->log, cap > XL_SERVE_GAIN_LOG ? XL_SERVE_GAIN_LOG : (uint32_t)cap, first_sample, gain_log2);
 }
 
+static void xl_serve_tune_log_add(XlServeTuneLog *l, uint64_t first_sample, int64_t F, int64_t R) {
+  // two changes before any sample was packed between them: the later one stands
+  if (l->n > 0u && l->first_sample[(l->head + l->n - 1u) % XL_SERVE_TUNE_LOG] == first_sample) {
+    const uint32_t at = (l->head + l->n - 1u) % XL_SERVE_TUNE_LOG;
+    l->F[at] = F, l->R[at] = R;
+    return;
+  }
+  if (l->n == XL_SERVE_TUNE_LOG) l->head = (l->head + 1u) % XL_SERVE_TUNE_LOG, --l->n;
+  const uint32_t at = (l->head + l->n) % XL_SERVE_TUNE_LOG;
+  l->first_sample[at] = first_sample, l->F[at] = F, l->R[at] = R;
+  ++l->n;
+}
+
+extern "C" int xlating_serve_set_tune(xlating_serve *s, int client_id, double shift_hz, double ramp_hz_per_s) {
+  if (s == nullptr || s->cfg.family == XL_SERVE_CS16) return -EINVAL;
+  const auto it = s->clients.find(client_id);
+  if (it == s->clients.end()) return -EINVAL;
+  XlServeClient &c = it->second;
+  int64_t F = 0, R = 0;
+  int rc = xlating_tune_from_hz(shift_hz, ramp_hz_per_s, c.rate, &F, &R);
+  if (rc != 0) return rc;
+  if (c.tn < 0) {  // from here on the client stays in the bank, at (0, 0) too: its phase is continuous
+    (void)hipSetDevice(s->device);
+    if (s->tb == nullptr && (rc = xlating_tune_bank_create(&s->tb)) != 0) return rc;
+    if ((rc = xlating_tune_bank_add(s->tb, 0u, F, R)) < 0) return rc;
+    c.tn = rc;
+  } else if ((rc = xlating_tune_bank_set(s->tb, c.tn, F, R)) != 0) {
+    return rc;
+  }
+  xl_serve_tune_log_add(&c.tune_log, c.packed, F, R);
+  return 0;
+}
+
+extern "C" int xlating_serve_tune_log(xlating_serve *s, int client_id, size_t cap, uint64_t *first_sample, int64_t *F, int64_t *R) {
+  if (s == nullptr || s->cfg.family == XL_SERVE_CS16 || (cap > 0 && (first_sample == nullptr || F == nullptr || R == nullptr))) return -EINVAL;
+  const auto it = s->clients.find(client_id);
+  if (it == s->clients.end()) return -EINVAL;
+  const XlServeTuneLog &l = it->second.tune_log;
+  const uint32_t n = l.n < cap ? l.n : (uint32_t)cap;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t at = (l.head + (l.n - n) + i) % XL_SERVE_TUNE_LOG;
+    first_sample[i] = l.first_sample[at], F[i] = l.F[at], R[i] = l.R[at];
+  }
+  return (int)n;
+}
+
 extern "C" struct xlating_batch_t *xlating_serve_engine(xlating_serve *s) { return s ? s->eng : nullptr; }
 
 extern "C" int xlating_serve_last_ops(const xlating_serve *s, unsigned *launches_after_engine, unsigned *copies_after_engine,
@@ -503,6 +592,7 @@ extern "C" void xlating_serve_destroy(xlating_serve *s) {
   if (s->dlv) xlating_delivery_destroy(s->dlv);
   if (s->rb) xlating_resample_bank_destroy(s->rb);
   if (s->rq) xlating_resample_q15_bank_destroy(s->rq);
+  if (s->tb) xlating_tune_bank_destroy(s->tb);
   if (s->eng) xlating_batch_destroy(s->eng);
   if (s->ev_call) (void)hipEventDestroy(s->ev_call);
   if (s->ev_pack) (void)hipEventDestroy(s->ev_pack);

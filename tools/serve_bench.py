@@ -23,6 +23,10 @@ client's sink is a pipe, and one reader thread drains them all.
       batch, the rows of the headline call; HIP events, the two alternating in one process, the spread of each over its rounds
       reported (profiles/serve_gain_vs_parent.txt)
 
+  (f) --tune: only the call period of Serve (cf32, overlap 0 and 1) with EVERY client tuned (xlating_serve_set_tune, a shift and a
+      ramp of its own each: one tuner-bank feed more per call) against the same object untuned, the loops alternating in one
+      process as in (b); the untuned loop's spread over its rounds is reported (profiles/tune_bank_vs_pack.txt)
+
 Prints a report; profiles/serve_vs_parent.txt is one run of it on an MI355X."""
 import argparse
 import os
@@ -98,9 +102,11 @@ def make_serve(n, family, overlap, group, drain, out_dir):
     s = xl.Serve(BAND_RATE, "cu8", BUFFER, out_dir, family=family, native=False, any_rate=True, overlap=overlap, group_blocks=group,
                  writer_threads=8, queue_bytes=(BURST + 2) * group * (BUFFER // 2 // 42 + 8) * 8, delivery_slots=2)
     s.engine().set_option("expected_clients", min(n, 8192))
+    s.ids = []  # the ids the requests returned
     for c, w in zip(centers(n), drain.pipes(n)):
         code, _, cid = s.request(xl.wire_build_request(c, RATE, BAND_FREQ, 1), socket_fd=w)
         assert code == 0
+        s.ids.append(cid)
     return s
 
 
@@ -281,6 +287,43 @@ def run_gain(args, out):
     d.close()
 
 
+def run_tune(args, drain, out):
+    """the call period with every client tuned against the same run untuned, per overlap, alternating rounds"""
+    import torch
+
+    x = np.random.default_rng(1).integers(0, 256, BUFFER * args.group, dtype=np.uint8)
+    loops = {}
+    serves = []
+    for ov in (0, 1):
+        for tuned in (False, True):
+            s = make_serve(args.clients, "cf32", ov, args.group, drain, args.out)
+            if tuned:
+                assert len(s.ids) == args.clients
+                for i, cid in enumerate(s.ids):
+                    s.set_tune(cid, -10000.0 + 20000.0 * i / args.clients, 300.0 - 600.0 * i / args.clients)
+            serves.append(s)
+            loops[f"overlap={ov} {'tuned  ' if tuned else 'untuned'}"] = (lambda x, s=s: s.blocks_host(x, args.group), torch.cuda.synchronize, s.flush, s)
+    res = {k: [] for k in loops}
+    for rnd in range(args.rounds):
+        for name, (step, sync, flush, _) in loops.items():
+            res[name].append(period(step, sync, flush, x, args.seconds))
+    out.append(f"[tune] call period, {args.clients} clients x {RATE} Hz, {args.group} blocks per call, cf32, sinks: pipes drained by one thread, "
+               f"bursts of {BURST} calls; every client tuned against the same run untuned")
+    for name, rs in res.items():
+        out.append(f"  {name:18s} ms per call, rounds: " + "  ".join(f"{1e3 * p:8.3f}" for p, _ in rs) +
+                   f"   launches, copies behind the engine call: {loops[name][3].last_ops()[:2]}")
+    for ov in (0, 1):
+        u = [p for p, _ in res[f"overlap={ov} untuned"]]
+        t = [p for p, _ in res[f"overlap={ov} tuned  "]]
+        spread = (max(u) - min(u)) / min(u)
+        r = float(np.median(t) / np.median(u))
+        out.append(f"  overlap={ov}: tuned / untuned (medians) = {r:.3f}, + {1e3 * (np.median(t) - np.median(u)):.3f} ms per call; the untuned loop's spread "
+                   f"over its rounds is {100 * spread:.1f} %: the difference {'exceeds' if abs(r - 1.0) > spread else 'lies within'} it")
+    out.append(f"  clients dropped by back-pressure: {[len(s.dropped()) for s in serves]}")
+    for s in serves:
+        s.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", type=int, default=1024)
@@ -291,6 +334,7 @@ def main(argv=None):
     ap.add_argument("--families", default="cf32,cs16", help="of cf32, cs16, cf32-cs16")
     ap.add_argument("--pack", action="store_true", help="only (a): the two pack launches against a device-to-device copy")
     ap.add_argument("--gain", action="store_true", help="only (e): the pack launch with gains and levels against the narrowing pack launch")
+    ap.add_argument("--tune", action="store_true", help="only (f): the call with every client tuned against the same run untuned")
     ap.add_argument("--out", default="/tmp/serve_bench_out")
     ap.add_argument("--report", default=None)
     a = ap.parse_args(argv)
@@ -300,11 +344,15 @@ def main(argv=None):
     resource.setrlimit(resource.RLIMIT_NOFILE, (hard if hard != resource.RLIM_INFINITY else 1 << 16, hard))
     os.makedirs(a.out, exist_ok=True)
     out = [f"serve_bench: {xl.device_info()}"]
-    if a.gain:
+    if a.tune:
+        drain = Drain()
+        run_tune(a, drain, out)
+        drain.close()
+    elif a.gain:
         run_gain(a, out)
     else:
         run_pack(a, out)
-    if not a.pack and not a.gain:
+    if not a.pack and not a.gain and not a.tune:
         drain = Drain()
         for family in a.families.split(","):
             run_periods(a, family, drain, out)

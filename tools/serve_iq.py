@@ -13,7 +13,12 @@ every admitted client fast enough also gets <out>/<id>.png from a spectrum bank 
 (xlating_serve_outputs_device) after every block.  With --cs16-out, --gain G delivers every client's stream as y * 2^(15 + G) (G a
 power of two's exponent, -48 .. 48) and --auto-gain lets the object choose each client's G from its level (include/xlating_serve.h);
 both also write <out>/<id>.gain: lines "first_sample gain_log2" from the client's gain log -- from that sample of the file on, the
-int16 values are y * 2^(15 + gain_log2); before the first line the gain is 0 -- and a last line "clipped_total N".  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
+int16 values are y * 2^(15 + gain_log2); before the first line the gain is 0 -- and a last line "clipped_total N".  --tune FILE (not with --variant q15) tunes running clients
+(xlating_serve_set_tune: a phase-continuous rotation of the client's final row, behind its filters): each line of FILE is
+"client_index seconds shift_hz ramp_hz_per_s" (client_index counts the --client options from 0; '#' starts a comment) and is applied
+before the first call whose first band sample is at or after `seconds`; every client so tuned also gets <out>/<id>.tune: lines
+"first_sample F R" from its tune log -- from that sample of the file on the steps are F and R (turns * 2^64 per sample and per
+sample^2), the phase 0 at the first line's sample and continuous from there.  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
 launch and one copy of exactly the delivered bytes."""
 import argparse
 import os
@@ -32,7 +37,7 @@ DTYPES = replay_iq.DTYPES
 
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
            gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False, cs16_out=False, gain=None,
-           auto_gain=False):
+           auto_gain=False, tune=None):
     """replay_iq.replay's arguments and its triple: {client_id: (center_hz, rate_hz)} of the admitted requests, [(center, rate,
     failure_details)] of the refused ones, and the counters -- blocks, and the sinks' own bytes_written and blocks_dropped
     (xlating_serve_sink_stats: what replay_iq reads from its Sinks objects)."""
@@ -50,15 +55,20 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
     metered = family == "cf32-cs16" and (gain is not None or auto_gain)
     if (gain is not None or auto_gain) and not metered:
         raise ValueError("--gain and --auto-gain need --cs16-out with --variant native | optimized")
+    tune = sorted(tune or [], key=lambda t: t[1])  # [(client index, seconds, shift_hz, ramp_hz_per_s)], stable in time
+    if tune and q15:
+        raise ValueError("--tune needs --variant native | optimized")
+    by_index, tuned = {}, set()
     bank = xl.SpectrumBank(waterfall_width, "cs16" if q15 else "cf32", wide=waterfall_width > 8192) if waterfall_width else None
     streams, rows, samples = {}, {}, {}
     admitted, rejected = {}, []
-    for center, rate in clients:
+    for index, (center, rate) in enumerate(clients):
         code, resp, cid = serve.request(xl.wire_build_request(center, rate, band_freq, 0))
         if code != 0:
             rejected.append((center, rate, xl.wire_parse_response(resp)[2]))
             continue
         admitted[cid] = (center, rate)
+        by_index[index] = cid
         if metered:
             if gain is not None:
                 serve.set_gain(cid, gain)
@@ -76,6 +86,11 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
             blk = blk[:-1]
         if blk.size == 0:
             break
+        while tune and tune[0][1] * band_rate <= off // 2:  # (the call's first band sample is at or after the line's time)
+            index, _, shift, ramp = tune.pop(0)
+            if by_index.get(index) in admitted:
+                serve.set_tune(by_index[index], shift, ramp)
+                tuned.add(by_index[index])
         serve.blocks_host(blk)
         for cid in serve.dropped():
             admitted.pop(cid, None)
@@ -104,6 +119,10 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
                 for first, g in serve.gain_log(cid):
                     f.write(f"{first} {g}\n")
                 f.write(f"clipped_total {total}\n")
+    for cid in sorted(tuned & set(admitted)):
+        with open(os.path.join(out_dir, f"{cid}.tune"), "w") as f:
+            for first, F, R in serve.tune_log(cid):
+                f.write(f"{first} {F} {R}\n")
     for cid, sid in streams.items():
         rows[cid].append(bank.take_rows(sid)[1])
         px = np.concatenate(rows[cid])[:samples[cid] // admitted[cid][1]]
@@ -140,7 +159,19 @@ def parse_args(argv=None):
                     help="with --cs16-out: deliver y * 2^(15 + G), G in -48 .. 48; also writes <id>.gain")
     ap.add_argument("--auto-gain", action="store_true",
                     help="with --cs16-out: the object picks each client's gain from its level; also writes <id>.gain")
+    ap.add_argument("--tune", default=None, metavar="FILE",
+                    help="lines 'client_index seconds shift_hz ramp_hz_per_s': tune running clients; also writes <id>.tune")
     return ap.parse_args(argv)
+
+
+def read_tune_file(path):
+    """-> [(client index, seconds, shift_hz, ramp_hz_per_s)]"""
+    out = []
+    for line in open(path):
+        f = line.split("#")[0].split()
+        if f:
+            out.append((int(f[0]), float(f[1]), float(f[2]), float(f[3])))
+    return out
 
 
 def main(argv=None):
@@ -148,7 +179,8 @@ def main(argv=None):
     clients = [tuple(int(v) for v in c.split(":")) for c in a.client]
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate, a.variant,
                           a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel, q15_nco=a.q15_nco,
-                          overlap=a.overlap, cs16_out=a.cs16_out, gain=a.gain, auto_gain=a.auto_gain)
+                          overlap=a.overlap, cs16_out=a.cs16_out, gain=a.gain, auto_gain=a.auto_gain,
+                          tune=read_tune_file(a.tune) if a.tune else None)
     ext = "cs16" if a.variant == "q15" or a.cs16_out else "cf32"
     for cid, (c, r) in adm.items():
         print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{ext}{'.gz' if a.gzip else ''}")
