@@ -313,4 +313,47 @@ XL_DEV void xl_phase_walk(v2f p, const uint32_t m0, const uint32_t count, const 
   }
 }
 
+// The inverse launches' consumer, one lane of a wave in converged control flow: the phases of a duty on the table's grid (xl_grid.h:
+// xl_grid_duty), handed to store(i, phase) for phase du.ma + i where it lies in the column's window.  `p` is table entry du.tab, the
+// phase of output du.ma itself: no step comes before the first store.  Every lane expands XL_PH_STRIDE phases, the column's last lane
+// (`last`) `extra` more (wave-uniform, xl_grid_extra).  Where no lane of the wave has a block end in front of a phase it stores -- all
+// but a few waves of a call -- the walk is a straight line of plain steps and predicated stores; otherwise, and in calls that step with
+// the fused operations, each lane with something to store takes xl_phase_walk over its range.  rS, rD: xl_rcp32 of the call's S and D.
+// The duty worked out again where the walk starts, from opaque copies of the column's record: a kernel that loads its table entry early
+// carries the record through its transforms, not the duty's integers (the registers the transforms need).
+XL_DEV XlGridDuty xl_grid_duty_again(const uint32_t j0_ref, uint32_t delta, uint32_t out_off, const uint32_t D, const XlPos pos,
+                                     const uint32_t V, const uint32_t s, const uint32_t g) {
+  asm volatile("" : "+v"(delta), "+v"(out_off));
+  return xl_grid_duty(j0_ref, delta, D, pos, V, s, g, out_off == 0xFFFFFFFFu);
+}
+
+template <class Store>
+XL_DEV void xl_phase_expand(v2f p, const XlGridDuty du, const bool last, const uint32_t extra, const v2f inc, const uint32_t rS,
+                            const uint32_t rD, Store store) {
+  if (__builtin_amdgcn_ballot_w64(du.span != 0u) == 0ull) return;
+  // phases ma + i, i0 <= i < iend, are the lane's stores (rel is below zero by i0 when the window starts inside the lane's range)
+  const uint32_t n = XL_PH_STRIDE + (last ? extra : 0u);
+  const uint32_t iend = du.span - du.rel < n ? du.span - du.rel : n;
+  bool slow = (du.bnd.flags & XL_POS_FMA_STEP) != 0u;
+  if (!slow && !(du.bnd.flags & XL_POS_NORENORM) && du.bnd.G > 1u) {
+    const uint32_t nb = xl_bnd_next_rcp(du.bnd, rS, rD, du.ma);  // (> ma; the phase of output nb is the first renormalised one)
+    slow = __builtin_amdgcn_ballot_w64(du.span != 0u && nb - du.ma < iend) != 0ull;
+  }
+  if (!slow) {
+    if (du.rel < du.span) store(0u, p);
+#pragma unroll
+    for (uint32_t i = 1u; i < XL_PH_STRIDE; ++i) {
+      p = xl_nco_next(p, inc);
+      if (du.rel + i < du.span) store(i, p);
+    }
+    for (uint32_t e = 0u; e < extra; ++e) {
+      p = xl_nco_next(p, inc);
+      if (last && du.rel + XL_PH_STRIDE + e < du.span) store(XL_PH_STRIDE + e, p);
+    }
+  } else if (du.span != 0u) {
+    const uint32_t i0 = (int32_t)du.rel < 0 ? 0u - du.rel : 0u;
+    xl_phase_walk(p, du.ma + i0, iend - i0, inc, du.bnd, [&](uint32_t i, v2f phs) { store(i0 + i, phs); });
+  }
+}
+
 #endif  // XL_DEV_INLINE_H_

@@ -148,4 +148,58 @@ XL_HD uint32_t xl_col_duty_count(XlColDuty d) {
   return d.ok ? (left < span ? left : span) : 0u;
 }
 
+/* ---- the same expansion with the duties on the TABLE's grid (the inverse launches; xl_col_duty above stays for its test and as the
+ * statement these duties are checked against).  A column's outputs in segment s are m in [m_lo, m_hi): the shared points s V .. s V + V - 1
+ * that are its outputs, less its shift.  With t0 = m_lo / 16, lane g of the column (g < M / 16) takes table entry t0 + g and expands
+ * exactly the XL_PH_STRIDE phases m = 16 (t0 + g) .. + 15 -- no step before its first phase; phase m belongs to row position
+ * m + shift - s V and is stored where m lies in the window.  m_lo - 16 t0 <= 15 and m_hi - m_lo <= V, so the M / 16 lanes cover the
+ * window but for at most xl_grid_extra() phases, which the last lane reaches by stepping on from its running phase. */
+XL_HD uint32_t xl_grid_extra(uint32_t M, uint32_t V) { return V + (XL_PH_STRIDE - 1u) > M ? V + (XL_PH_STRIDE - 1u) - M : 0u; }
+
+typedef struct XlGridDuty {
+  XlBnd bnd;      /* as XlColDuty */
+  uint32_t shift; /* q - k of the column */
+  uint32_t ma;    /* the lane's first phase, 16 (t0 + g): the output its table entry belongs to */
+  uint32_t pos;   /* row position of phase ma, ma + shift - s V; below 0 (wrapped) where ma lies before the window */
+  uint32_t rel;   /* ma - m_lo (wrapped): phase ma + i is stored exactly when rel + i < span in unsigned arithmetic */
+  uint32_t span;  /* m_hi - m_lo; 0 when the lane has nothing to store (vacant column, empty window, entry beyond the window) */
+  uint32_t tab;   /* t0 + g, the entry of the column's part of the phase table (0 when span = 0) */
+} XlGridDuty;
+XL_HD XlGridDuty xl_grid_duty(uint32_t j0_ref, uint32_t delta, uint32_t D, XlPos p, uint32_t V, uint32_t s, uint32_t g, int vacant) {
+  XlGridDuty d;
+  uint32_t qlo, qhi, m_lo, m_hi;
+  d.bnd.j0 = xl_merge_j0(j0_ref, delta, D), d.bnd.D = D, d.bnd.S = p.S, d.bnd.G = p.G, d.bnd.flags = p.pad;
+  d.bnd.K = xl_merge_outputs(j0_ref, delta, D, p);
+  d.shift = xl_merge_shift(j0_ref, delta, D);
+  qlo = s * V > d.shift ? s * V : d.shift;
+  qhi = s * V + V < d.shift + d.bnd.K ? s * V + V : d.shift + d.bnd.K;
+  m_lo = qlo - d.shift;
+  m_hi = qhi > qlo ? qhi - d.shift : m_lo;
+  d.ma = (m_lo & ~(XL_PH_STRIDE - 1u)) + g * XL_PH_STRIDE;
+  d.pos = d.ma + d.shift - s * V;
+  d.rel = d.ma - m_lo;
+  d.span = !vacant && d.ma < m_hi ? m_hi - m_lo : 0u;
+  d.tab = d.span ? d.ma >> XL_PH_SHIFT : 0u;
+  return d;
+}
+
+/* floor(x / d) from rcp = xl_rcp32(d): a multiply-high and one correction, exact for every 32-bit x and d >= 1
+ * (x rcp / 2^32 lies in (x / d - 1, x / d]).  The inverse launches get the reciprocals of S and D as arguments. */
+XL_HD uint32_t xl_rcp32(uint32_t d) { return d > 1u ? (uint32_t)(0x100000000ull / d) : 0xFFFFFFFFu; }
+XL_HD uint32_t xl_div_rcp(uint32_t x, uint32_t d, uint32_t rcp) {
+  const uint32_t q = (uint32_t)(((uint64_t)x * rcp) >> 32);
+  return q + (x - q * d >= d ? 1u : 0u);
+}
+/* xl_bnd_next without a division: rS = xl_rcp32(b.S), rD = xl_rcp32(b.D) */
+XL_HD uint32_t xl_bnd_next_rcp(const XlBnd b, uint32_t rS, uint32_t rD, uint32_t m) {
+  uint32_t g, n, nb;
+  if (b.flags & XL_POS_NORENORM) return 0xFFFFFFFFu;
+  if (b.G <= 1u) return b.K;
+  g = xl_div_rcp(b.j0 + m * b.D, b.S, rS);
+  if (g + 1u >= b.G) return b.K;
+  n = (g + 1u) * b.S;
+  nb = n > b.j0 ? xl_div_rcp(n - b.j0 + b.D - 1u, b.D, rD) : 0u;
+  return nb < b.K ? nb : b.K;
+}
+
 #endif /* XL_GRID_H_ */

@@ -23,7 +23,7 @@
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
-// Registers: 154, three waves per SIMD.  (Held to 128 for four the kernel spills 24 registers and runs 35 % slower; a form that takes
+// Registers: 164 (154 before the phase expansion moved to the table's grid), three waves per SIMD.  (Held to 128 for four the kernel spills 24 registers and runs 35 % slower; a form that takes
 // its two rounds over the rows instead of the columns fits 120 -- and loses more, 77 against 49 us per block at 4096 clients: its store
 // instructions write 128-byte runs whose lines the other round completes microseconds later.  profiles/r05_inverse_cut32.txt)
 #define XLI32_WPE 3
@@ -76,16 +76,12 @@ __global__ __launch_bounds__(64 * XLI32_WAVES) __attribute__((amdgpu_waves_per_e
   for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(z[i]));  // (all 32 outputs now, not the last stage's operands: fewer registers)
   // ---- what the walk and the stores need of the two columns, and the walk's table entries (the table holds every 16th phase)
   const uint32_t gq = xli32_walk_gq(j);
-  XlBnd ebnd[2];
-  uint32_t m0[2], cnt[2];  // the column's output index of the first phase to expand, phases to expand (0: none)
-  v2f pe[2];
+  v2f pe[2];  // (xl_grid.h: the 16 phases of entry t0 + gq of the column's window in the segment)
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
-    const XlColDuty du = xl_col_duty(a.j0_ref, ce[r].delta, a.D, a.pos, a.V, s, gq, ce[r].out_off == 0xFFFFFFFFu);
-    ebnd[r] = du.bnd, cnt[r] = xl_col_duty_count(du);
-    pe[r] = reinterpret_cast<const v2f *>(a.phtab)[du.ok ? (ce[r].out_off >> XL_PH_SHIFT) + du.tab : 0u];
-    if (gq == 0u) *reinterpret_cast<v4u *>(reg + xli32_meta(8u * r + xli32_walk_c8(j))) = (v4u){ce[r].out_off, du.shift, ce[r].out_off != 0xFFFFFFFFu ? du.bnd.K : 0u, du.ibeg};
-    m0[r] = du.m0 | du.ibeg << 31;  // (ibeg kept for the walk's LDS address)
+    const XlGridDuty du = xl_grid_duty(a.j0_ref, ce[r].delta, a.D, a.pos, a.V, s, gq, ce[r].out_off == 0xFFFFFFFFu);
+    pe[r] = reinterpret_cast<const v2f *>(a.phtab)[du.span ? (ce[r].out_off >> XL_PH_SHIFT) + du.tab : 0u];
+    if (gq == 0u) *reinterpret_cast<v4u *>(reg + xli32_meta(8u * r + xli32_walk_c8(j))) = (v4u){ce[r].out_off, du.shift, ce[r].out_off != 0xFFFFFFFFu ? du.bnd.K : 0u, 0u};
   }
   {
     const unsigned char *const twp = reg + xli32_tw(0u, xli32_load_m1(j));
@@ -119,12 +115,9 @@ __global__ __launch_bounds__(64 * XLI32_WAVES) __attribute__((amdgpu_waves_per_e
 #pragma unroll
     for (int k = 0; k < 4; ++k) xl_fft4_inverse<v2f, XlpFftOps>(y[k]);
     // ---- the phases of the round's 8 x 128 shared points
-    if (cnt[r] != 0u) {
-      const uint32_t ibeg = m0[r] >> 31;
-      unsigned char *const pw = reg + xli32_phase(xli32_walk_c8(j), gq * XL_PH_STRIDE + ibeg);
-      xl_phase_walk(pe[r], m0[r] & 0x7FFFFFFFu, cnt[r], (v2f){ce[r].incr.x, ce[r].incr.y}, ebnd[r],
-                    [&](uint32_t i, v2f phs) { *reinterpret_cast<v2f *>(pw + i * 8u) = phs; });
-    }
+    const XlGridDuty du = xl_grid_duty_again(a.j0_ref, ce[r].delta, ce[r].out_off, a.D, a.pos, a.V, s, gq);
+    xl_phase_expand(pe[r], du, gq == 7u, xl_grid_extra(M, a.V), (v2f){ce[r].incr.x, ce[r].incr.y}, a.rcp_S, a.rcp_D,
+                    [&](uint32_t i, v2f phs) { *reinterpret_cast<v2f *>(reg + xli32_phase(xli32_walk_c8(j), du.pos + i)) = phs; });
     __builtin_amdgcn_wave_barrier();
     // ---- epilogue: lane (cc, t) holds the shared points t + 32 g of columns 2 k + cc: a store instruction (fixed k, g) covers 32
     // consecutive outputs of each of two columns

@@ -53,13 +53,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
   // ---- the lane's client column in roles 3 (reader), 4, phase expansion and epilogue: column 8 w + (j >> 3).  It lies on the
   // class's shared grid with its own offset (xl_grid.h): its output k is the shared point q = k + shift, shift in {0, 1}, and
-  // it owns K outputs in this call.  Phase expansion duty of lane (column, g): the phases of the shared points 16 g .. 16 g + 15
-  // of the segment, from the one table entry requested here (the table holds every XL_PH_STRIDE-th phase).
+  // it owns K outputs in this call.  Phase expansion duty of lane (column, g): the 16 phases of entry t0 + g of the column's window in
+  // the segment (xl_grid.h: xl_grid_duty), from the one table entry requested here (the table holds every XL_PH_STRIDE-th phase).
   static_assert(XL_PH_STRIDE == 16u, "one table entry per lane: 8 entries per column and segment");
   const uint32_t c8 = xli8_col(j), u = xli8_u(j);
   const XlpCol ce = a.cols[cg * XLP_COLS + sub * CW + 8u * w + c8];
-  const XlColDuty du = xl_col_duty(a.j0_ref, ce.delta, a.D, a.pos, a.V, s, u, ce.out_off == 0xFFFFFFFFu);
-  const v2f pe = reinterpret_cast<const v2f *>(a.phtab)[du.ok ? (ce.out_off >> XL_PH_SHIFT) + du.tab : 0u];
+  const XlGridDuty du = xl_grid_duty(a.j0_ref, ce.delta, a.D, a.pos, a.V, s, u, ce.out_off == 0xFFFFFFFFu);
+  const v2f pe = reinterpret_cast<const v2f *>(a.phtab)[du.span ? (ce.out_off >> XL_PH_SHIFT) + du.tab : 0u];
   __syncthreads();  // (the table; the tile loads are still travelling)
   unsigned char *const reg = region[w];
   // ---- roles 1, 2: Z_m1[t] = 16-point inverse transform over m2, times w^{m1 t}; role 3: into the exchange rows
@@ -90,11 +90,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   xl_fft8_inverse<v2f, XlpFftOps>(y[0]);
   xl_fft8_inverse<v2f, XlpFftOps>(y[1]);
   // ---- the phases of the wave's 8 x 128 shared points
-  if (du.ok) {
-    unsigned char *const pw = reg + xli8_phase(c8, u * XL_PH_STRIDE + du.ibeg);
-    xl_phase_walk(pe, du.m0, xl_col_duty_count(du), (v2f){ce.incr.x, ce.incr.y}, du.bnd,
-                  [&](uint32_t i, v2f phs) { *reinterpret_cast<v2f *>(pw + i * 8u) = phs; });
-  }
+  xl_phase_expand(pe, du, u == 7u, xl_grid_extra(M, a.V), (v2f){ce.incr.x, ce.incr.y}, a.rcp_S, a.rcp_D,
+                  [&](uint32_t i, v2f phs) { *reinterpret_cast<v2f *>(reg + xli8_phase(c8, du.pos + i)) = phs; });
   __builtin_amdgcn_wave_barrier();
   // ---- epilogue: lane (c8, u) holds the shared points 16 g + 8 e + u of its column: a store instruction (fixed g, e) covers 8
   // consecutive outputs per column

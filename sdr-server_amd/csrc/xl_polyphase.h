@@ -68,6 +68,7 @@ struct XlpArgs {
   uint32_t n0, n1;
   uint32_t fmt;
   XlPos pos;           // stream position of the call (per-column output counts, block boundaries, the NCO role)
+  uint32_t rcp_S, rcp_D;  // (set by xlp_launch_inverse) xl_rcp32 of pos.S and D: the phase expansion's block ends without divisions
   uint32_t j0_ref;     // shared grid of the class in this call: j0 of its virtual reference client (xl_grid.h)
   uint32_t base;       // sample index in [in0 | in1] coordinates of the first tap of shared point q = 0
   uint32_t Kq;         // shared points evaluated, q < Kq

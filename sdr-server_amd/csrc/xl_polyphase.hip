@@ -346,9 +346,8 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   // the epilogue's operands.  A column's client lies on the class's shared grid with its own offset (xl_grid.h):
   // its output k is the shared point q = k + shift, shift in {0, 1}, and it owns K_c outputs in this call.
   // NCO phases: the table holds every XL_PH_STRIDE-th phase; after the transforms lane (en, gq) = (j / GQ, j % GQ),
-  // GQ = M / XL_PH_STRIDE, expands the phases of the shared points gq*XL_PH_STRIDE .. of the segment for the wave's
-  // column en into that column's tile row (free by then), and every lane picks the phases of its own points
-  // l + L r from there.  The one table entry a lane needs is requested here, before the transforms.
+  // GQ = M / XL_PH_STRIDE, expands the phases of table entry t0 + gq of the wave's column en (xl_grid.h: xl_grid_duty) into
+  // that column's tile row (free by then), and every lane picks the phases of its own points l + L r from there.  The one table entry a lane needs is requested here, before the transforms.
   constexpr uint32_t GQ = M / XL_PH_STRIDE;
   static_assert(WPC * GQ == 64u, "one expansion duty per lane");
   const v2f *__restrict__ ph = reinterpret_cast<const v2f *>(a.phtab);
@@ -373,10 +372,13 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
     rel[n] = l - lo;
     span[n] = hi > lo ? hi - lo : 0u;
   }
-  const uint32_t en = j / GQ, gq = j % GQ;  // expansion duty: column en of the wave, shared points s V + gq*XL_PH_STRIDE ..
+  const uint32_t en = j / GQ, gq = j % GQ;  // expansion duty: column en of the wave, entry gq of its window in this segment
   const XlpCol ce = a.cols[colbase + en];
-  const XlColDuty du = xl_col_duty(a.j0_ref, ce.delta, a.D, a.pos, a.V, s, gq, ce.out_off == 0xFFFFFFFFu);
-  const v2f pe = ph[du.ok ? (ce.out_off >> XL_PH_SHIFT) + du.tab : 0u];
+  v2f pe;
+  {
+    const XlGridDuty du = xl_grid_duty(a.j0_ref, ce.delta, a.D, a.pos, a.V, s, gq, ce.out_off == 0xFFFFFFFFu);
+    pe = ph[du.span ? (ce.out_off >> XL_PH_SHIFT) + du.tab : 0u];
+  }
   __syncthreads();
   const unsigned long long t_loaded = a.trace ? wall_clock64() : 0ull;
   v2f u[4][4];
@@ -391,12 +393,12 @@ XL_DEV void xlp_inverse_body(const XlpArgs &a) {
   __builtin_amdgcn_wave_barrier();
   xlp_dft<+1, 4, M, P>(u, rows, tw, l, rs);
   __builtin_amdgcn_wave_barrier();
-  if (du.ok) {
+  {
     v2f *__restrict__ row = tile[WPC * w + en];
     const uint32_t ers = XLP_SWZ_ROW(WPC * w + en);
-    const uint32_t p0 = gq * XL_PH_STRIDE + du.ibeg;
-    xl_phase_walk(pe, du.m0, xl_col_duty_count(du), (v2f){ce.incr.x, ce.incr.y}, du.bnd,
-                  [&](uint32_t i, v2f phs) { row[P::pos(p0 + i, ers)] = phs; });
+    const XlGridDuty du = xl_grid_duty_again(a.j0_ref, ce.delta, ce.out_off, a.D, a.pos, a.V, s, gq);
+    xl_phase_expand(pe, du, gq == GQ - 1u, xl_grid_extra(M, a.V), (v2f){ce.incr.x, ce.incr.y}, a.rcp_S, a.rcp_D,
+                    [&](uint32_t i, v2f phs) { row[P::pos(du.pos + i, ers)] = phs; });
   }
   __builtin_amdgcn_wave_barrier();
   const unsigned long long t_xf = a.trace ? wall_clock64() : 0ull;
@@ -524,7 +526,8 @@ hipError_t xlp_launch_inverse(const XlpArgs &a0, hipStream_t s, hipEvent_t done)
   const uint32_t tiles = a0.nseg * a0.ncg * (XLP_COLS / xly_tile_columns(a0.M));
   const uint32_t kind = xlp_inverse_pick(a0.M, a0.inv_reg, tiles);
   const uint32_t work = kind == 6u ? xlp_inverse32_work(tiles) : tiles;
-  const XlpArgs a = xlp_checked_skip(a0, work);
+  XlpArgs a = xlp_checked_skip(a0, work);
+  a.rcp_S = xl_rcp32(a.pos.S), a.rcp_D = xl_rcp32(a.D);
   const dim3 grid(a.nco_blocks + a.nco_skip + work);
   if (kind == 6u) {
     xlp_inverse32_launch(a, grid, s, done);
