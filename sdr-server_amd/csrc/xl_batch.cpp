@@ -1718,6 +1718,15 @@ fail:
   return b->poisoned ? -EIO : xl_errno_of_last_hip_error();
 }
 
+// one direct launch in describe: its tile height and groups; " lanes<ota>" when it runs fewer than 64 outputs per wave (a window image
+// of 64 exceeds the LDS) and " reads8" when it reads single samples (a group of odd decimation: no 16-byte LDS reads)
+static std::string xl_describe_launch(const Launch &L) {
+  std::string d = " h" + std::to_string(L.ct) + " x " + std::to_string(L.groups.size()) + " groups";
+  if (L.ota < 64u) d += " lanes" + std::to_string(L.ota);
+  if (!L.all_wide) d += " reads8";
+  return d;
+}
+
 extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
   if (b == nullptr || buf == nullptr || n == 0) return -EINVAL;
   if (hipSetDevice(b->device) != hipSuccess) return -EIO;
@@ -1732,7 +1741,7 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
   std::string d = "clients " + std::to_string(b->nalive) + " classes " + std::to_string(b->classes.size()) + " | direct:";
   if (!b->all_built && !b->nco.empty()) d += " (built by the first call that runs all clients on the direct kernel)";
   for (const Launch &L : b->launches)
-    if (!L.groups.empty()) d += " h" + std::to_string(L.ct) + " x " + std::to_string(L.groups.size()) + " groups";
+    if (!L.groups.empty()) d += xl_describe_launch(L);
   d += " | polyphase:";
   if (b->poly.empty()) d += " none";
   for (size_t k = 0; k < b->poly.size(); ++k) {
@@ -1755,7 +1764,7 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
     bool any = false;
     for (const Launch &L : b->launches_rest)
       if (!L.groups.empty()) {
-        d += " h" + std::to_string(L.ct) + " x " + std::to_string(L.groups.size()) + " groups";
+        d += xl_describe_launch(L);
         any = true;
       }
     if (!any) d += " none";
@@ -1776,6 +1785,7 @@ extern "C" int xlating_batch_describe(xlating_batch *b, char *buf, size_t n) {
   }
   if (b->q15_nco == 1u)
     d += " | q15 nco: ahead, " + std::to_string(b->qahead.used) + " used, " + std::to_string(b->qahead.dropped) + " dropped";
+  if (b->exp_flags & 2u) d += " | tap loop: flat priority";  // (XL_EXP_FLATPRIO: every direct launch takes the one-piece tap loop)
   if (b->reserve_r) d += " | side kernel: " + std::to_string(8u * b->reserve_r) + " CUs reserved";
   if (pending) d += " | re-plan pending (client set or options changed: the next process call plans again)";
   const size_t len = std::min(d.size(), n - 1);
