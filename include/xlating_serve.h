@@ -14,7 +14,7 @@
  *     xlating_serve_flush(s); xlating_serve_destroy(s);
  *
  * Per blocks call: the engine call in the configured mode; one resampler-bank feed for the fractional clients (pointers from
- * xlating_batch_outputs_device); one tuner-bank feed for the clients of xlating_serve_set_tune, if there are any; ONE delivery batch
+ * xlating_batch_outputs_device); one tuner-bank feed for the clients of xlating_serve_set_tune, if there are any; one meter launch for the clients of xlating_serve_set_squelch, if there are any; ONE delivery batch
  * holding the final row of every client (key: the client id; 8 bytes a sample in the cf32 family, 4 in the cs16 family and in
  * XL_SERVE_CF32_AS_CS16), which is one launch and one device-to-host copy of exactly those
  * bytes.  xlating_batch_fetch and the banks' _fetch are never called: a fractional client's engine row never crosses to the host, and after an XL_MODE_Q15 call only
@@ -161,6 +161,42 @@ int xlating_serve_set_tune(xlating_serve *s, int client_id, double shift_hz, dou
  * entry's sample is 0 and continues through every later entry, and before the first entry the stream is not rotated.  With it a
  * consumer knows the exact rotation of every delivered sample.  Returns the number of entries written, or -EINVAL. */
 int xlating_serve_tune_log(xlating_serve *s, int client_id, size_t cap, uint64_t *first_sample, int64_t *F, int64_t *R);
+
+/* ---- every family: a squelch per client on a power meter that runs on the device (xlating_meter.h).
+ * A monitor of many narrow channels is mostly quiet channels, and without this each of them pays its bytes over PCIe, through its queue
+ * and out of its descriptor on every call.  A client with a squelch has the mean power of its FINAL row measured on every blocks call
+ * (the resampler's and the tuner's row where those apply; cf32 rows in XL_SERVE_CF32 and XL_SERVE_CF32_AS_CS16, 1.0 = |y| of 1; int16
+ * pairs in XL_SERVE_CS16, 1.0 = full scale): ONE meter launch on the object's stream for all squelched clients, behind the tuner feed
+ * and in front of the pack, with one table copy and one small copy back (counted in xlating_serve_last_ops).  THE HOST WAITS for that
+ * copy, with overlap = 0 and with overlap = 1: the decision is made on the same call's power, before the pack, so a transmission's
+ * first call is delivered whole.  The wait covers the engine call's device time -- a fraction of a millisecond per block against a
+ * call period of tens of milliseconds at 1024 clients.
+ * The policy (csrc/xl_serve_squelch.h), per client and per call with power P, gate closed at first:  P not below open_power (a NaN
+ * included) opens the gate;  while it is open, each call with P < close_power counts, the gate closes once more than hang_calls such
+ * calls came in a row, and a call with close_power <= P < open_power restarts the count;  a closed gate stays closed under open_power.
+ * A call's row is delivered exactly when the gate is open after the step (hang_calls = h still delivers h calls below the close mark).
+ * A power that is not finite opens: a broken stream is never hidden.
+ * A closed row is packed with length 0: it costs no byte of the image, of the device-to-host copy or of the client's queue, nothing
+ * is written to its sink, and to the gain policy, the levels, the gain log and the tune log's sample count it is a call that did not
+ * happen (those count DELIVERED samples; the tuner's phase runs on through the withheld ones).  When every row of a call is closed,
+ * no pack launch and no device-to-host copy are issued.  xlating_serve_outputs_device still gives every row: a spectrum bank sees the
+ * quiet calls too.  With no squelch ever set a call is, launch for launch and byte for byte, what it is without these functions. */
+/* The client's squelch from the next blocks call on (mean power, not dB); a client that has one keeps its gate and takes the new
+ * marks.  The meter object is created with the first call.  Marks of (0, 0) never close: a level meter without a squelch.
+ * 0; -EINVAL: no such client, a mark that is not finite or is negative, open_power < close_power; the meter's errors. */
+int xlating_serve_set_squelch(xlating_serve *s, int client_id, double open_power, double close_power, unsigned hang_calls);
+/* No squelch from the next blocks call on: every row is delivered again.  0 (also for a client that had none), -EINVAL. */
+int xlating_serve_clear_squelch(xlating_serve *s, int client_id);
+/* The latest blocks call's figures: each client's mean power, its gate after the step (1: the row was delivered) and the samples
+ * withheld from it since it joined.  A client without a squelch reports power 0 and an open gate.  Any output array may be NULL.
+ * 0, -EINVAL (an id that is not a client: nothing is filled). */
+int xlating_serve_squelch_state(xlating_serve *s, size_t n, const int *client_ids, double *power, uint8_t *open, uint64_t *withheld_samples);
+/* The client's latest gate changes, at most 64 and at most cap, oldest first: from sample stream_sample[i] of the stream the client
+ * PRODUCED (delivered or not, counted from its first block) the gate is open[i], and at that point the client had been DELIVERED
+ * delivered_sample[i] samples -- the index the gain log and the tune log count in.  Before the first entry the gate is open (a client
+ * is delivered until its squelch first closes); the entries alternate.  Returns the number of entries written, or -EINVAL. */
+int xlating_serve_squelch_log(xlating_serve *s, int client_id, size_t cap, uint64_t *stream_sample, uint64_t *delivered_sample,
+                              uint8_t *open);
 
 void xlating_serve_destroy(xlating_serve *s);
 

@@ -1346,11 +1346,128 @@ class TuneBank:
             pass
 
 
+# ------------------------------------------------------------------------------------------------- power meter (libxlating_meter.so)
+METER_SYMBOLS = ["xlating_meter_create", "xlating_meter_measure_device", "xlating_meter_query", "xlating_meter_wait",
+                 "xlating_meter_power", "xlating_meter_partials", "xlating_meter_last_ops", "xlating_meter_piece_samples",
+                 "xlating_meter_destroy"]
+METER_FMT = {"cf32": 0, "cs16": 1}
+_meterlib = None
+
+
+def meter_library_path():
+    return os.path.join(os.path.dirname(library_path()), "libxlating_meter.so")
+
+
+def meter_lib():
+    """include/xlating_meter.h: the mean power of many device rows in one launch."""
+    global _meterlib
+    if _meterlib is not None:
+        return _meterlib
+    lib()  # (torch's HIP runtime first, see lib())
+    path = meter_library_path()
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    M = C.CDLL(path)
+    M.xlating_meter_create.argtypes = [C.POINTER(C.c_void_p)]
+    M.xlating_meter_create.restype = C.c_int
+    M.xlating_meter_measure_device.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    M.xlating_meter_measure_device.restype = C.c_int
+    for name in ("xlating_meter_query", "xlating_meter_wait"):
+        getattr(M, name).argtypes = [C.c_void_p]
+        getattr(M, name).restype = C.c_int
+    M.xlating_meter_power.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    M.xlating_meter_power.restype = C.c_int
+    M.xlating_meter_partials.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    M.xlating_meter_partials.restype = C.c_int
+    M.xlating_meter_last_ops.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    M.xlating_meter_last_ops.restype = C.c_int
+    M.xlating_meter_piece_samples.argtypes = []
+    M.xlating_meter_piece_samples.restype = C.c_uint
+    M.xlating_meter_destroy.argtypes = [C.c_void_p]
+    M.xlating_meter_destroy.restype = None
+    _meterlib = M
+    return M
+
+
+def meter_piece_samples():
+    return meter_lib().xlating_meter_piece_samples()
+
+
+class Meter:
+    """One `xlating_meter *` (include/xlating_meter.h): the mean power of many device rows of one format by one launch, one table copy
+    and one copy back; one measurement outstanding at a time."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        code = meter_lib().xlating_meter_create(C.byref(h))
+        if code != 0:
+            raise XlatingError("xlating_meter_create", code)
+        self.h = h
+
+    def measure(self, fmt, ptrs, counts, stream=0):
+        """row i: counts[i] samples of `fmt` ("cf32" | "cs16") at device address ptrs[i], read in place, ordered on `stream`"""
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        assert p.size == c.size
+        code = meter_lib().xlating_meter_measure_device(self.h, METER_FMT[fmt], p.size, p.ctypes.data, c.ctypes.data, stream)
+        if code != 0:
+            raise XlatingError("xlating_meter_measure_device", code)
+
+    def query(self):
+        code = meter_lib().xlating_meter_query(self.h)
+        if code < 0:
+            raise XlatingError("xlating_meter_query", code)
+        return bool(code)
+
+    def wait(self):
+        code = meter_lib().xlating_meter_wait(self.h)
+        if code != 0:
+            raise XlatingError("xlating_meter_wait", code)
+
+    def power(self, i):
+        """-> (mean power as a Python float, samples) of row i of the latest measurement, which is done"""
+        p, n = C.c_double(0), C.c_uint64(0)
+        code = meter_lib().xlating_meter_power(self.h, i, C.byref(p), C.byref(n))
+        if code != 0:
+            raise XlatingError("xlating_meter_power", code)
+        return p.value, n.value
+
+    def partials(self, i):
+        """-> uint64 [pieces]: row i's partials as the kernel left them (cf32: the float32's bits in the low half)"""
+        n = meter_lib().xlating_meter_partials(self.h, i, 0, None)
+        if n < 0:
+            raise XlatingError("xlating_meter_partials", n)
+        out = np.zeros(n, np.uint64)
+        if n > 0:
+            n = meter_lib().xlating_meter_partials(self.h, i, n, out.ctypes.data)
+            if n < 0:
+                raise XlatingError("xlating_meter_partials", n)
+        return out
+
+    def last_ops(self):
+        """-> (kernel launches, memory copies) the latest measurement issued"""
+        a, b = C.c_uint(0), C.c_uint(0)
+        meter_lib().xlating_meter_last_ops(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            meter_lib().xlating_meter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 SERVE_SYMBOLS = ["xlating_serve_create", "xlating_serve_request", "xlating_serve_remove", "xlating_serve_blocks_host",
                  "xlating_serve_blocks_device", "xlating_serve_flush", "xlating_serve_outputs_device", "xlating_serve_dropped",
                  "xlating_serve_engine", "xlating_serve_last_ops", "xlating_serve_sink_stats", "xlating_serve_destroy",
                  "xlating_serve_set_gain", "xlating_serve_set_auto_gain", "xlating_serve_enable_levels", "xlating_serve_levels",
-                 "xlating_serve_gain_log", "xlating_serve_set_tune", "xlating_serve_tune_log"]
+                 "xlating_serve_gain_log", "xlating_serve_set_tune", "xlating_serve_tune_log", "xlating_serve_set_squelch",
+                 "xlating_serve_clear_squelch", "xlating_serve_squelch_state", "xlating_serve_squelch_log"]
 SERVE_FAMILY = {"cf32": 0, "cs16": 1, "cf32-cs16": 2}  # (2: the cf32 family, narrowed to cs16 by the delivery)
 _vlib = None
 
@@ -1374,6 +1491,7 @@ def serve_lib():
         return _vlib
     resample_lib()  # (torch's HIP runtime first, see lib(); the libraries this one links)
     tune_lib()
+    meter_lib()
     path = serve_library_path()
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
@@ -1434,6 +1552,14 @@ def serve_lib():
     V.xlating_serve_set_tune.restype = C.c_int
     V.xlating_serve_tune_log.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     V.xlating_serve_tune_log.restype = C.c_int
+    V.xlating_serve_set_squelch.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_uint]
+    V.xlating_serve_set_squelch.restype = C.c_int
+    V.xlating_serve_clear_squelch.argtypes = [C.c_void_p, C.c_int]
+    V.xlating_serve_clear_squelch.restype = C.c_int
+    V.xlating_serve_squelch_state.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_serve_squelch_state.restype = C.c_int
+    V.xlating_serve_squelch_log.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    V.xlating_serve_squelch_log.restype = C.c_int
     V.xlating_serve_destroy.argtypes = [C.c_void_p]
     V.xlating_serve_destroy.restype = None
     _vlib = V
@@ -1648,6 +1774,36 @@ class Serve:
         if n < 0:
             raise XlatingError("xlating_serve_tune_log", n)
         return [(int(f[i]), int(F[i]), int(R[i])) for i in range(n)]
+
+    def set_squelch(self, client_id, open_power, close_power=None, hang_calls=0):
+        """every family: the client's rows are delivered only while its gate is open (mean power of its final row against the two
+        marks, with hysteresis and a hang time in calls; include/xlating_serve.h), from the next blocks call on"""
+        close_power = open_power if close_power is None else close_power
+        code = serve_lib().xlating_serve_set_squelch(self.h, client_id, float(open_power), float(close_power), int(hang_calls))
+        if code != 0:
+            raise XlatingError("xlating_serve_set_squelch", code)
+
+    def clear_squelch(self, client_id):
+        code = serve_lib().xlating_serve_clear_squelch(self.h, client_id)
+        if code != 0:
+            raise XlatingError("xlating_serve_clear_squelch", code)
+
+    def squelch_state(self, cids):
+        """-> dict of arrays [n]: power (float64), open (uint8) of the latest blocks call, withheld_samples (uint64) since each joined"""
+        a = np.ascontiguousarray(cids, dtype=np.intc)
+        out = {"power": np.zeros(a.size, np.float64), "open": np.zeros(a.size, np.uint8), "withheld_samples": np.zeros(a.size, np.uint64)}
+        code = serve_lib().xlating_serve_squelch_state(self.h, a.size, a.ctypes.data, *[v.ctypes.data for v in out.values()])
+        if code != 0:
+            raise XlatingError("xlating_serve_squelch_state", code)
+        return out
+
+    def squelch_log(self, client_id, cap=64):
+        """-> [(stream_sample, delivered_sample, open)]: the client's latest gate changes, oldest first"""
+        a, b, o = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint8)
+        n = serve_lib().xlating_serve_squelch_log(self.h, client_id, cap, a.ctypes.data, b.ctypes.data, o.ctypes.data)
+        if n < 0:
+            raise XlatingError("xlating_serve_squelch_log", n)
+        return [(int(a[i]), int(b[i]), int(o[i])) for i in range(n)]
 
     def dropped(self, cap=4096):
         ids = (C.c_int * cap)()

@@ -1,6 +1,6 @@
 // xl_serve.cpp -- the serve object (include/xlating_serve.h): one band on one GPU, from the wire request to the sink.  It owns an
-// engine, at most one resampler bank of its family, at most one tuner bank, a delivery object and the sinks, and calls nothing but their
-// public functions; the ordering rule between them is stated in the header and kept in xl_serve_run below.  No arithmetic on samples
+// engine, at most one resampler bank of its family, at most one tuner bank, at most one power meter, a delivery object and the sinks, and
+// calls nothing but their public functions; the ordering rule between them is stated in the header and kept in xl_serve_run below.  No arithmetic on samples
 // happens here.
 #include "../../include/xlating_serve.h"
 
@@ -15,6 +15,7 @@
 
 #include "../../include/xlating_batch.h"
 #include "../../include/xlating_delivery.h"
+#include "../../include/xlating_meter.h"
 #include "../../include/xlating_resample.h"
 #include "../../include/xlating_resample_q15.h"
 #include "../../include/xlating_sinks.h"
@@ -22,6 +23,7 @@
 #include "../../include/xlating_wire.h"
 #include "xl_common.h"
 #include "xl_serve_gain.h"
+#include "xl_serve_squelch.h"
 
 namespace {
 
@@ -50,6 +52,14 @@ struct XlServeClient {
   uint64_t clipped_total = 0;
   uint32_t peak_bits = 0, clipped = 0, nans = 0;  // of the latest call queued to its sink
   int8_t level_gain = 0;                          // the gain that call was packed with
+  // xlating_serve_set_squelch (xl_serve_squelch.h holds the policy and the log)
+  bool sq_on = false;
+  XlServeSquelch sq = {};
+  XlServeSquelchLog sq_log = {};
+  uint64_t produced = 0;   // samples of its final rows so far, delivered or withheld
+  uint64_t withheld = 0;   // of those, the samples of the calls its gate was closed in
+  double sq_power = 0.0;   // the latest call's mean power (0 while the client has no squelch) ...
+  bool sq_open = true;     // ... and gate
 };
 
 }  // namespace
@@ -66,6 +76,7 @@ struct xlating_serve_t {
   xlating_resample_bank *rb = nullptr;       // cf32 family, created with the first fractional client
   xlating_resample_q15_bank *rq = nullptr;   // cs16 family
   xlating_tune_bank *tb = nullptr;           // created with the first xlating_serve_set_tune
+  xlating_meter *mt = nullptr;               // created with the first xlating_serve_set_squelch
   hipStream_t st = nullptr;                  // the feed and the pack launch
   hipEvent_t ev_call = nullptr, ev_pack = nullptr;  // behind the engine call; behind the pack launch
   bool packed = false;                       // ev_pack has been recorded
@@ -73,6 +84,7 @@ struct xlating_serve_t {
   int pending = -1;                          // the ticket not handed to the sinks yet
   std::vector<int> pending_ids;              // its keys that are still owed their row (a client that is forgotten leaves the list)
   std::vector<int> handing;                  // (scratch of a hand-over)
+  std::vector<int> pending_withheld, handing_withheld;  // the ticket's keys whose gate was closed (ascending): rows of length 0
   bool levels_on = false;                    // xlating_serve_enable_levels
   bool pending_gained = false, handing_gained = false;  // the ticket is one of pack_device_cs16_gain ...
   std::map<int, int8_t> pending_gain, handing_gain;     // ... packed with these gains, by client id
@@ -84,6 +96,8 @@ struct xlating_serve_t {
   std::vector<int> ids, rs_ids, tn_ids;
   std::vector<const void *> rows, rs_rows, tn_rows;
   std::vector<size_t> lens, rs_lens, tn_lens, bytes;
+  std::vector<const void *> sq_rows;
+  std::vector<size_t> sq_lens, sq_at;
 };
 
 // the bank's functions for either family
@@ -160,6 +174,8 @@ static int xl_serve_deliver(xlating_serve *s, int t) {
     size_t n = 0;
     if ((rc = xlating_delivery_row(s->dlv, t, id, &p, &n)) != 0) break;
     if (n > 0) (void)xlating_sinks_write_bytes(s->sinks, id, p, n);  // (-EPIPE: reported by xlating_sinks_failed below)
+    // a row the squelch withheld: to the levels, the gain policy and the gain log this call did not happen
+    if (std::binary_search(s->handing_withheld.begin(), s->handing_withheld.end(), id)) continue;
     if (!s->handing_gained) continue;
     // the row's level, and what the client's policy makes of it: a new gain holds from the next call that is packed
     XlServeClient &c = s->clients[id];
@@ -171,7 +187,7 @@ static int xl_serve_deliver(xlating_serve *s, int t) {
     if (g != c.gain) xl_serve_gain_log_add(&c.log, c.packed, g);
     c.gain = (int8_t)g;
   }
-  s->handing.clear();
+  s->handing.clear(), s->handing_withheld.clear();
   const int rr = xlating_delivery_release(s->dlv, t);
   xl_serve_reap(s);
   return rc != 0 ? rc : rr;
@@ -184,6 +200,8 @@ static int xl_serve_hand_over(xlating_serve *s) {
   s->pending = -1;
   s->handing.swap(s->pending_ids);
   s->pending_ids.clear();
+  s->handing_withheld.swap(s->pending_withheld);
+  s->pending_withheld.clear();
   s->handing_gain.swap(s->pending_gain), s->handing_gained = s->pending_gained;
   s->pending_gain.clear(), s->pending_gained = false;
   return xl_serve_deliver(s, t);
@@ -374,6 +392,35 @@ static int xl_serve_run(xlating_serve *s) {
     s->launches += l, s->copies += c;
     if ((rc = xl_serve_tuned_rows(s, n, s->ids.data(), s->rows.data(), s->lens.data())) != 0) return rc;
   }
+  // the squelch: the squelched clients' final rows through one meter launch; the host waits for its figures (in both overlap modes:
+  // the decision is made on THIS call's power, before the pack), steps each policy, and a closed row is packed with length 0
+  bool squelched = false;
+  for (const auto &kv : s->clients) squelched = squelched || kv.second.sq_on;
+  s->handing_withheld.clear();  // (scratch until the tickets change hands below: this call's withheld keys)
+  if (squelched) {
+    s->sq_rows.clear(), s->sq_lens.clear(), s->sq_at.clear();
+    for (size_t i = 0; i < n; ++i)
+      if (s->clients[s->ids[i]].sq_on) s->sq_at.push_back(i), s->sq_rows.push_back(s->rows[i]), s->sq_lens.push_back(s->lens[i]);
+    if ((rc = xlating_meter_measure_device(s->mt, s->cfg.family == XL_SERVE_CS16 ? XL_METER_CS16 : XL_METER_CF32, s->sq_at.size(),
+                                           s->sq_rows.data(), s->sq_lens.data(), s->st)) != 0)
+      return rc;
+    unsigned l = 0, c = 0;
+    (void)xlating_meter_last_ops(s->mt, &l, &c);
+    s->launches += l, s->copies += c;
+    if ((rc = xlating_meter_wait(s->mt)) != 0) return rc;
+    for (size_t k = 0; k < s->sq_at.size(); ++k) {
+      const size_t i = s->sq_at[k];
+      XlServeClient &cl = s->clients[s->ids[i]];
+      if ((rc = xlating_meter_power(s->mt, k, &cl.sq_power, nullptr)) != 0) return rc;
+      cl.sq_open = xl_serve_squelch_step(&cl.sq, cl.sq_power) != 0;
+      xl_serve_squelch_log_note(&cl.sq_log, cl.produced, cl.packed, cl.sq_open);
+      if (cl.sq_open) continue;
+      cl.withheld += s->lens[i];
+      cl.produced += s->lens[i];  // (the open rows' below, with `packed`)
+      s->lens[i] = 0;
+      s->handing_withheld.push_back(s->ids[i]);  // (ascending: ids is)
+    }
+  }
   for (size_t i = 0; i < n; ++i) s->bytes[i] = s->lens[i] * s->esz;
   // the pack with gains and levels exactly when somebody asked for either; otherwise the call is what it always was
   bool gained = s->narrow && s->levels_on;
@@ -385,7 +432,7 @@ static int xl_serve_run(xlating_serve *s) {
                 : s->narrow ? xlating_delivery_pack_device_cs16(s->dlv, n, s->ids.data(), s->rows.data(), s->lens.data(), s->st)
                             : xlating_delivery_pack_device(s->dlv, n, s->ids.data(), s->rows.data(), s->bytes.data(), s->st);
   if (t < 0) return t;
-  for (size_t i = 0; i < n; ++i) s->clients[s->ids[i]].packed += s->lens[i];
+  for (size_t i = 0; i < n; ++i) s->clients[s->ids[i]].packed += s->lens[i], s->clients[s->ids[i]].produced += s->lens[i];
   unsigned l = 0, c = 0;
   (void)xlating_delivery_last_ops(s->dlv, &l, &c, &s->d2h_bytes);
   s->launches += l, s->copies += c;
@@ -396,6 +443,7 @@ static int xl_serve_run(xlating_serve *s) {
   // is forgotten, and with it its id in this ticket's list
   const int prev = s->pending;
   s->handing.swap(s->pending_ids);
+  s->handing_withheld.swap(s->pending_withheld);  // (this call's list becomes the pending ticket's, the previous ticket's is handed over)
   s->handing_gain.swap(s->pending_gain), s->handing_gained = s->pending_gained;
   s->pending = t;
   s->pending_ids = s->ids;
@@ -571,6 +619,59 @@ extern "C" int xlating_serve_tune_log(xlating_serve *s, int client_id, size_t ca
   return (int)n;
 }
 
+extern "C" int xlating_serve_set_squelch(xlating_serve *s, int client_id, double open_power, double close_power, unsigned hang_calls) {
+  if (s == nullptr || !xl_serve_squelch_valid(open_power, close_power)) return -EINVAL;
+  const auto it = s->clients.find(client_id);
+  if (it == s->clients.end()) return -EINVAL;
+  if (s->mt == nullptr) {
+    (void)hipSetDevice(s->device);
+    const int rc = xlating_meter_create(&s->mt);
+    if (rc != 0) return rc;
+  }
+  XlServeClient &c = it->second;
+  if (c.sq_on) {  // new marks: the gate stays where it is
+    c.sq.open_power = open_power, c.sq.close_power = close_power, c.sq.hang_calls = hang_calls, c.sq.below = 0u;
+  } else {
+    xl_serve_squelch_init(&c.sq, open_power, close_power, hang_calls);
+    c.sq_on = true;
+  }
+  return 0;
+}
+
+extern "C" int xlating_serve_clear_squelch(xlating_serve *s, int client_id) {
+  if (s == nullptr) return -EINVAL;
+  const auto it = s->clients.find(client_id);
+  if (it == s->clients.end()) return -EINVAL;
+  XlServeClient &c = it->second;
+  if (!c.sq_on) return 0;
+  c.sq_on = false, c.sq_open = true, c.sq_power = 0.0;
+  xl_serve_squelch_log_note(&c.sq_log, c.produced, c.packed, 1);
+  return 0;
+}
+
+extern "C" int xlating_serve_squelch_state(xlating_serve *s, size_t n, const int *client_ids, double *power, uint8_t *open,
+                                           uint64_t *withheld_samples) {
+  if (s == nullptr || (n > 0 && client_ids == nullptr)) return -EINVAL;
+  for (size_t i = 0; i < n; ++i)
+    if (s->clients.count(client_ids[i]) == 0) return -EINVAL;
+  for (size_t i = 0; i < n; ++i) {
+    const XlServeClient &c = s->clients[client_ids[i]];
+    if (power) power[i] = c.sq_power;
+    if (open) open[i] = c.sq_open ? 1u : 0u;
+    if (withheld_samples) withheld_samples[i] = c.withheld;
+  }
+  return 0;
+}
+
+extern "C" int xlating_serve_squelch_log(xlating_serve *s, int client_id, size_t cap, uint64_t *stream_sample, uint64_t *delivered_sample,
+                                         uint8_t *open) {
+  if (s == nullptr || (cap > 0 && (stream_sample == nullptr || delivered_sample == nullptr || open == nullptr))) return -EINVAL;
+  const auto it = s->clients.find(client_id);
+  if (it == s->clients.end()) return -EINVAL;
+  return (int)xl_serve_squelch_log_read(&it->second.sq_log, cap > XL_SERVE_SQUELCH_LOG ? XL_SERVE_SQUELCH_LOG : (uint32_t)cap, stream_sample,
+                                        delivered_sample, open);
+}
+
 extern "C" struct xlating_batch_t *xlating_serve_engine(xlating_serve *s) { return s ? s->eng : nullptr; }
 
 extern "C" int xlating_serve_last_ops(const xlating_serve *s, unsigned *launches_after_engine, unsigned *copies_after_engine,
@@ -593,6 +694,7 @@ extern "C" void xlating_serve_destroy(xlating_serve *s) {
   if (s->rb) xlating_resample_bank_destroy(s->rb);
   if (s->rq) xlating_resample_q15_bank_destroy(s->rq);
   if (s->tb) xlating_tune_bank_destroy(s->tb);
+  if (s->mt) xlating_meter_destroy(s->mt);
   if (s->eng) xlating_batch_destroy(s->eng);
   if (s->ev_call) (void)hipEventDestroy(s->ev_call);
   if (s->ev_pack) (void)hipEventDestroy(s->ev_pack);

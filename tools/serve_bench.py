@@ -27,6 +27,13 @@ client's sink is a pipe, and one reader thread drains them all.
       ramp of its own each: one tuner-bank feed more per call) against the same object untuned, the loops alternating in one
       process as in (b); the untuned loop's spread over its rounds is reported (profiles/tune_bank_vs_pack.txt)
 
+  (g) --squelch FRACTIONS (e.g. 1.0,0.25,0.05): the call period and the bytes to the host per call of Serve (--families, overlap 0
+      and 1) with EVERY client squelched (xlating_serve_set_squelch) and that fraction of the gates open, against the same object
+      with no squelch set, the loops alternating in one process as in (b).  The capture is noise, and the fraction is made by
+      per-client marks: (0, 0) never closes, marks far above the noise never open -- the figures measure bytes, not detection.  Then
+      the meter alone: HIP events around one measurement of the headline call's rows (table upload, launch, copy back) against the
+      plain pack launch of the same rows, alternating in one process (profiles/serve_squelch_vs_parent.txt)
+
 Prints a report; profiles/serve_vs_parent.txt is one run of it on an MI355X."""
 import argparse
 import os
@@ -324,6 +331,101 @@ def run_tune(args, drain, out):
         s.close()
 
 
+def run_squelch(args, family, fractions, drain, out):
+    """the call period with every client squelched and a fraction of the gates open against the same run with no squelch set, per
+    overlap, alternating rounds"""
+    import torch
+
+    x = np.random.default_rng(1).integers(0, 256, BUFFER * args.group, dtype=np.uint8)
+    loops, serves = {}, []
+    for ov in (0, 1):
+        for fr in [None] + fractions:
+            s = make_serve(args.clients, family, ov, args.group, drain, args.out)
+            if fr is not None:
+                nopen = int(round(fr * args.clients))
+                for i, cid in enumerate(s.ids):  # (open gates spread evenly over the band)
+                    is_open = (i * nopen) // args.clients != ((i + 1) * nopen) // args.clients
+                    s.set_squelch(cid, *((0.0, 0.0) if is_open else (1e30, 1e30)), 0)
+            serves.append(s)
+            name = f"overlap={ov} " + ("no squelch " if fr is None else f"open {fr:5.3f} ")
+            loops[name] = (lambda x, s=s: s.blocks_host(x, args.group), torch.cuda.synchronize, s.flush, s)
+    res = {k: [] for k in loops}
+    for rnd in range(args.rounds):
+        for name, (step, sync, flush, _) in loops.items():
+            res[name].append(period(step, sync, flush, x, args.seconds))
+    out.append(f"[squelch {family}] call period, {args.clients} clients x {RATE} Hz, {args.group} blocks per call, sinks: pipes drained by one "
+               f"thread, bursts of {BURST} calls; every client squelched, a fraction of the gates open, against no squelch set")
+    for name, rs in res.items():
+        s = loops[name][3]
+        st = s.squelch_state(s.ids)
+        out.append(f"  {name:22s} ms per call, rounds: " + "  ".join(f"{1e3 * p:8.3f}" for p, _ in rs) +
+                   f"   median {1e3 * float(np.median([p for p, _ in rs])):8.3f}   ops behind the engine call {s.last_ops()[:2]}, bytes to the host "
+                   f"{s.last_ops()[2]}, gates open {int(st['open'].sum())}")
+    for ov in (0, 1):
+        u = [p for p, _ in res[f"overlap={ov} no squelch "]]
+        spread = (max(u) - min(u)) / min(u)
+        out.append(f"  overlap={ov}: the unsquelched loop's spread over its rounds is {100 * spread:.1f} %")
+        for fr in fractions:
+            t = [p for p, _ in res[f"overlap={ov} open {fr:5.3f} "]]
+            out.append(f"    open {fr:5.3f}: squelched / unsquelched (medians) = {float(np.median(t) / np.median(u)):.3f}")
+    out.append(f"  clients dropped by back-pressure: {[len(s.dropped()) for s in serves]}")
+    for s in serves:
+        s.close()
+
+
+def run_meter(args, out):
+    """one measurement of the headline call's rows (table upload, launch, copy back) against the plain pack launch of the same rows,
+    in turn, args.rounds rounds of args.pack_iters each"""
+    import torch
+
+    esz, rows = 8, args.group * (BUFFER // 2 // 42)
+    n = args.clients
+    src = (0.3 * torch.randn((n * (rows * esz + 64) // 4,), dtype=torch.float32, device="cuda")).view(torch.uint8)
+    ptrs = [src.data_ptr() + i * (rows * esz + 64) for i in range(n)]
+    d, m = xl.Delivery(2), xl.Meter()
+    st = torch.cuda.Stream()
+    keys = list(range(n))
+
+    def timed(what):
+        a, b = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        with torch.cuda.stream(st):
+            a.record()
+            if what == "pack":
+                t = d.pack(keys, ptrs, [rows * esz] * n, st.cuda_stream)
+            else:
+                m.measure("cf32" if what == "meter cf32" else "cs16", ptrs, [rows if what == "meter cf32" else 2 * rows] * n, st.cuda_stream)
+            b.record()
+        if what == "pack":
+            d.wait(t)
+            d.release(t)
+        else:
+            m.wait()
+        st.synchronize()
+        return a.elapsed_time(b)
+
+    names = ("pack", "meter cf32", "meter cs16")
+    for what in names:
+        for _ in range(3):
+            timed(what)
+    med = {k: [] for k in names}
+    for rnd in range(args.rounds):
+        for what in names:
+            med[what].append(float(np.median([timed(what) for _ in range(args.pack_iters)])))
+    total = n * rows * esz
+    label = {"pack": "table upload + plain pack launch (read + write)", "meter cf32": "table upload + meter launch + copy back, cf32 rows",
+             "meter cs16": "the same bytes measured as cs16 rows"}
+    out.append(f"[meter] {n} rows of {rows * esz} bytes = {total / 1e6:.1f} MB; HIP events on the launch stream, {args.rounds} alternating rounds, "
+               f"median of {args.pack_iters} each; {m.last_ops()} launches, copies per measurement")
+    for k in names:
+        v = med[k]
+        out.append(f"  {label[k]:52s} ms, rounds: " + "  ".join(f"{t:7.3f}" for t in v) +
+                   f"   median {float(np.median(v)):.3f} ms, spread {100 * (max(v) - min(v)) / min(v):.1f} %, {total / float(np.median(v)) / 1e6:.0f} GB/s read")
+    p = float(np.median(med["pack"]))
+    out.append(f"  meter / plain pack: cf32 {float(np.median(med['meter cf32'])) / p:.2f}, cs16 {float(np.median(med['meter cs16'])) / p:.2f}")
+    d.close()
+    m.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--clients", type=int, default=1024)
@@ -335,6 +437,8 @@ def main(argv=None):
     ap.add_argument("--pack", action="store_true", help="only (a): the two pack launches against a device-to-device copy")
     ap.add_argument("--gain", action="store_true", help="only (e): the pack launch with gains and levels against the narrowing pack launch")
     ap.add_argument("--tune", action="store_true", help="only (f): the call with every client tuned against the same run untuned")
+    ap.add_argument("--squelch", default=None, metavar="FRACTIONS",
+                    help="only (g): every client squelched with these fractions of the gates open (e.g. 1.0,0.25,0.05) against no squelch, then the meter against the pack launch")
     ap.add_argument("--out", default="/tmp/serve_bench_out")
     ap.add_argument("--report", default=None)
     a = ap.parse_args(argv)
@@ -344,7 +448,13 @@ def main(argv=None):
     resource.setrlimit(resource.RLIMIT_NOFILE, (hard if hard != resource.RLIM_INFINITY else 1 << 16, hard))
     os.makedirs(a.out, exist_ok=True)
     out = [f"serve_bench: {xl.device_info()}"]
-    if a.tune:
+    if a.squelch:
+        drain = Drain()
+        for family in a.families.split(","):
+            run_squelch(a, family, [float(v) for v in a.squelch.split(",")], drain, out)
+        drain.close()
+        run_meter(a, out)
+    elif a.tune:
         drain = Drain()
         run_tune(a, drain, out)
         drain.close()
@@ -352,7 +462,7 @@ def main(argv=None):
         run_gain(a, out)
     else:
         run_pack(a, out)
-    if not a.pack and not a.gain and not a.tune:
+    if not a.pack and not a.gain and not a.tune and not a.squelch:
         drain = Drain()
         for family in a.families.split(","):
             run_periods(a, family, drain, out)

@@ -18,7 +18,13 @@ int16 values are y * 2^(15 + gain_log2); before the first line the gain is 0 -- 
 "client_index seconds shift_hz ramp_hz_per_s" (client_index counts the --client options from 0; '#' starts a comment) and is applied
 before the first call whose first band sample is at or after `seconds`; every client so tuned also gets <out>/<id>.tune: lines
 "first_sample F R" from its tune log -- from that sample of the file on the steps are F and R (turns * 2^64 per sample and per
-sample^2), the phase 0 at the first line's sample and continuous from there.  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
+sample^2), the phase 0 at the first line's sample and continuous from there.  --squelch OPEN_DB[:CLOSE_DB[:HANG]] (every variant) gives
+every client a squelch (xlating_serve_set_squelch): the marks in dBFS of the mean power of its final row (0 dBFS: |y| of 1; with
+--variant q15 full scale), converted here to powers as 10^(dB / 10); CLOSE_DB defaults to OPEN_DB, HANG (calls) to 0; write it with '=' (--squelch=-20:-40:2), as the
+marks begin with a minus sign.  A client's file
+then holds only the calls its gate was open in, and <out>/<id>.squelch its gate changes: lines "stream_sample delivered_sample open"
+-- from that sample of the stream the client produced the gate is `open`, and the file held delivered_sample samples at that point --
+and a last line "withheld_samples N".  No fetch of the engine's or the bank's arena happens anywhere: per block one pack
 launch and one copy of exactly the delivered bytes."""
 import argparse
 import os
@@ -37,7 +43,7 @@ DTYPES = replay_iq.DTYPES
 
 def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144, lpf_cutoff_rate=5, variant="optimized",
            gzip=False, writer_threads=2, waterfall_width=None, any_rate=False, q15_kernel=0, q15_nco=0, overlap=False, cs16_out=False, gain=None,
-           auto_gain=False, tune=None):
+           auto_gain=False, tune=None, squelch=None):
     """replay_iq.replay's arguments and its triple: {client_id: (center_hz, rate_hz)} of the admitted requests, [(center, rate,
     failure_details)] of the refused ones, and the counters -- blocks, and the sinks' own bytes_written and blocks_dropped
     (xlating_serve_sink_stats: what replay_iq reads from its Sinks objects)."""
@@ -74,6 +80,8 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
                 serve.set_gain(cid, gain)
             if auto_gain:
                 serve.set_auto_gain(cid, True)
+        if squelch is not None:
+            serve.set_squelch(cid, *squelch)
         if bank is not None and rate >= waterfall_width:
             streams[cid], rows[cid], samples[cid] = bank.add(rate), [], 0
     elem = np.dtype(DTYPES[fmt]).itemsize
@@ -123,6 +131,14 @@ def replay(path, fmt, band_rate, band_freq, clients, out_dir, buffer_size=262144
         with open(os.path.join(out_dir, f"{cid}.tune"), "w") as f:
             for first, F, R in serve.tune_log(cid):
                 f.write(f"{first} {F} {R}\n")
+    if squelch is not None:
+        ids = sorted(admitted)
+        withheld = serve.squelch_state(ids)["withheld_samples"].tolist() if ids else []
+        for cid, total in zip(ids, withheld):
+            with open(os.path.join(out_dir, f"{cid}.squelch"), "w") as f:
+                for stream_sample, delivered_sample, is_open in serve.squelch_log(cid):
+                    f.write(f"{stream_sample} {delivered_sample} {is_open}\n")
+                f.write(f"withheld_samples {total}\n")
     for cid, sid in streams.items():
         rows[cid].append(bank.take_rows(sid)[1])
         px = np.concatenate(rows[cid])[:samples[cid] // admitted[cid][1]]
@@ -161,7 +177,23 @@ def parse_args(argv=None):
                     help="with --cs16-out: the object picks each client's gain from its level; also writes <id>.gain")
     ap.add_argument("--tune", default=None, metavar="FILE",
                     help="lines 'client_index seconds shift_hz ramp_hz_per_s': tune running clients; also writes <id>.tune")
+    ap.add_argument("--squelch", default=None, metavar="OPEN_DB[:CLOSE_DB[:HANG]]",
+                    help="deliver a client's call only while its gate is open: marks in dBFS of its mean power, hang time in calls; "
+                         "also writes <id>.squelch")
     return ap.parse_args(argv)
+
+
+def parse_squelch(text):
+    """"OPEN_DB[:CLOSE_DB[:HANG]]" -> (open_power, close_power, hang_calls): dBFS to mean power on the host"""
+    f = text.split(":")
+    if not 1 <= len(f) <= 3:
+        raise ValueError("--squelch OPEN_DB[:CLOSE_DB[:HANG]]")
+    open_db = float(f[0])
+    close_db = float(f[1]) if len(f) > 1 and f[1] != "" else open_db
+    hang = int(f[2]) if len(f) > 2 else 0
+    if close_db > open_db or hang < 0:
+        raise ValueError("--squelch: CLOSE_DB may not lie above OPEN_DB, HANG may not be negative")
+    return 10.0 ** (open_db / 10.0), 10.0 ** (close_db / 10.0), hang
 
 
 def read_tune_file(path):
@@ -180,7 +212,7 @@ def main(argv=None):
     adm, rej, st = replay(a.iq_file, a.format, a.band_rate, a.band_freq, clients, a.out, a.buffer_size, a.lpf_cutoff_rate, a.variant,
                           a.gzip, waterfall_width=a.waterfall_width, any_rate=a.any_rate, q15_kernel=a.q15_kernel, q15_nco=a.q15_nco,
                           overlap=a.overlap, cs16_out=a.cs16_out, gain=a.gain, auto_gain=a.auto_gain,
-                          tune=read_tune_file(a.tune) if a.tune else None)
+                          tune=read_tune_file(a.tune) if a.tune else None, squelch=parse_squelch(a.squelch) if a.squelch else None)
     ext = "cs16" if a.variant == "q15" or a.cs16_out else "cf32"
     for cid, (c, r) in adm.items():
         print(f"client {cid}: center {c} Hz rate {r} Hz -> {a.out}/{cid}.{ext}{'.gz' if a.gzip else ''}")
